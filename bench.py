@@ -32,6 +32,15 @@ GPU) and passes their one JSON line through.
 The timed region runs with the per-kernel HIP-event timers OFF and one host poll at its end
 (poll_every = steps); the per-kernel shares and the roofline come from a second pass of the
 same length with the timers on.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`,
+...); everything else the line can carry -- the per-kernel pass and roofline, the single-population
+and convergence legs, the bounded C5 leg, the other configs, the CPU baselines -- runs only with
+`--full` (where the `--no-*` switches still trim it).  `--dump-outputs DIR` writes what the timed
+path computed in its last step (rank 0) as DIR/<name>.npy, float64: every population's solution
+(`solution_x`, `solution_n_evals`, `solution_converged`) and the last generation's state
+(CMA: `xmean`, `sigma`, `fitness`; DE / APSO / CSO: `fitness`).  Inputs are fixed by the
+arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -210,10 +219,11 @@ def make_optimizer(bb, wl, P, seed, device, poll=None):
     raise ValueError(a)
 
 
-def measure(bb, wl, P, steps, warmup, seed, device, profile, barrier=None):
+def measure(bb, wl, P, steps, warmup, seed, device, profile, barrier=None, dump=None):
     """W untimed generations, then exactly `steps` timed ones (HIP-event timers off, one host
-    poll at the end); with profile=True a second pass of `steps` generations with the per-kernel
-    timers on follows and its report is returned"""
+    poll at the end); `dump(alg)` then sees the state the last timed step left; with
+    profile=True a second pass of `steps` generations with the per-kernel timers on follows and
+    its report is returned"""
     n = wl["n"]
     lo = wl["box"][0] * np.ones(n)
     up = wl["box"][1] * np.ones(n)
@@ -239,6 +249,8 @@ def measure(bb, wl, P, steps, warmup, seed, device, profile, barrier=None):
     fev = sum(alg.get_state("fev", p)[0] for p in pops) - fev0
     if count_all:
         fev /= P            # (the caller multiplies by P again)
+    if dump is not None:
+        dump(alg)
     prof = None
     if profile:
         alg.set_state("profile", [1.0])
@@ -246,6 +258,49 @@ def measure(bb, wl, P, steps, warmup, seed, device, profile, barrier=None):
         prof = alg.get_state("profile")
         alg.set_state("profile", [0.0])
     return dt, prof, fev, alg
+
+
+# --dump-outputs: at most this many bytes in all; beyond it a fixed, seeded sample of the
+# populations is written (`populations.npy` lists the ones written, always)
+DUMP_LIMIT_BYTES = 48 << 20
+# last-generation state per algorithm: get_state key -> file name
+DUMP_STATE = {"ActiveCMAES": {"xmean": "xmean", "sigma": "sigma", "fitness": "fitness"},
+              "SepCMAES": {"xmean": "xmean", "sigma": "sigma", "fitness": "fitness"},
+              "SHADE": {"f": "fitness"}, "JADE": {"f": "fitness"}, "SANSDE": {"f": "fitness"},
+              "APSO": {"f": "fitness"}, "CSO": {"f": "fitness"}}
+
+
+def _save_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def dump_outputs(alg, wl, P, outdir):
+    """what a caller of the timed path receives after its last step, population by population:
+    the solution (x*, evaluations, converged) and the last generation's state (DUMP_STATE)"""
+    state = DUMP_STATE.get(wl["algo"], {})
+
+    def row(p):
+        s = alg.solution(p)
+        r = {"solution_x": s.x, "solution_n_evals": s.n_evals,
+             "solution_converged": float(bool(s.converged))}
+        for key, name in state.items():
+            v = alg.get_state(key, p)
+            r[name] = v[0] if v.size == 1 else v
+        return r
+
+    first = row(0)
+    per_pop = sum(8 * np.size(v) for v in first.values())
+    pops = np.arange(P)
+    if P * per_pop > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // per_pop)
+        pops = np.sort(np.random.default_rng(0).choice(P, keep, replace=False))
+    rows = [first if p == 0 else row(p) for p in pops]
+    out = {name: np.stack([np.asarray(r[name], dtype=np.float64) for r in rows])
+           for name in first}
+    out["populations"] = pops
+    _save_outputs(outdir, out)
 
 
 # generations-to-tol of the reference itself (BASELINE.md section 2, measured on its C++):
@@ -538,9 +593,14 @@ def bench_bipop(args, world, rank, local_rank, use_dist, barrier):
                                max(1, args.steps) * 25000, barrier, slots=args.slots)
     if rank != 0:
         return
-    wl, prof = c5_inner_profile(bb, local_rank)
-    kernels, roofline = kernel_report(CMA_KERNELS, cma_kernel_costs(wl["n"], wl["np"], 1), prof,
-                                      "C5", 1)
+    if args.dump_outputs:
+        _save_outputs(args.dump_outputs, {"solution_x": st.xbest, "solution_n_evals": [st.fev],
+                                          "best_f": [st.fxbest]})
+    kernels = roofline = None
+    if args.full:
+        wl, prof = c5_inner_profile(bb, local_rank)
+        kernels, roofline = kernel_report(CMA_KERNELS, cma_kernel_costs(wl["n"], wl["np"], 1),
+                                          prof, "C5", 1)
     out = {
         "metric": "candidate-evals/sec", "value": st.fev / dt, "unit": "candidate-evals/s",
         "n_gpus": world, "steps": st.round, "warmup": 0,
@@ -553,7 +613,7 @@ def bench_bipop(args, world, rank, local_rank, use_dist, barrier):
                    "rounds": st.round, "large_restarts": st.largerestarts,
                    "small_restarts": st.smallrestarts, "best_f": st.fxbest},
         "roofline": roofline, "kernels": kernels,
-        "cpu_baseline": None if args.no_cpu_baseline else c5_cpu_baseline(),
+        "cpu_baseline": c5_cpu_baseline() if args.full and not args.no_cpu_baseline else None,
     }
     print(json.dumps(out))
 
@@ -688,7 +748,14 @@ def main():
     ap.add_argument("--cpu-replica", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--slots", type=int, default=1,
                     help="C5: concurrent restart populations per GPU (default 1, as configured)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel pass and roofline, single-"
+                         "population, convergence, C5 and config legs, CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_replica:
         cpu_replica_main(args.cpu_replica)
@@ -730,8 +797,12 @@ def main():
         return
     wl = WORKLOADS[args.workload]
     P = args.populations if args.populations else wl["P"]
+    dump = None
+    if args.dump_outputs and rank == 0:
+        def dump(alg):
+            dump_outputs(alg, wl, P, args.dump_outputs)
     dt, prof, fev_pop, _ = measure(bb, wl, P, args.steps, args.warmup, 1000 + rank, local_rank,
-                                   profile=(rank == 0), barrier=barrier)
+                                   profile=(rank == 0 and args.full), barrier=barrier, dump=dump)
     if use_dist:
         dt = max_over_ranks(dt)
     total_evals = world * P * fev_pop
@@ -739,7 +810,7 @@ def main():
 
     # BIPOP multi-restart scaling (north_star): a bounded C5 leg at this world size, all ranks
     bipop = None
-    if args.workload == "M" and not args.no_bipop:
+    if args.full and args.workload == "M" and not args.no_bipop:
         st, bdt, budget = bipop_leg(bb, world, rank, local_rank, use_dist, C5_LEG_BUDGET, barrier,
                                     tol=C5_LEG_TOL)
         bipop = {"workload": "BIPOP-CMA-ES (ActiveCMAES inner, tol %g) n=256 rastrigin, one "
@@ -780,7 +851,7 @@ def main():
         kernels, roofline = kernel_report(names, costs, prof, args.workload, P)
         single = None
         singles = None
-        if world == 1 and not args.no_single:
+        if args.full and world == 1 and not args.no_single:
             if P != 1:
                 # (a generation of ONE population is ~0.4 ms: 200 of them, so that the one host
                 # synchronisation at the end of the timed region is noise, not 1 % of it)
@@ -798,16 +869,16 @@ def main():
                     singles[key] = {"value": f1 / d1, "ms_per_step": 1e3 * d1 / sk, "steps": sk,
                                     "unit": "candidate-evals/s"}
         conv = ftar = None
-        if (world == 1 and wl["algo"] == "ActiveCMAES" and not args.no_convergence
+        if (args.full and world == 1 and wl["algo"] == "ActiveCMAES" and not args.no_convergence
                 and not args.no_single):
             conv = generations_to_tol(bb, wl, local_rank)
             conv["reference"] = REFERENCE_GENERATIONS_TO_TOL.get(args.workload)
             ftar = generations_to_ftarget(bb, wl, local_rank)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(wl, key=args.workload)
         configs = None
-        if world == 1 and args.workload == "M" and not args.no_configs:
+        if args.full and world == 1 and args.workload == "M" and not args.no_configs:
             configs = {key: config_leg(bb, key, local_rank, cpu=not args.no_cpu_baseline)
                        for key in CONFIG_LEGS}
         out = {

@@ -1,10 +1,10 @@
-"""GPU: INTEGRATION.md section B on a real device.  integration/_build/adapter_check is
+"""GPU: INTEGRATION.md section B on a real device.  oracle/_ref/adapter_check is
 integration/adapter_check.cpp compiled in the development container against the REFERENCE's own
-src/multivariate/multivariate.h:132-146 (`make -C integration`, also part of
+src/multivariate/multivariate.h:132-146 (`make -C oracle adapter`, also part of
 __graft_entry__.build()); it drives a HipOptimizer through a `MultivariateOptimizer*` exactly as
 the reference drives any of its optimizers: optimize() on the README example (Rosenbrock, n = 10,
-box [-10, 10]) and the stepwise init / iterate / solution.  The binary travels to the GPU box with
-the snapshot (git-ignored, like oracle/_ref); the reference itself does not and is not needed."""
+box [-10, 10]) and the stepwise init / iterate / solution.  The binary is git-ignored like the
+rest of oracle/_ref and goes with the built tree; the reference itself is not needed to run it."""
 import os
 import re
 import subprocess
@@ -14,13 +14,13 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "integration", "_build", "adapter_check")
+EXE = os.path.join(ROOT, "oracle", "_ref", "adapter_check")
 
 
 def test_adapter_optimizes_through_the_reference_interface(hip):
     if not os.path.exists(EXE):
-        pytest.skip("integration/_build/adapter_check was not built (no /root/reference where "
-                    "this snapshot was made)")
+        pytest.skip("oracle/_ref/adapter_check was not built (no reference sources where "
+                    "this tree was built)")
     run = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout + run.stderr
     out = run.stdout

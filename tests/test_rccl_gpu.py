@@ -53,11 +53,12 @@ def test_bench_runs_under_a_world_size_1_nccl_group(hip):
     port = s.getsockname()[1]
     s.close()
     env = dict(_env(), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_PORT=str(port))
-    # the DEFAULT workload (what the driver launches), small: the bounded C5 leg then runs too --
-    # ConcurrentBiPop under the nccl group, its all_gather on device tensors, max_over_ranks
+    # the DEFAULT workload (what the driver launches), small, with --full: the bounded C5 leg then
+    # runs too -- ConcurrentBiPop under the nccl group, its all_gather on device tensors,
+    # max_over_ranks
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--populations", "8",
-                          "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-single",
-                          "--no-convergence"],
+                          "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline",
+                          "--no-single", "--no-convergence"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
