@@ -8,9 +8,9 @@ of include/bbopt_hip.h.  See DESIGN.md.
 from . import objectives
 from .objectives import vectorized
 from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, CMAES,
-                           ActiveCMAES, SepCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
+                           ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
                            SANSDE, APSO, CSO, CCPSO)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "objectives",
            "vectorized"]

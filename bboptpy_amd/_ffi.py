@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
-    ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO = range(11)
+    ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES = range(12)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB = 0, 1, 2
 # bbo_cma_phase
@@ -43,6 +43,7 @@ class Params(C.Structure):
         ("crref", C.c_int), ("pupdate", C.c_int), ("crupdate", C.c_int),
         ("pcompete", C.c_int), ("ring", C.c_int), ("vmax", C.c_double),
         ("npps", C.c_int), ("pps", C.c_int * 16), ("pcauchy", C.c_double),
+        ("stol", C.c_double), ("ranked", C.c_int),
     ]
 
 

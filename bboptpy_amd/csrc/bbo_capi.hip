@@ -4,6 +4,7 @@
 #include "bbo_cma.hpp"
 #include "bbo_ccpso.hpp"
 
+#include <cstddef>
 #include <memory>
 #include <mutex>
 
@@ -64,6 +65,20 @@ bbo::ObjectiveSpec to_spec(const bbo_objective *o)
     return s;
 }
 
+// bbo_params as a caller built against an earlier header knows it ends where `stol` begins.  Such a
+// caller can only name the algorithms of its header, so the fields appended for CholeskyCMAES are
+// read and written for BBO_ALGO_CHOLESKY_CMAES alone: nothing here touches memory past the struct
+// the caller allocated.
+constexpr size_t PARAMS_BASE_BYTES = offsetof(bbo_params, stol);
+
+bbo_params own_copy(const bbo_params *params)
+{
+    bbo_params p;
+    std::memset(&p, 0, sizeof(p));
+    std::memcpy(&p, params, params->algo == BBO_ALGO_CHOLESKY_CMAES ? sizeof(p) : PARAMS_BASE_BYTES);
+    return p;
+}
+
 } // namespace
 
 #include <dlfcn.h>
@@ -93,7 +108,7 @@ extern "C" {
 void bbo_params_default(bbo_params *p, int algo)
 {
     if (!p) return;
-    std::memset(p, 0, sizeof(*p));
+    std::memset(p, 0, algo == BBO_ALGO_CHOLESKY_CMAES ? sizeof(*p) : PARAMS_BASE_BYTES);
     p->algo = algo;
     // defaults of py/multivariate_py.cpp:103-171,265-269
     p->sigma0 = 2.;
@@ -127,6 +142,10 @@ void bbo_params_default(bbo_params *p, int algo)
     p->vmax = 0.2;
     p->npps = 0;
     p->pcauchy = -1.;
+    if (algo == BBO_ALGO_CHOLESKY_CMAES) {     // (see PARAMS_BASE_BYTES)
+        p->stol = 0.;
+        p->ranked = 0;
+    }
 }
 
 int bbo_create(const bbo_params *params, bbo_handle *out)
@@ -140,10 +159,13 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
     try {
         std::unique_ptr<bbo_handle_s> h(new bbo_handle_s());
         h->algo = params->algo;
+        const bbo_params own = own_copy(params);
+        params = &own;
         switch (params->algo) {
         case BBO_ALGO_CMAES:
         case BBO_ALGO_ACTIVE_CMAES:
         case BBO_ALGO_SEP_CMAES:
+        case BBO_ALGO_CHOLESKY_CMAES:
             h->opt.reset(new bbo::CmaEngine(*params));
             break;
         case BBO_ALGO_SHADE:
@@ -187,11 +209,12 @@ int bbo_create_restart(const bbo_params *params, bbo_handle base, bbo_handle *ou
         if (params->algo != BBO_ALGO_IPOP_CMAES && params->algo != BBO_ALGO_BIPOP_CMAES)
             throw bbo::Error(BBO_ERR_ARG, "bbo_create_restart: algo must be IPOP or BIPOP");
         if (base->algo != BBO_ALGO_CMAES && base->algo != BBO_ALGO_ACTIVE_CMAES
-                && base->algo != BBO_ALGO_SEP_CMAES)
+                && base->algo != BBO_ALGO_SEP_CMAES && base->algo != BBO_ALGO_CHOLESKY_CMAES)
             throw bbo::Error(BBO_ERR_ARG, "bbo_create_restart: base must be a CMA-ES handle");
         std::unique_ptr<bbo_handle_s> h(new bbo_handle_s());
         h->algo = params->algo;
-        h->opt.reset(bbo::make_restart_driver(*params, base->opt.get()));
+        const bbo_params own = own_copy(params);
+        h->opt.reset(bbo::make_restart_driver(own, base->opt.get()));
         *out = h.release();
         return BBO_OK;
     } catch (const bbo::Error &e) {

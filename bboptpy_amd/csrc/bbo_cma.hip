@@ -3,9 +3,11 @@
 //
 // Reference behaviour restated on the host: BaseCmaes::init (base_cmaes.cpp:54-134),
 // Cmaes::init (cmaes.cpp:44-63), ActiveCmaes::init (active_cmaes.cpp:42-69),
+// CholeskyCmaes::init (cholesky_cmaes.cpp:40-52),
 // BaseCmaes::setParams (:136-148), optimize (:162-174), solution (:158-160).
 #include "bbo_cma_kernels.hpp"
 #include "bbo_sep_kernels.hpp"
+#include "bbo_chol_kernels.hpp"
 #include "bbo_eig_mw.hpp"
 
 #include <algorithm>
@@ -51,7 +53,8 @@ CmaEngine::CmaEngine(const bbo_params &p) :
         params_(p)
 {
     BBO_REQUIRE(p.algo == BBO_ALGO_CMAES || p.algo == BBO_ALGO_ACTIVE_CMAES
-            || p.algo == BBO_ALGO_SEP_CMAES, "CmaEngine: algo must be CMAES, ACTIVE_CMAES or SEP_CMAES");
+            || p.algo == BBO_ALGO_SEP_CMAES || p.algo == BBO_ALGO_CHOLESKY_CMAES,
+            "CmaEngine: algo must be CMAES, ACTIVE_CMAES, SEP_CMAES or CHOLESKY_CMAES");
     BBO_REQUIRE(p.np >= 4, "CMA-ES needs np >= 4 (mu >= 2, best/worst pairs)");
     BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
     int ndev = 0;
@@ -175,7 +178,11 @@ void CmaEngine::set_params(int np, double sigma, int mfev)
 void CmaEngine::init(int n, const double *lower, const double *upper, const double *guess,
         const ObjectiveSpec &obj)
 {
+    const bool chol = params_.algo == BBO_ALGO_CHOLESKY_CMAES;
     const bool sep = params_.algo == BBO_ALGO_SEP_CMAES;
+    // dense: the variants with the eigen-state B, C, D, C^-1/2 (the Cholesky variant keeps its
+    // factor A and the scratch image of C' instead, the separable one a diagonal)
+    const bool dense = !sep && !chol;
     if (sep)
         BBO_REQUIRE(n >= 1 && n <= 4096, "SepCMAES: dimension must be in [1, 4096]");
     else
@@ -192,11 +199,13 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     c.lambda_pad = round_up(lambda, 16);
     c.mu = lambda / 2;
     c.mu_pad = round_up(c.mu, 16);
-    c.variant = sep ? 2 : params_.algo == BBO_ALGO_ACTIVE_CMAES ? 1 : 0;
+    c.variant = chol ? 3 : sep ? 2 : params_.algo == BBO_ALGO_ACTIVE_CMAES ? 1 : 0;
+    c.stol = params_.stol;
+    c.ranked = params_.ranked ? 1 : 0;
     c.bound = params_.bound ? 1 : 0;
     // (16 < ld <= 128: the samplers there always hand down ||z||^2, so without a box nothing in
     // a generation reads C^-1/2 but cma_paths, which can work from B and D)
-    c.lazy_isc = (!sep && !c.bound && c.ld > 16 && c.ld <= 256) ? 1 : 0;
+    c.lazy_isc = (dense && !c.bound && c.ld > 16 && c.ld <= 256) ? 1 : 0;
     c.obj = obj.on_device() ? obj.builtin : OBJ_HOST;
     c.mfev = params_.mfev;
     c.mit = params_.mfev / lambda;
@@ -274,12 +283,13 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
         c.rps = ((c.lambda_pad + want - 1) / want + G128_CH - 1) / G128_CH * G128_CH;
     }
     c.splits = (c.lambda_pad + c.rps - 1) / c.rps;
-    if (sep)   // slabs of the mu selected ranks: enough workgroups to stream at HBM rate
+    if (chol) c.splits = 1;      // (chol_cprime sums its rows inside one workgroup per tile)
+    else if (sep)   // slabs of the mu selected ranks: enough workgroups to stream at HBM rate
         c.splits = std::max(1, std::min(c.mu / 16, (1024 + P - 1) / P));
 
     // ---- HBM state ------------------------------------------------------------
     const size_t ld = c.ld, ld2 = ld * ld;
-    const bool same_shape = !sep && keep_bc_ && last_n_ == n && C_.count == P * ld2;
+    const bool same_shape = dense && keep_bc_ && last_n_ == n && C_.count == P * ld2;
     X_.alloc((size_t) P * c.lambda_pad * ld);
     f_.alloc((size_t) P * c.lambda_pad);
     zn2_.alloc((size_t) P * c.lambda_pad);
@@ -291,13 +301,32 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     ps_.alloc(P * ld);
     D_.alloc(P * ld);
     csep_.alloc(P * ld);
-    if (!sep) {
+    if (dense) {
         isc_.alloc(P * ld2);
         BDp_.alloc(P * ld2);
         ISp_.alloc(P * ld2);
     }
+    if (chol) {
+        // A = I (cholesky_cmaes.cpp:45-51: cleared at every init, nothing survives a re-init)
+        A_.alloc(P * ld2);
+        C_.alloc(P * ld2);
+        BDp_.alloc(P * ld2);
+        std::vector<double> eyeA(P * ld2, 0.), eyeP(P * ld2, 0.);
+        const size_t KS = ld >> 2;
+        for (int p = 0; p < P; p++)
+            for (size_t i = 0; i < (size_t) n; i++) {
+                eyeA[p * ld2 + i * ld + i] = 1.;
+                eyeP[p * ld2 + ((i >> 4) * KS + (i >> 2)) * 64 + ((i & 3) << 4) + (i & 15)] = 1.;
+            }
+        A_.upload(eyeA.data(), P * ld2);
+        allow_lds((const void*) chol_factor, 136 * 1024);      // (ld <= 128: the matrix in LDS)
+        std::vector<int> zero(P, 0);
+        chol_repairs_.alloc(P);
+        chol_repairs_.upload(zero.data(), P);
+        BDp_.upload(eyeP.data(), P * ld2);
+    }
     S_.alloc((size_t) P * c.mu_pad);
-    gram_part_.alloc((size_t) P * c.splits * (sep ? ld : ld2));   // sep: second moments, [ld]
+    gram_part_.alloc((size_t) P * c.splits * (dense ? ld2 : ld));   // sep: second moments, [ld]; Cholesky: unused
     mean_part_.alloc((size_t) P * c.splits * ld);
     hist_best_.alloc((size_t) P * c.hlen);
     hist_kth_.alloc((size_t) P * c.hlen);
@@ -323,9 +352,9 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     // B = C = C^-1/2 = I, D = 1.  The reference resize()s _b/_c, so on a re-init of the
     // SAME object with the same n the old off-diagonals survive and only the diagonals are
     // reset (cmaes.cpp:53-59); restart drivers depend on that, so it is kept.
-    std::vector<double> eye(sep ? 0 : P * ld2, 0.), ones(P * ld, 1.);
+    std::vector<double> eye(dense ? P * ld2 : 0, 0.), ones(P * ld, 1.);
     csep_.upload(ones.data(), P * ld);
-    if (!sep) {
+    if (dense) {
     for (int p = 0; p < P; p++)
         for (int i = 0; i < n; i++) eye[p * ld2 + (size_t) i * ld + i] = 1.;
     if (same_shape) {
@@ -346,9 +375,9 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
         C_.upload(eye.data(), P * ld2);
     }
     isc_.upload(eye.data(), P * ld2);
-    }   // !sep
+    }   // dense
     D_.upload(ones.data(), P * ld);
-    keep_bc_ = !sep;
+    keep_bc_ = dense;
     last_n_ = n;
 
     std::vector<double> xm(P * ld, 0.);
@@ -373,13 +402,15 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     // the eigensolver keeps its matrix in LDS when it fits
     // global scratch of the eigensolver: the work matrix when it does not fit LDS, or
     // (divide and conquer) the Householder matrix and the merge factor
-    if (!sep) eig_work_.alloc((size_t) P * 4 * eig_slab((int) ld));
+    if (dense) eig_work_.alloc((size_t) P * 4 * eig_slab((int) ld));
 
     CmaDev &d = d_;
     d = CmaDev {};
     d.X = X_.p; d.f = f_.p; d.rank = rank_.p; d.order = order_.p;
     d.xmean = xmean_.p; d.xold = xold_.p; d.pc = pc_.p; d.ps = ps_.p;
     d.C = C_.p; d.B = B_.p; d.D = D_.p; d.isc = isc_.p; d.BDp = BDp_.p; d.ISp = ISp_.p;
+    d.A = chol ? A_.p : nullptr;
+    d.chol_repairs = chol ? chol_repairs_.p : nullptr;
     d.S = S_.p; d.zn2 = zn2_.p; d.csep = csep_.p; d.gram_part = gram_part_.p; d.mean_part = mean_part_.p;
     d.hist_best = hist_best_.p; d.hist_kth = hist_kth_.p; d.eig_work = eig_work_.p;
     d.weights = weights_.p; d.lower = lower_.p; d.upper = upper_.p; d.aux = aux_.p;
@@ -392,7 +423,7 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     // packed operands of the initial B, D, C^-1/2
     c.honor_stop = 0;
     inited_ = true;
-    if (!sep) {
+    if (dense) {
         launch_post(2);
         BBO_HIP(hipGetLastError());
         BBO_HIP(hipStreamSynchronize(stream_));
@@ -497,6 +528,11 @@ void CmaEngine::launch_sample_eval()
         // the lean build of the tile loop where nothing needs guarding (M, C3)
         const int full = (c.n == 128 && !c.bound && c.lambda == c.lambda_pad && !d_.zinject
                 && !d_.zrecord && !(d_.dbg & 256)) ? 1 : 0;
+        if (c.variant == 3 && chol_tri_) {      // (lower-triangular operand: 36 of 64 block pairs)
+            allow_lds((const void*) cma_sample_eval128_tri, 128 * 1024);
+            hipLaunchKernelGGL(cma_sample_eval128_tri, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
+                    full);
+        } else
         hipLaunchKernelGGL(cma_sample_eval128, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
                 full);
         zn_valid = true;
@@ -505,6 +541,10 @@ void CmaEngine::launch_sample_eval()
         // form C5's handful of candidates takes at n = 256) -- a wavefront's chain is 32 MFMAs and
         // one Philox call instead of 256 and eight
         const size_t lds = (size_t) 16 * (c.ld + 2) * sizeof(double);
+        if (c.variant == 3 && chol_tri_)
+            hipLaunchKernelGGL((cma_sample_eval<1, 8, true>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds,
+                    stream_, d_, c_);
+        else
         hipLaunchKernelGGL((cma_sample_eval<1, 8>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds, stream_,
                 d_, c_);
         zn_valid = true;
@@ -582,6 +622,24 @@ void CmaEngine::launch_rank()
 void CmaEngine::launch_update()
 {
     const CmaConst &c = c_;
+    if (c.variant == 3) {
+        // paths and C' read the old factor; chol_factor (launch_eigen's slot in the order of a
+        // generation, but part of this phase: BBO_PHASE_EIGEN does nothing here) writes the new one
+        timer_.begin(stream_, K_PATHS);
+        hipLaunchKernelGGL(chol_paths, dim3(c.npop), dim3(256), 0, stream_, d_, c_);
+        timer_.end(stream_);
+        const int NT = c.ld / 16;
+        timer_.begin(stream_, K_GRAM);
+        hipLaunchKernelGGL(chol_cprime, dim3(NT * (NT + 1) / 2, c.npop), dim3(256), 0, stream_, d_, c_);
+        timer_.end(stream_);
+        const int in_lds = c.ld <= 128 ? 1 : 0;
+        const size_t lds = in_lds ? (size_t) c.ld * (c.ld + 1) * sizeof(double) : 0;
+        timer_.begin(stream_, K_COV);
+        hipLaunchKernelGGL(chol_factor, dim3(c.npop), dim3(256), lds, stream_, d_, c_, in_lds);
+        timer_.end(stream_);
+        BBO_HIP(hipGetLastError());
+        return;
+    }
     if (c.variant == 2) {
         timer_.begin(stream_, K_GRAM);
         hipLaunchKernelGGL(sep_moments, dim3(c.splits, (c.ld + 511) / 512, c.npop), dim3(256), 0,
@@ -668,7 +726,7 @@ int CmaEngine::next_mw_xcd()
 void CmaEngine::launch_eigen()
 {
     const CmaConst &c = c_;
-    if (c.variant == 2) return;        // diagonal covariance: d = sqrt(c) is part of sep_paths
+    if (c.variant >= 2) return;        // diagonal covariance: d = sqrt(c) is part of sep_paths; Cholesky: no decomposition
     // 64 < n <= 128 with few matrices in flight (one optimisation run at a time): the reduction on
     // one workgroup, the divide and conquer and the reflectors over many -- the structure of
     // 128 < n <= 256 (diagnostic bit 4194304: everything on the reducing workgroup, as for a batch)
@@ -826,6 +884,9 @@ void CmaEngine::launch_eigen()
 void CmaEngine::launch_history_stop()
 {
     timer_.begin(stream_, K_STOP);
+    if (c_.variant == 3)
+        hipLaunchKernelGGL(chol_history_stop, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
+    else
     hipLaunchKernelGGL(cma_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
@@ -857,7 +918,7 @@ void CmaEngine::host_evaluate()
 bool CmaEngine::small_fused_ok() const
 {
     const CmaConst &c = c_;
-    return c.variant != 2 && c.ld == 16 && c.n >= 2 && c.lambda_pad <= 64 && obj_.on_device()
+    return c.variant < 2 && c.ld == 16 && c.n >= 2 && c.lambda_pad <= 64 && obj_.on_device()
             && c.npop <= SMALL_FUSED_MAXP && !timer_.on() && !(d_.dbg & (16 | 64));
 }
 
@@ -1029,7 +1090,8 @@ void CmaEngine::solution(int population, double *x_out, int *n_evals, int *conve
     // solution() re-runs converged() (base_cmaes.cpp:158-160); before any generation the
     // tests see it = 0 and the initial state
     if (s.it <= 0) {
-        *converged = (0 >= c_.mit) ? 1 : 0;
+        // (CholeskyCmaes::converged on the initial state: all f and all radii are 0, both parts hold)
+        *converged = c_.variant == 3 ? (c_.tol >= 0. ? 1 : 0) : (0 >= c_.mit) ? 1 : 0;
     } else {
         *converged = s.flag != 0 ? 1 : 0;
     }
@@ -1094,6 +1156,12 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     };
     if (c.variant == 2 && (k == "B" || k == "C" || k == "invsqrtC" || k == "ycoeff"))
         throw Error(BBO_ERR_KEY, "SepCMAES keeps a diagonal covariance: read 'csep' and 'D'");
+    if (c.variant == 3 && (k == "B" || k == "C" || k == "D" || k == "invsqrtC" || k == "ycoeff" || k == "csep"))
+        throw Error(BBO_ERR_KEY, "CholeskyCMAES keeps the factor: read 'A'");
+    if (k == "A") {
+        if (c.variant != 3) throw Error(BBO_ERR_KEY, "'A' belongs to CholeskyCMAES");
+        return mat(A_, n, ld, n, p * ld * ld);
+    }
     if (k == "xmean") return vec(xmean_);
     if (k == "xold") return vec(xold_);
     if (k == "pc") return vec(pc_);
@@ -1200,6 +1268,15 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "basis_ok") return one(s.basis_ok);
     if (k == "eig_stage") return one(s.eig_stage);
     if (k == "eig_mw_fail") return one(s.eig_mw_fail);     // (bbo_eig_mw.hpp: sticky)
+    if (k == "chol_repairs") {                             // (chol_factor: sticky)
+        if (c.variant != 3) throw Error(BBO_ERR_KEY, "'chol_repairs' belongs to CholeskyCMAES");
+        int r = 0;
+        chol_repairs_.download(&r, 1, p);
+        return one(r);
+    }
+    if (c.variant == 3 && k == "chol_tri") return one(chol_tri_ ? 1 : 0);
+    if (c.variant == 3 && k == "stol") return one(c.stol);
+    if (c.variant == 3 && k == "ranked") return one(c.ranked);
     if (k == "eig_mw_off") return one(mw_disabled_ ? 1 : 0);
     if (k == "eig_split_maxp") return one(split_maxp_);
     if (k == "eig_mw_reserved") return one((double) mw_reserved_);       // this engine's share of the device's ...
@@ -1259,6 +1336,35 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
     };
     if (c.variant == 2 && (k == "B" || k == "C" || k == "D"))
         throw Error(BBO_ERR_KEY, "SepCMAES: set 'csep' (D is its square root)");
+    if (c.variant == 3 && (k == "B" || k == "C" || k == "D" || k == "csep"))
+        throw Error(BBO_ERR_KEY, "CholeskyCMAES keeps the factor: set 'A'");
+    if (k == "A") {
+        // the factor and its packed form for the sampler (upper triangle dropped)
+        if (c.variant != 3) throw Error(BBO_ERR_KEY, "'A' belongs to CholeskyCMAES");
+        BBO_REQUIRE(count == (int) (n * n), "set: wrong element count");
+        std::vector<double> a(ld * ld, 0.), pk(ld * ld, 0.);
+        const size_t KS = ld >> 2;
+        for (size_t i = 0; i < n; i++)
+            for (size_t j = 0; j <= i; j++) {
+                a[i * ld + j] = in[i * n + j];
+                pk[((i >> 4) * KS + (j >> 2)) * 64 + ((j & 3) << 4) + (i & 15)] = in[i * n + j];
+            }
+        A_.upload(a.data(), ld * ld, p * ld * ld);
+        BDp_.upload(pk.data(), ld * ld, p * ld * ld);
+        return count;
+    }
+    if (c.variant == 3 && k == "arx") {          // (crafted stop states of the Cholesky variant's rule)
+        BBO_REQUIRE(count == (int) (c.lambda * n), "set: wrong element count");
+        std::vector<double> tmp((size_t) c.lambda * ld, 0.);
+        for (size_t i = 0; i < (size_t) c.lambda; i++) std::copy(in + i * n, in + (i + 1) * n, tmp.begin() + i * ld);
+        X_.upload(tmp.data(), tmp.size(), (size_t) p * c.lambda_pad * ld);
+        return count;
+    }
+    if (c.variant == 3 && k == "fitness") {      // (the same; the ranking is NOT redone: fit_idx keeps its order)
+        BBO_REQUIRE(count == c.lambda, "set: wrong element count");
+        f_.upload(in, c.lambda, (size_t) p * c.lambda_pad);
+        return count;
+    }
     if (k == "xmean") return vec(xmean_);
     if (k == "xold") return vec(xold_);
     if (k == "pc") return vec(pc_);
@@ -1302,6 +1408,10 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
     }
     if (k == "dbg") {
         d_.dbg = (int) in[0];
+        return 1;
+    }
+    if (c.variant == 3 && k == "chol_tri") {   // n = 128: 1 = the triangular samplers, 0 = the full-operand ones (same bits)
+        chol_tri_ = in[0] != 0.;
         return 1;
     }
     if (k == "sample_wide_max") {  // (tuning: at most this many 16-row tiles take the tile-per-workgroup sampler)

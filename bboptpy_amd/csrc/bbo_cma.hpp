@@ -1,4 +1,4 @@
-// bbo_cma.hpp -- device-resident CMA-ES / active CMA-ES engine (declarations).
+// bbo_cma.hpp -- device-resident CMA-ES engine: plain, active, separable, Cholesky (declarations).
 //
 // One generation of the reference (BaseCmaes::iterate, base_cmaes.cpp:150-156:
 // samplePopulation -> evaluateAndSortPopulation -> updateDistribution ->
@@ -33,7 +33,8 @@ struct CmaConst {
     int n, ld;                // dimension, padded leading dimension (multiple of 16)
     int lambda, lambda_pad;   // population size, padded to a multiple of 16
     int mu, mu_pad;
-    int variant;              // 0 plain (cmaes.cpp), 1 active (active_cmaes.cpp), 2 separable (sep_cmaes.cpp)
+    int variant;              // 0 plain (cmaes.cpp), 1 active (active_cmaes.cpp), 2 separable (sep_cmaes.cpp),
+                              // 3 Cholesky (cholesky_cmaes.cpp)
     int bound, obj;
     int use_zn;               // this generation's zn2 is valid and x was not clamped
     int lazy_isc;             // C^-1/2 is not formed after a decomposition (16 < ld <= 256, no box): cma_paths
@@ -49,6 +50,10 @@ struct CmaConst {
     // reference's stop test with flag k; f_best <= ftarget raises the non-reference flag 10
     int stop_off;
     double ftarget;
+    // CholeskyCMAES: the radius-spread tolerance of its stop rule; ranked != 0 (extension): the
+    // rank-mu term takes the mu best about the old mean instead of the first mu about the new one
+    double stol;
+    int ranked;
 };
 
 struct CmaDev {
@@ -61,7 +66,9 @@ struct CmaDev {
     double *B;          // [P][ld][ld]  eigenvectors in columns
     double *D;          // [P][ld]      sqrt(eigenvalues), ascending
     double *isc;        // [P][ld][ld]  C^-1/2
-    double *BDp;        // [P][ld*ld]   (B diag D) in MFMA B-fragment order
+    double *A;          // [P][ld][ld]  CholeskyCMAES: the lower factor, row-major (upper triangle 0)
+    int *chol_repairs;  // [P]          CholeskyCMAES, sticky: pivots chol_factor had to lift to a positive value
+    double *BDp;        // [P][ld*ld]   (B diag D) in MFMA B-fragment order (CholeskyCMAES: A)
     double *ISp;        // [P][ld*ld]   C^-1/2   in MFMA B-fragment order
     double *S;          // [P][mu_pad]  whitened squared norms of the worst mu
     double *csep;       // [P][ld] diagonal covariance of the separable variant (D = its sqrt)
@@ -145,16 +152,17 @@ private:
     static int next_mw_xcd();
     long sample_wide_max_tiles_ = 512;       // n = 128: at most this many 16-row tiles take cma_sample_eval<1, 8>
     long sample128_min_rows_ = 256 * 128;   // candidates in flight from which cma_sample_eval128 is used
+    bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;
     std::vector<double> lower_h_, upper_h_, aux_h_;
 
-    DevBuf<double> zn2_, csep_;
+    DevBuf<double> zn2_, csep_, A_;
     DevBuf<double> X_, f_, xmean_, xold_, pc_, ps_, C_, B_, D_, isc_, BDp_, ISp_, S_,
             gram_part_, mean_part_, hist_best_, hist_kth_, eig_work_, weights_, lower_,
             upper_, aux_, zinject_, zrecord_;
-    DevBuf<int> rank_, order_;
+    DevBuf<int> rank_, order_, chol_repairs_;
     DevBuf<long long> stamps_;
     DevBuf<CmaScal> scal_;
     int *mw_fail_host_ = nullptr;   // pinned, device-visible: raised by a spread reduction that timed out

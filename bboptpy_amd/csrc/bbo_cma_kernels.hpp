@@ -134,7 +134,10 @@ __device__ inline double cma_settle_draw(const CmaDev &d, const CmaConst &c, int
 // wavefront, and NW = ld / 16 wavefronts of ONE column tile each put four times the requests in
 // flight (round 4: 60 -> 3x us).  Same products in the same order for every NW.
 // ---------------------------------------------------------------------------
-template<int MAXT, int NW = 4>
+// TRI (CholeskyCMAES: the operand is lower triangular): only the k-steps up to the column
+// tile's own block are fetched and issued -- the others multiply by exact zeros, so the sums are
+// the same bits.
+template<int MAXT, int NW = 4, bool TRI = false>
 __global__ __launch_bounds__(64 * NW) void cma_sample_eval(CmaDev d, CmaConst c)
 {
     const int p = blockIdx.y, mt = blockIdx.x;
@@ -189,7 +192,8 @@ __global__ __launch_bounds__(64 * NW) void cma_sample_eval(CmaDev d, CmaConst c)
 #pragma unroll
             for (int t = 0; t < MAXT; t++) {
                 const int nt = wave + NW * t;
-                b[u][t] = nt < NT ? bdp[((size_t) nt * KS + ks0 + u) * 64 + lane] : 0.;
+                b[u][t] = (nt < NT && (!TRI || ks0 + u < 4 * (nt + 1)))
+                        ? bdp[((size_t) nt * KS + ks0 + u) * 64 + lane] : 0.;
             }
         }
 #pragma unroll
@@ -198,7 +202,7 @@ __global__ __launch_bounds__(64 * NW) void cma_sample_eval(CmaDev d, CmaConst c)
 #pragma unroll
             for (int t = 0; t < MAXT; t++) {
                 const int nt = wave + NW * t;
-                if (nt < NT)
+                if (nt < NT && (!TRI || ks0 + u < 4 * (nt + 1)))
                     acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u][t], acc[t], 0, 0, 0);
             }
         }
@@ -452,7 +456,9 @@ __device__ inline void sample128_epilogue(const CmaDev &d, const CmaConst &c, in
     }
 }
 
-template<bool FULL>
+// TRI: as in cma_sample_eval -- k-step i meets column tile t only while its block i >> 2 <= t
+// (36 of the 64 block pairs)
+template<bool FULL, bool TRI = false>
 __device__ __forceinline__ void sample_eval128_body(const CmaDev &d, const CmaConst &c,
         int rows_per_wg, double *bd, const double2 *ntab, const double *ftab, const double *xms)
 {
@@ -511,13 +517,15 @@ __device__ __forceinline__ void sample_eval128_body(const CmaDev &d, const CmaCo
             for (int i = 0; i < 32; i++) {
 #pragma unroll
                 for (int t = 0; t < 8; t++) {
+                    if (TRI && (i >> 2) > t) continue;
                     const double bv = (i & 3) == 0 ? pre[t] : frag(i, t);
                     acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[i], bv, acc[t], 0, 0, 0);
                 }
                 if ((i & 3) == 3) {
                     if (i + 1 < 32) {
 #pragma unroll
-                        for (int t = 0; t < 8; t++) pre[t] = frag(i + 1, t);
+                        for (int t = 0; t < 8; t++)
+                            if (!TRI || ((i + 1) >> 2) <= t) pre[t] = frag(i + 1, t);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -542,9 +550,11 @@ __device__ __forceinline__ void sample_eval128_body(const CmaDev &d, const CmaCo
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
 #pragma unroll
-                    for (int t = 0; t < 8; t++)
+                    for (int t = 0; t < 8; t++) {
+                        if (TRI && 2 * kc + (i >> 2) > t) continue;
                         acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bk[(t * 32 + i) * 64],
                                 acc[t], 0, 0, 0);
+                    }
                 }
             }
         }
@@ -579,6 +589,32 @@ __global__ __launch_bounds__(512, 1) void cma_sample_eval128(CmaDev d, CmaConst 
     __syncthreads();
     if (full) sample_eval128_body<true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
     else sample_eval128_body<false>(d, c, rows_per_wg, bd, ntab, ftab, xms);
+}
+
+// the same kernel over a lower-triangular operand (CholeskyCMAES' factor)
+__global__ __launch_bounds__(512, 1) void cma_sample_eval128_tri(CmaDev d, CmaConst c, int rows_per_wg,
+        int full)
+{
+    const int p = blockIdx.y;
+    const CmaScal *sc = d.scal + p;
+    if (pop_frozen(c, sc)) return;
+    extern __shared__ __attribute__((aligned(16))) double bd[];
+    const int tid = threadIdx.x;
+    {
+        const double2 *src = reinterpret_cast<const double2*>(d.BDp + (size_t) p * 128 * 128);
+        double2 *dst = reinterpret_cast<double2*>(bd);
+#pragma unroll
+        for (int i = 0; i < 16; i++) dst[tid + 512 * i] = src[tid + 512 * i];
+    }
+    __shared__ double2 ntab[NORMAL_TABLE_N];
+    __shared__ double ftab[NORMAL_FTABLE_N];
+    __shared__ double xms[128];
+    normal_table_fill(ntab, tid, 512);
+    normal_ftable_fill(ftab, tid, 512);
+    if (tid < 128) xms[tid] = d.xmean[(size_t) p * 128 + tid];
+    __syncthreads();
+    if (full) sample_eval128_body<true, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
+    else sample_eval128_body<false, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
 }
 
 // ---------------------------------------------------------------------------

@@ -7,7 +7,8 @@ order, keyword names and defaults of every constructor (:103-171, :265-269), the
 methods optimize / initialize / iterate / solution (:376-420) and the MultivariateSolution
 result object (:360-371).  Every constructor additionally accepts keyword-only extensions
 that have no reference counterpart: `seed` (Philox key; default = fresh entropy, like the
-reference's random_device seeding), `device`, `populations`, and `poll_every`.
+reference's random_device seeding), `device`, `populations`, and `poll_every`
+(CholeskyCMAES also `ranked`).
 
 All computation happens in libbbopt_hip.so on the GPU.  A Python callable objective is
 supported through the host-callback path (X leaves HBM once per generation); the objects in
@@ -318,10 +319,27 @@ class SepCMAES(BaseCMAES):
         p.sigma0, p.bound, p.adjustlr = float(sigma0), int(bool(bound)), int(bool(adjustlr))
 
 
+class CholeskyCMAES(BaseCMAES):
+    """CholeskyCMAES(mfev, tol, stol, np, sigma0=2., bound=False) -- :118-120
+    (Cholesky-factor CMA-ES without eigendecomposition, Krause, Arbones, Igel 2016;
+    cholesky_cmaes.cpp).  Keyword-only extension `ranked` (default False = the reference): the
+    rank-mu term of the factor update takes the mu best candidates about the old mean instead of
+    the reference's first mu in sampling order about the new mean."""
+    _algo = _ffi.ALGO_CHOLESKY_CMAES
+
+    def __init__(self, mfev, tol, stol, np, sigma0=2., bound=False, **ext):
+        ranked = ext.pop("ranked", False)
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.stol, p.np = int(mfev), float(tol), float(stol), int(np)
+        p.sigma0, p.bound, p.ranked = float(sigma0), int(bool(bound)), int(bool(ranked))
+
+
 class _RestartDriver(MultivariateSearch):
     def __init__(self, base, **ext):
         if not isinstance(base, BaseCMAES):
-            raise TypeError("base must be a CMA-ES optimizer (CMAES / ActiveCMAES / SepCMAES)")
+            raise TypeError("base must be a CMA-ES optimizer (CMAES / ActiveCMAES / SepCMAES / "
+                            "CholeskyCMAES)")
         if base._params.populations != 1:
             raise ValueError("restart drivers need a base optimizer with populations=1")
         super().__init__(**ext)

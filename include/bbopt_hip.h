@@ -52,7 +52,8 @@ typedef enum {
     BBO_ALGO_SEP_CMAES = 7,    /* SepCmaes     src/multivariate/cma/sep_cmaes.h:36    */
     BBO_ALGO_SANSDE = 8,       /* SaNSDESearch src/multivariate/de/sansde.h:40        */
     BBO_ALGO_CSO = 9,          /* CSOSearch    src/multivariate/pso/cso.h:44          */
-    BBO_ALGO_CCPSO = 10        /* CCPSOSearch  src/multivariate/pso/ccpso.h:46        */
+    BBO_ALGO_CCPSO = 10,       /* CCPSOSearch  src/multivariate/pso/ccpso.h:46        */
+    BBO_ALGO_CHOLESKY_CMAES = 11 /* CholeskyCmaes src/multivariate/cma/cholesky_cmaes.h:37 */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -155,6 +156,16 @@ typedef struct {
     int npps;              /* number of candidate swarm sizes                      */
     int pps[16];           /* the candidate swarm sizes (each must divide n)       */
     double pcauchy;        /* fixed Cauchy rate in (0,1), else adaptive            */
+    /* ---- appended for CholeskyCMAES: keeps the layout of everything above.  The library reads
+     * and writes these two fields only when algo == BBO_ALGO_CHOLESKY_CMAES, so a caller compiled
+     * against an earlier header (a shorter struct, none of whose algorithms is this one) stays
+     * binary compatible: bbo_params_default and bbo_create* never touch memory past its struct.
+     * CholeskyCMAES(mfev,tol,stol,np,sigma0=2,bound=False)              :118-120 */
+    double stol;           /* tolerance on the spread of the candidates' radii (its stop rule) */
+    int ranked;            /* (extension, default 0) rank-mu term of the factor update:
+                              0 = the reference's (cholesky_cmaes.cpp:91-94): the FIRST mu
+                                  candidates in sampling order, centred on the NEW mean;
+                              1 = the textbook form: the mu best, centred on the old mean */
 } bbo_params;
 
 void bbo_params_default(bbo_params *p, int algo);
@@ -162,7 +173,8 @@ void bbo_params_default(bbo_params *p, int algo);
 /* ---- life cycle ----------------------------------------------------------------
  * bbo_create            <- the Python constructors (py/multivariate_py.cpp:103-171,265-269)
  * bbo_create_restart    <- IPopCmaes / BiPopCmaes constructors taking `BaseCmaes *base`
- *                          (ipop_cmaes.cpp:56, bipop_cmaes.cpp:54).  `base` stays owned
+ *                          (ipop_cmaes.cpp:56, bipop_cmaes.cpp:54): a CMAES, ActiveCMAES,
+ *                          SepCMAES or CholeskyCMAES handle.  `base` stays owned
  *                          by the caller and must outlive the driver, as in the reference.
  * bbo_destroy           <- destructor                                                  */
 int bbo_create(const bbo_params *params, bbo_handle *out);
@@ -206,6 +218,17 @@ int bbo_run(bbo_handle h, int max_generations, int *generations_done);
  * that move between two refreshes of the swarm's best inside a generation (the reference refreshes
  * after every particle, apso.cpp:194-197; the default here is np / 16 in whole workgroups, at least
  * 64; 0 = the whole swarm sees the best of the generation start). */
+/* CholeskyCMAES (BBO_ALGO_CHOLESKY_CMAES): the keys the dense variants share (arx, xmean, xold,
+ * sigma, pc, ps, fit_val, fit_idx, it, fev, flag, zlast, record_normals, ...) plus "A" (the lower
+ * Cholesky factor of the covariance, n x n row-major, upper triangle exactly 0; readable and
+ * writable) and "chol_repairs" (sticky count of pivots the factor update had to lift to a positive
+ * value: 0 unless rounding broke a factorisation); B, C, D, invsqrtC return BBO_ERR_KEY.  Its stop
+ * rule (cholesky_cmaes.cpp:137-161: |f_best - f_worst| <= tol and the squared deviations of the
+ * candidates' radii sum to <= (lambda - 1) stol^2) reports "flag" 11; flags 1-10 belong to the
+ * other variants.  "chol_tri" (default 1): at n = 128 the samplers issue only the products of
+ * the factor's lower block triangle; 0 selects the full-operand samplers (the same bits).
+ * Writable on this variant only, for crafting states of its stop rule: "arx" and "fitness"
+ * (lambda values in sampling order; the ranking "fit_idx" is NOT redone). */
 int bbo_get(bbo_handle h, const char *key, int population, double *out, int cap);
 int bbo_set(bbo_handle h, const char *key, int population, const double *in, int count);
 
@@ -215,7 +238,8 @@ typedef enum {
     BBO_PHASE_SAMPLE_EVALUATE = 0, /* samplePopulation + objective       cmaes.cpp:65-80       */
     BBO_PHASE_RANK = 1,            /* sort part of evaluateAndSortPopulation base_cmaes.cpp:221 */
     BBO_PHASE_UPDATE = 2,          /* updateDistribution without eigen   active_cmaes.cpp:71-164 */
-    BBO_PHASE_EIGEN = 3,           /* eigenDecomposition                 cmaes.cpp:229-283     */
+    BBO_PHASE_EIGEN = 3,           /* eigenDecomposition                 cmaes.cpp:229-283
+                                      (SepCMAES, CholeskyCMAES: nothing to do, BBO_OK)          */
     BBO_PHASE_HISTORY_STOP = 4     /* updateHistory, it++, converged()   base_cmaes.cpp:191-209, cmaes.cpp:151-227 */
 } bbo_cma_phase;
 int bbo_cma_phase_run(bbo_handle h, int phase);
