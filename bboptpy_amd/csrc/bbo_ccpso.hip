@@ -14,23 +14,17 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:ccp_regroup", "bbo:ccp_eval",
 }
 
 CcpsoEngine::CcpsoEngine(const bbo_params &p) :
-        params_(p)
+        Engine(checked(p))
+{
+}
+
+// the algorithm's own parameter checks, ahead of the base's (populations, device)
+const bbo_params &CcpsoEngine::checked(const bbo_params &p)
 {
     BBO_REQUIRE(p.algo == BBO_ALGO_CCPSO, "CcpsoEngine: bad algo");
     BBO_REQUIRE(p.np >= 3, "CCPSO needs at least 3 particles (ring neighbourhood)");
     BBO_REQUIRE(p.npps >= 1 && p.npps <= 16, "CCPSO: between 1 and 16 swarm sizes (pps)");
-    BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(BBO_ERR_NO_DEVICE, "no HIP device visible: libbbopt_hip has no CPU path");
-    BBO_REQUIRE(p.device >= 0 && p.device < ndev, "device ordinal out of range");
-    BBO_HIP(hipSetDevice(p.device));
-    BBO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-}
-
-CcpsoEngine::~CcpsoEngine()
-{
-    if (stream_) (void) hipStreamDestroy(stream_);
+    return p;
 }
 
 void CcpsoEngine::init(int n, const double *lower, const double *upper, const double *guess,
@@ -38,9 +32,8 @@ void CcpsoEngine::init(int n, const double *lower, const double *upper, const do
 {
     (void) guess;   // never read (ccpso.cpp:66-112)
     BBO_REQUIRE(n >= 1 && n <= 1024, "CCPSO: dimension must be in [1, 1024]");
-    for (int j = 0; j < n; j++)
-        BBO_REQUIRE(std::isfinite(lower[j]) && std::isfinite(upper[j]),
-                "CCPSO draws its swarm from [lower, upper]: the bounds must be finite");
+    require_finite_box("CCPSO draws its swarm from [lower, upper]: the bounds must be finite", n,
+            lower, upper);
     for (int k = 0; k < params_.npps; k++)   // the reference throws when the size is drawn (:196)
         if (params_.pps[k] <= 0 || params_.pps[k] > n || n % params_.pps[k] != 0)
             throw Error(BBO_ERR_ARG, "Error [CC-PSO]: invalid component size.");
@@ -80,20 +73,10 @@ void CcpsoEngine::init(int n, const double *lower, const double *upper, const do
     grp_of_.alloc((size_t) P * n);
     radius_.alloc(rows);
     rpart_.alloc(rows * ((ld / 2 + 255) / 256));
-    lower_.alloc(ld);
-    upper_.alloc(ld);
-    aux_.alloc(ld);
     scal_.alloc(P);
-    std::vector<double> lo(ld, 0.), up(ld, 0.);
-    aux_h_.assign(ld, 0.);
-    std::copy(lower, lower + n, lo.begin());
-    std::copy(upper, upper + n, up.begin());
-    fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
-    lower_.upload(lo.data(), ld);
-    upper_.upload(up.data(), ld);
-    aux_.upload(aux_h_.data(), ld);
-    lower_h_.assign(lower, lower + n);
-    upper_h_.assign(upper, upper + n);
+    upload_box(n, c.ld, lower, upper, obj);
+    lower_h_.resize(n);      // (the local search's box: exactly n)
+    upper_h_.resize(n);
     nlocal_ = 0;
     std::vector<int> zi(sw, 0);
     strat_.upload(zi.data(), sw);
@@ -127,8 +110,7 @@ void CcpsoEngine::init(int n, const double *lower, const double *upper, const do
         for (int p = 0; p < P; p++) {
             X_.download(xh.data(), xh.size(), (size_t) p * c.np * c.ld);
             obj_.eval_host(xh.data(), c.np, c.n, c.ld, fh.data());
-            for (auto &v : fh)
-                if (v != v) v = std::numeric_limits<double>::infinity();
+            nan_to_inf(fh.data(), c.np);
             fX_.upload(fh.data(), c.np, (size_t) p * n * c.np);
         }
     }
@@ -164,7 +146,7 @@ void CcpsoEngine::host_eval_candidates()
                     for (int q = 0; q < cp; q++) work[rg[j * cp + q]] = src[rg[j * cp + q]];
                     double f = 0.;
                     obj_.eval_host(work.data(), 1, c.n, c.ld, &f);
-                    if (f != f) f = std::numeric_limits<double>::infinity();
+                    nan_to_inf(&f, 1);
                     (which ? fy : fx)[(size_t) j * c.np + i] = f;
                 }
         fX_.upload(fx.data(), fx.size(), (size_t) p * c.n * c.np);
@@ -186,7 +168,8 @@ void CcpsoEngine::host_eval_yhat()
         yhat_.download(yh.data(), c.ld, (size_t) p * c.ld);
         double f = 0.;
         obj_.eval_host(yh.data(), 1, c.n, c.ld, &f);
-        sc[p].fyhat = f != f ? std::numeric_limits<double>::infinity() : f;
+        nan_to_inf(&f, 1);
+        sc[p].fyhat = f;
         touched = true;
     }
     if (touched) scal_.upload(sc.data(), c.npop);
@@ -266,8 +249,7 @@ void CcpsoEngine::set_shard(int rank, int world)
 
 void CcpsoEngine::phase(int which)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "phase before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
+    enter("phase");
     c_.honor_stop = 0;
     if (which == 0) launch_regroup_eval();
     else if (which == 1) launch_rest();
@@ -298,8 +280,7 @@ int CcpsoEngine::table_record() const
 
 void CcpsoEngine::export_tables(double *dst, bool device_memory)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "export_tables before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
+    enter("export_tables");
     const int stride = shard_stride();
     double *out = dst;
     if (!device_memory) {
@@ -318,9 +299,8 @@ void CcpsoEngine::export_tables(double *dst, bool device_memory)
 
 void CcpsoEngine::merge_tables(const double *gathered, int world, bool device_memory)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "merge_tables before initialize()");
+    enter("merge_tables");
     BBO_REQUIRE(world == c_.shard_world, "merge_tables: world differs from the shard setting");
-    BBO_HIP(hipSetDevice(params_.device));
     const int stride = shard_stride();
     const double *src = gathered;
     if (!device_memory) {
@@ -373,7 +353,8 @@ double CcpsoEngine::eval_full(const double *x)
     if (!obj_.on_device()) {
         double f = 0.;
         obj_.eval_host(x, 1, c_.n, c_.n, &f);
-        return f != f ? std::numeric_limits<double>::infinity() : f;
+        nan_to_inf(&f, 1);
+        return f;
     }
     return builtin_objective_host(obj_.builtin, c_.n, x, aux_h_.data());
 }
@@ -476,65 +457,47 @@ void CcpsoEngine::after_generation(int gen_before)
     }
 }
 
+// with a local optimizer attached: `gen` before the chunk's one generation
+void CcpsoEngine::launch_chunk(int gens)
+{
+    if (local_) {
+        CcpScal s;
+        scal_.download(&s, 1, 0);
+        gen0_ = s.gen;
+    }
+    Engine::launch_chunk(gens);
+}
+
+void CcpsoEngine::after_chunk(bool in_run)
+{
+    if (!local_) return;
+    if (in_run) after_generation(gen0_);
+    else if (localfreq_ > 0 && gen0_ % localfreq_ == 0) local_search();   // (iterate()'s generation always runs)
+}
+
 void CcpsoEngine::iterate()
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "iterate() before initialize()");
+    enter("iterate()");
     require_unsharded("iterate()");
-    BBO_HIP(hipSetDevice(params_.device));
-    int gen0 = 0;
     if (local_) {
         CcpScal s;
         BBO_HIP(hipStreamSynchronize(stream_));
         scal_.download(&s, 1, 0);
-        gen0 = s.gen;
+        gen0_ = s.gen;
     }
-    generation(false);
-    BBO_HIP(hipStreamSynchronize(stream_));
-    if (local_ && localfreq_ > 0 && gen0 % localfreq_ == 0) local_search();
-    timer_.collect();
-}
-
-bool CcpsoEngine::all_stopped()
-{
-    std::vector<CcpScal> sc(c_.npop);
-    scal_.download(sc.data(), c_.npop);
-    for (const auto &s : sc)
-        if (!s.stop) return false;
-    return true;
+    Engine::iterate();
 }
 
 int CcpsoEngine::run(int max_generations)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "run() before initialize()");
+    enter("run()");
     require_unsharded("run()");
-    BBO_HIP(hipSetDevice(params_.device));
-    // (the reference's loop is `while (true) { iterate(); ... }`: at least one generation)
-    const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
-    int done = 0;
-    while (done < max_generations) {
-        if (all_stopped()) break;
-        const int chunk = (obj_.on_device() && !local_) ? std::min(poll, max_generations - done) : 1;
-        int gen0 = 0;
-        if (local_) {
-            CcpScal s;
-            scal_.download(&s, 1, 0);
-            gen0 = s.gen;
-        }
-        for (int g = 0; g < chunk; g++) generation(true);
-        BBO_HIP(hipStreamSynchronize(stream_));
-        if (local_) after_generation(gen0);
-        timer_.collect();
-        done += chunk;
-    }
-    return done;
+    return Engine::run(max_generations);
 }
 
 void CcpsoEngine::solution(int population, double *x_out, int *n_evals, int *converged)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "solution() before initialize()");
-    BBO_REQUIRE(population >= 0 && population < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("solution()", population);
     CcpScal s;
     scal_.download(&s, 1, population);
     std::vector<double> x(c_.ld);
@@ -542,14 +505,7 @@ void CcpsoEngine::solution(int population, double *x_out, int *n_evals, int *con
     std::copy(x.begin(), x.begin() + c_.n, x_out);
     *n_evals = s.fev;
     if (s.gen == 0) {
-        std::vector<double> rad(c_.np);
-        radius_.download(rad.data(), c_.np, (size_t) population * c_.np);
-        double mean = 0.;
-        for (double r : rad) mean += r;
-        mean /= c_.np;
-        double m2 = 0.;
-        for (double r : rad) m2 += (r - mean) * (r - mean);
-        *converged = m2 <= (c_.np - 1) * c_.stol * c_.stol ? 1 : 0;
+        *converged = radius_spread_converged(radius_, (size_t) population * c_.np, c_.np, c_.stol);
     } else {
         *converged = s.conv;
     }
@@ -559,21 +515,12 @@ void CcpsoEngine::optimize(int n, const double *lower, const double *upper, cons
         const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged)
 {
     require_unsharded("optimize()");
-    init(n, lower, upper, guess, obj);
-    run(std::numeric_limits<int>::max());
-    int conv = 0;
-    solution(0, x_out, n_evals, &conv);
-    CcpScal s;
-    scal_.download(&s, 1, 0);
-    *converged = s.stop == 1 ? 1 : 0;
+    Engine::optimize(n, lower, upper, guess, obj, x_out, n_evals, converged);
 }
 
 int CcpsoEngine::get(const std::string &k, int p, double *out, int cap)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "get() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("get()", p);
     const CcpConst &c = c_;
     CcpScal s;
     scal_.download(&s, 1, p);
@@ -581,7 +528,7 @@ int CcpsoEngine::get(const std::string &k, int p, double *out, int cap)
         if (out && cap >= 1) out[0] = v;
         return 1;
     };
-    if (k == "profile") return timer_.report(out, cap);
+    if (k == "profile") return profile_report(out, cap);
     if (k == "x" || k == "y") {
         const int cnt = c.np * c.n;
         if (out && cap >= cnt) {
@@ -635,16 +582,10 @@ int CcpsoEngine::get(const std::string &k, int p, double *out, int cap)
 
 int CcpsoEngine::set(const std::string &k, int p, const double *in, int count)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "set() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    if (k == "profile") {
-        timer_.enable(in[0] != 0., K_COUNT, K_NAMES);
-        return 1;
-    }
+    enter_population("set()", p);      // (synchronises: the uploads below are not stream-ordered)
+    if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
     // what a host-side local search (ccpso.cpp:371-435; the Python class drives it) hands back:
     // the re-weighted context vector, its value, the evaluations it spent, the `improved` flag
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));      // (uploads below are not stream-ordered)
     if (k == "yhat") {
         BBO_REQUIRE(count == c_.n, "set yhat: wrong element count");
         std::vector<double> v(c_.ld, 0.);

@@ -8,7 +8,7 @@
 // that is embarrassingly parallel (yhat does not move while they run).
 #pragma once
 
-#include "bbo_common.hpp"
+#include "bbo_engine.hpp"
 
 namespace bbo {
 
@@ -41,10 +41,9 @@ struct CcpDev {
     CcpScal *scal;
 };
 
-class CcpsoEngine: public Optimizer {
+class CcpsoEngine: public Engine<CcpScal> {
 public:
     explicit CcpsoEngine(const bbo_params &p);
-    ~CcpsoEngine() override;
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
     void iterate() override;
@@ -68,33 +67,31 @@ public:
     double eval_full(const double *x);     // the objective at one n-vector, on the host
 
 private:
+    static const bbo_params &checked(const bbo_params &p);
     void launch_regroup_eval();
     void launch_rest();
-    void generation(bool honor_stop);
+    void generation(bool honor_stop) override;
+    // (the reference's loop is `while (true) { iterate(); ... }`: at least one generation)
+    bool budget_spent(const CcpScal&) const override { return false; }
+    int chunk_limit(int want) override { return local_ ? 1 : want; }   // a search may follow every generation
+    void launch_chunk(int gens) override;
+    void after_chunk(bool in_run) override;
     void host_eval_candidates();
     void host_eval_yhat();
-    bool all_stopped();
     int shard_stride() const;
     void require_unsharded(const char *what) const;
 
-    bbo_params params_;
-    ObjectiveSpec obj_;
     CcpConst c_ {};
     CcpDev d_ {};
-    hipStream_t stream_ = nullptr;
-    bool inited_ = false;
     int shard_rank_ = 0, shard_world_ = 1;     // survive init() (c_ is rebuilt there)
     void local_search();
     void after_generation(int gen_before);
     Optimizer *local_ = nullptr;               // borrowed, like the reference's `local` pointer
     int localfreq_ = 10, nlocal_ = 0;
+    int gen0_ = 0;                             // with a local optimizer: `gen` before the generation in flight
     uint64_t local_seed0_ = 0;
-    std::vector<double> lower_h_, upper_h_;
-    std::vector<double> aux_h_;
-    DevBuf<double> X_, Y_, yhat_, ysave_, fX_, fY_, radius_, rpart_, lower_, upper_, aux_, gather_, stage_;
+    DevBuf<double> X_, Y_, yhat_, ysave_, fX_, fY_, radius_, rpart_, gather_, stage_;
     DevBuf<int> ibest_, strat_, range_, grp_of_;
-    DevBuf<CcpScal> scal_;
-    KernelTimer timer_;
 };
 
 Optimizer* make_ccpso_engine(const bbo_params &p);

@@ -47,30 +47,35 @@ size_t gram_lds_bytes(int ld, int rps)
     return ((size_t) rps * gram_ldy(ld) + 2 * (size_t) rps + (size_t) rpp * ld) * sizeof(double);
 }
 
+// where element (i, j) of an ld x ld matrix sits in MFMA B-fragment order (BDp, ISp; the kernels'
+// packed operands): tile i >> 4, k-step j >> 2 of ld / 4, lane (j & 3, i & 15) of 64
+inline size_t bfrag_index(size_t i, size_t j, size_t ld)
+{
+    return ((i >> 4) * (ld >> 2) + (j >> 2)) * 64 + ((j & 3) << 4) + (i & 15);
+}
+
 } // namespace
 
 CmaEngine::CmaEngine(const bbo_params &p) :
-        params_(p)
+        Engine(checked(p))
+{
+    BBO_HIP(hipHostMalloc((void**) &mw_fail_host_, sizeof(int)));
+    *mw_fail_host_ = 0;
+}
+
+// the algorithm's own parameter checks, ahead of the base's (populations, device)
+const bbo_params &CmaEngine::checked(const bbo_params &p)
 {
     BBO_REQUIRE(p.algo == BBO_ALGO_CMAES || p.algo == BBO_ALGO_ACTIVE_CMAES
             || p.algo == BBO_ALGO_SEP_CMAES || p.algo == BBO_ALGO_CHOLESKY_CMAES,
             "CmaEngine: algo must be CMAES, ACTIVE_CMAES, SEP_CMAES or CHOLESKY_CMAES");
     BBO_REQUIRE(p.np >= 4, "CMA-ES needs np >= 4 (mu >= 2, best/worst pairs)");
-    BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(BBO_ERR_NO_DEVICE, "no HIP device visible: libbbopt_hip has no CPU path");
-    BBO_REQUIRE(p.device >= 0 && p.device < ndev, "device ordinal out of range");
-    BBO_HIP(hipSetDevice(p.device));
-    BBO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    BBO_HIP(hipHostMalloc((void**) &mw_fail_host_, sizeof(int)));
-    *mw_fail_host_ = 0;
+    return p;
 }
 
 CmaEngine::~CmaEngine()
 {
     mw_release();
-    if (stream_) (void) hipStreamDestroy(stream_);
     if (mw_fail_host_) (void) hipHostFree(mw_fail_host_);
 }
 
@@ -312,11 +317,10 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
         C_.alloc(P * ld2);
         BDp_.alloc(P * ld2);
         std::vector<double> eyeA(P * ld2, 0.), eyeP(P * ld2, 0.);
-        const size_t KS = ld >> 2;
         for (int p = 0; p < P; p++)
             for (size_t i = 0; i < (size_t) n; i++) {
                 eyeA[p * ld2 + i * ld + i] = 1.;
-                eyeP[p * ld2 + ((i >> 4) * KS + (i >> 2)) * 64 + ((i & 3) << 4) + (i & 15)] = 1.;
+                eyeP[p * ld2 + bfrag_index(i, i, ld)] = 1.;
             }
         A_.upload(eyeA.data(), P * ld2);
         allow_lds((const void*) chol_factor, 136 * 1024);      // (ld <= 128: the matrix in LDS)
@@ -332,22 +336,10 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     hist_kth_.alloc((size_t) P * c.hlen);
     weights_.alloc(c.mu);
     weights_.upload(w.data(), c.mu);
-    lower_.alloc(ld);
-    upper_.alloc(ld);
-    aux_.alloc(ld);
     scal_.alloc(P);
     zinject_.release();
     zrecord_.release();
-
-    lower_h_.assign(ld, 0.);
-    upper_h_.assign(ld, 0.);
-    aux_h_.assign(ld, 0.);
-    std::copy(lower, lower + n, lower_h_.begin());
-    std::copy(upper, upper + n, upper_h_.begin());
-    fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
-    lower_.upload(lower_h_.data(), ld);
-    upper_.upload(upper_h_.data(), ld);
-    aux_.upload(aux_h_.data(), ld);
+    upload_box(n, c.ld, lower, upper, obj);
 
     // B = C = C^-1/2 = I, D = 1.  The reference resize()s _b/_c, so on a re-init of the
     // SAME object with the same n the old off-diagonals survive and only the diagonals are
@@ -355,27 +347,27 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     std::vector<double> eye(dense ? P * ld2 : 0, 0.), ones(P * ld, 1.);
     csep_.upload(ones.data(), P * ld);
     if (dense) {
-    for (int p = 0; p < P; p++)
-        for (int i = 0; i < n; i++) eye[p * ld2 + (size_t) i * ld + i] = 1.;
-    if (same_shape) {
-        std::vector<double> bm(P * ld2), cm(P * ld2);
-        B_.download(bm.data(), P * ld2);
-        C_.download(cm.data(), P * ld2);
         for (int p = 0; p < P; p++)
-            for (int i = 0; i < n; i++) {
-                bm[p * ld2 + (size_t) i * ld + i] = 1.;
-                cm[p * ld2 + (size_t) i * ld + i] = 1.;
-            }
-        B_.upload(bm.data(), P * ld2);
-        C_.upload(cm.data(), P * ld2);
-    } else {
-        B_.alloc(P * ld2);
-        C_.alloc(P * ld2);
-        B_.upload(eye.data(), P * ld2);
-        C_.upload(eye.data(), P * ld2);
+            for (int i = 0; i < n; i++) eye[p * ld2 + (size_t) i * ld + i] = 1.;
+        if (same_shape) {
+            std::vector<double> bm(P * ld2), cm(P * ld2);
+            B_.download(bm.data(), P * ld2);
+            C_.download(cm.data(), P * ld2);
+            for (int p = 0; p < P; p++)
+                for (int i = 0; i < n; i++) {
+                    bm[p * ld2 + (size_t) i * ld + i] = 1.;
+                    cm[p * ld2 + (size_t) i * ld + i] = 1.;
+                }
+            B_.upload(bm.data(), P * ld2);
+            C_.upload(cm.data(), P * ld2);
+        } else {
+            B_.alloc(P * ld2);
+            C_.alloc(P * ld2);
+            B_.upload(eye.data(), P * ld2);
+            C_.upload(eye.data(), P * ld2);
+        }
+        isc_.upload(eye.data(), P * ld2);
     }
-    isc_.upload(eye.data(), P * ld2);
-    }   // dense
     D_.upload(ones.data(), P * ld);
     keep_bc_ = dense;
     last_n_ = n;
@@ -533,8 +525,8 @@ void CmaEngine::launch_sample_eval()
             hipLaunchKernelGGL(cma_sample_eval128_tri, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
                     full);
         } else
-        hipLaunchKernelGGL(cma_sample_eval128, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
-                full);
+            hipLaunchKernelGGL(cma_sample_eval128, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
+                    full);
         zn_valid = true;
     } else if (c.ld == 128 && (long) c.npop * (c.lambda_pad / 16) <= sample_wide_max_tiles_) {
         // one population at a time: a 16-row tile per WORKGROUP, one column tile per wavefront (the
@@ -545,8 +537,8 @@ void CmaEngine::launch_sample_eval()
             hipLaunchKernelGGL((cma_sample_eval<1, 8, true>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds,
                     stream_, d_, c_);
         else
-        hipLaunchKernelGGL((cma_sample_eval<1, 8>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds, stream_,
-                d_, c_);
+            hipLaunchKernelGGL((cma_sample_eval<1, 8>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds, stream_,
+                    d_, c_);
         zn_valid = true;
     } else if (c.ld <= 128) {
         // 64 candidates per workgroup, packed operand held in registers
@@ -569,12 +561,12 @@ void CmaEngine::launch_sample_eval()
         if ((long) grid.x * grid.y <= 32 && c.ld <= 256 && !(d_.dbg & 268435456))
             hipLaunchKernelGGL((cma_sample_eval<1, 16>), grid, dim3(1024), lds, stream_, d_, c_);
         else
-        switch (pick_maxt(c.ld)) {
-        case 1: hipLaunchKernelGGL(cma_sample_eval<1>, grid, dim3(256), lds, stream_, d_, c_); break;
-        case 2: hipLaunchKernelGGL(cma_sample_eval<2>, grid, dim3(256), lds, stream_, d_, c_); break;
-        case 4: hipLaunchKernelGGL(cma_sample_eval<4>, grid, dim3(256), lds, stream_, d_, c_); break;
-        default: hipLaunchKernelGGL(cma_sample_eval<8>, grid, dim3(256), lds, stream_, d_, c_); break;
-        }
+            switch (pick_maxt(c.ld)) {
+            case 1: hipLaunchKernelGGL(cma_sample_eval<1>, grid, dim3(256), lds, stream_, d_, c_); break;
+            case 2: hipLaunchKernelGGL(cma_sample_eval<2>, grid, dim3(256), lds, stream_, d_, c_); break;
+            case 4: hipLaunchKernelGGL(cma_sample_eval<4>, grid, dim3(256), lds, stream_, d_, c_); break;
+            default: hipLaunchKernelGGL(cma_sample_eval<8>, grid, dim3(256), lds, stream_, d_, c_); break;
+            }
         zn_valid = true;
     }
     timer_.end(stream_);
@@ -791,7 +783,7 @@ void CmaEngine::launch_eigen()
                 hipLaunchKernelGGL(cma_tred_tail, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
             }
         } else
-        hipLaunchKernelGGL(cma_eigen_g1, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
+            hipLaunchKernelGGL(cma_eigen_g1, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
         hipLaunchKernelGGL(cma_eig_halves, dim3(3, c.npop), dim3(512), plh.lds_bytes, stream_, d_, c_,
                 plh, pl.lda);
         // the top merge: with few matrices in flight its secular equation goes to ceil(n / 32)
@@ -808,9 +800,9 @@ void CmaEngine::launch_eigen()
                 hipLaunchKernelGGL(cma_eig_lowner, dim3((c.n + 31) / 32, c.npop), dim3(512), 0, stream_, d_, c_);
                 hipLaunchKernelGGL(cma_eig_fcols, dim3((c.n + 31) / 32, c.npop), dim3(512), 0, stream_, d_, c_);
             } else
-            hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 2);
+                hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 2);
         } else
-        hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
+            hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
     } else if (pl.hybrid)
         hipLaunchKernelGGL(cma_eigen_g, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_,
                 pl, 0);
@@ -868,8 +860,8 @@ void CmaEngine::launch_eigen()
                 hipLaunchKernelGGL(cma_eig_wy4, dim3((c.n + 15) / 16, c.npop), dim3(256), 0, stream_, d_, c_,
                         wy4_packs ? (fcols_closed ? 2 : 1) : 0);
             } else
-            hipLaunchKernelGGL(cma_eig_wy, dim3((c.n + 63) / 64, c.npop), dim3(256), 0, stream_, d_,
-                    c_);
+                hipLaunchKernelGGL(cma_eig_wy, dim3((c.n + 63) / 64, c.npop), dim3(256), 0, stream_, d_,
+                        c_);
         }
         BBO_HIP(hipGetLastError());
     }
@@ -887,7 +879,7 @@ void CmaEngine::launch_history_stop()
     if (c_.variant == 3)
         hipLaunchKernelGGL(chol_history_stop, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
     else
-    hipLaunchKernelGGL(cma_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
+        hipLaunchKernelGGL(cma_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
 }
@@ -900,14 +892,13 @@ void CmaEngine::host_evaluate()
     std::vector<double> xh(rows * c.ld), fh(rows, std::numeric_limits<double>::infinity());
     BBO_HIP(hipStreamSynchronize(stream_));
     X_.download(xh.data(), xh.size());
-    std::vector<CmaScal> sc;
-    fetch_scal(sc);
+    std::vector<CmaScal> sc(c.npop);
+    scal_.download(sc.data(), c.npop);
     for (int p = 0; p < c.npop; p++) {
         if (c.honor_stop && sc[p].stop) continue;
         const size_t r0 = (size_t) p * c.lambda_pad;
         obj_.eval_host(xh.data() + r0 * c.ld, c.lambda, c.n, c.ld, fh.data() + r0);
-        for (int r = 0; r < c.lambda; r++)
-            if (fh[r0 + r] != fh[r0 + r]) fh[r0 + r] = std::numeric_limits<double>::infinity();
+        nan_to_inf(fh.data() + r0, c.lambda);
     }
     f_.upload(fh.data(), rows);
 }
@@ -995,31 +986,19 @@ void CmaEngine::inject_normals(const double *z, int count)
     d_.zinject = zinject_.p;
 }
 
-void CmaEngine::iterate()
+void CmaEngine::after_chunk(bool in_run)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "iterate() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    generation(false);
-    BBO_HIP(hipStreamSynchronize(stream_));
+    if (in_run) return;      // (run() looks at its next poll: inspect)
     if (mw_check_failed()) {
         // the spread reduction gave up (bbo_eig_mw.hpp): the decomposition this generation was due
         // is not lost -- eigenlastev has not moved, the one-workgroup kernels take it now
         launch_eigen();
         BBO_HIP(hipStreamSynchronize(stream_));
     }
-    timer_.collect();
 }
 
-void CmaEngine::fetch_scal(std::vector<CmaScal> &out)
+void CmaEngine::inspect(const std::vector<CmaScal> &sc)
 {
-    out.resize(c_.npop);
-    scal_.download(out.data(), c_.npop);
-}
-
-bool CmaEngine::all_stopped()
-{
-    std::vector<CmaScal> sc;
-    fetch_scal(sc);
     // (the one host-side copy of "every population's C^-1/2 matches its (B, D)": see launch_rank)
     bool stale = false;
     for (const auto &s : sc) stale = stale || !s.basis_ok;
@@ -1032,52 +1011,24 @@ bool CmaEngine::all_stopped()
             mw_disabled_ = true;
             mw_release();
         }
-    for (const auto &s : sc)
-        if (!s.stop) return false;
-    return true;
 }
 
-int CmaEngine::run(int max_generations)
+// (one launch = `chunk` generations on the fused path: keep a launch to tens of milliseconds
+// whatever poll_every says)
+int CmaEngine::chunk_limit(int want)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "run() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
-    int done = 0;
-    // a population whose budget is already spent must not take another generation
-    // (the reference's loop is `while (_fev < _mfev)`, base_cmaes.cpp:166)
-    {
-        std::vector<CmaScal> sc;
-        fetch_scal(sc);
-        bool touched = false;
-        for (auto &s : sc)
-            if (!s.stop && s.fev >= c_.mfev) {
-                s.stop = 2;
-                touched = true;
-            }
-        if (touched) scal_.upload(sc.data(), c_.npop);
-    }
-    while (done < max_generations) {
-        if (all_stopped()) break;
-        int chunk = obj_.on_device() ? std::min(poll, max_generations - done) : 1;
-        // (one launch = `chunk` generations on the fused path: keep a launch to tens of
-        // milliseconds whatever poll_every says)
-        if (small_fused_ok()) chunk = std::min(chunk, 512);
-        if (small_fused_ok()) launch_small(chunk, true);
-        else
-            for (int g = 0; g < chunk; g++) generation(true);
-        BBO_HIP(hipStreamSynchronize(stream_));
-            timer_.collect();
-        done += chunk;
-    }
-    return done;
+    return small_fused_ok() ? std::min(want, 512) : want;
+}
+
+void CmaEngine::launch_chunk(int gens)
+{
+    if (small_fused_ok()) launch_small(gens, true);
+    else Engine::launch_chunk(gens);
 }
 
 void CmaEngine::solution(int population, double *x_out, int *n_evals, int *converged)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "solution() before initialize()");
-    BBO_REQUIRE(population >= 0 && population < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("solution()", population);
     CmaScal s;
     scal_.download(&s, 1, population);
     std::vector<double> x(c_.ld);
@@ -1129,10 +1080,7 @@ double CmaEngine::evaluate_point(const double *x)
 // ---- named state access ---------------------------------------------------------------
 int CmaEngine::get(const std::string &k, int p, double *out, int cap)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "get() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("get()", p);
     const CmaConst &c = c_;
     const size_t ld = c.ld, n = c.n;
     auto vec = [&](const DevBuf<double> &b) {   // [P][ld] -> n
@@ -1182,15 +1130,12 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         return mat(isc_, n, ld, n, p * ld * ld);
     }
     if (k == "BD") {
-        // the sampler's operand B diag(D) as the kernels hold it (MFMA B-fragment order), unpacked to
-        // n x n row-major: element (i, j) sits at tile i >> 4, k-step j >> 2, lane (j & 3, i & 15)
+        // the sampler's operand B diag(D) as the kernels hold it (bfrag_index), unpacked to n x n row-major
         if (out && cap >= (int) (n * n)) {
             std::vector<double> pk(ld * ld);
             BDp_.download(pk.data(), ld * ld, p * ld * ld);
-            const size_t KS = ld >> 2;
             for (size_t i = 0; i < n; i++)
-                for (size_t j = 0; j < n; j++)
-                    out[i * n + j] = pk[((i >> 4) * KS + (j >> 2)) * 64 + ((j & 3) << 4) + (i & 15)];
+                for (size_t j = 0; j < n; j++) out[i * n + j] = pk[bfrag_index(i, j, ld)];
         }
         return (int) (n * n);
     }
@@ -1232,7 +1177,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         if (out && cap >= (int) cnt) zrecord_.download(out, cnt, p * cnt);
         return (int) cnt;
     }
-    if (k == "profile") return timer_.report(out, cap);
+    if (k == "profile") return profile_report(out, cap);
     if (k == "eig_work") {   // diagnostic: the eigensolver's global scratch of population p
         const size_t cnt = std::min((size_t) 4 * eig_slab(c.ld), eig_work_.count);
         if (out && (size_t) cap >= cnt) eig_work_.download(out, cnt, (size_t) p * 4 * eig_slab(c.ld));
@@ -1313,10 +1258,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
 
 int CmaEngine::set(const std::string &k, int p, const double *in, int count)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "set() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("set()", p);
     rank_wrote_norms_ = false;      // (S of a ranking before this call may not match the new state)
     const CmaConst &c = c_;
     const size_t ld = c.ld, n = c.n;
@@ -1343,11 +1285,10 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
         if (c.variant != 3) throw Error(BBO_ERR_KEY, "'A' belongs to CholeskyCMAES");
         BBO_REQUIRE(count == (int) (n * n), "set: wrong element count");
         std::vector<double> a(ld * ld, 0.), pk(ld * ld, 0.);
-        const size_t KS = ld >> 2;
         for (size_t i = 0; i < n; i++)
             for (size_t j = 0; j <= i; j++) {
                 a[i * ld + j] = in[i * n + j];
-                pk[((i >> 4) * KS + (j >> 2)) * 64 + ((j & 3) << 4) + (i & 15)] = in[i * n + j];
+                pk[bfrag_index(i, j, ld)] = in[i * n + j];
             }
         A_.upload(a.data(), ld * ld, p * ld * ld);
         BDp_.upload(pk.data(), ld * ld, p * ld * ld);
@@ -1402,10 +1343,7 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
         BBO_HIP(hipStreamSynchronize(stream_));
         return r;
     }
-    if (k == "profile") {
-        timer_.enable(in[0] != 0., K_COUNT, K_NAMES);
-        return 1;
-    }
+    if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
     if (k == "dbg") {
         d_.dbg = (int) in[0];
         return 1;

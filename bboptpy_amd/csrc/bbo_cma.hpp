@@ -6,7 +6,7 @@
 // See DESIGN.md for the kernel table and the data layout.
 #pragma once
 
-#include "bbo_common.hpp"
+#include "bbo_engine.hpp"
 
 namespace bbo {
 
@@ -88,18 +88,17 @@ struct CmaDev {
     int *mw_fail_host;                // pinned host word: a spread reduction of this engine timed out
 };
 
-class CmaEngine: public Optimizer {
+class CmaEngine: public Engine<CmaScal> {
 public:
     explicit CmaEngine(const bbo_params &p);
     ~CmaEngine() override;
 
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
-    void iterate() override;
     void solution(int population, double *x_out, int *n_evals, int *converged) override;
+    // (its own form: max_gen = mfev / lambda + 2, `converged` straight from the stop flag)
     void optimize(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged) override;
-    int run(int max_generations) override;
     int get(const std::string &key, int population, double *out, int cap) override;
     int set(const std::string &key, int population, const double *in, int count) override;
     int dimension() const override { return c_.n; }
@@ -122,7 +121,14 @@ public:
     }
 
 private:
-    void generation(bool honor_stop);
+    static const bbo_params &checked(const bbo_params &p);
+    void generation(bool honor_stop) override;
+    // (c_.mfev: set_params may have moved params_.mfev since init())
+    bool budget_spent(const CmaScal &s) const override { return s.fev >= c_.mfev; }
+    void inspect(const std::vector<CmaScal> &sc) override;   // basis_maybe_stale_, the spread reduction's flags
+    int chunk_limit(int want) override;                      // the fused path: at most 512 generations a launch
+    void launch_chunk(int gens) override;                    // the fused path: one launch
+    void after_chunk(bool in_run) override;                  // iterate(): a spread reduction that gave up is redone
     bool small_fused_ok() const;
     void launch_small(int gens, bool honor_stop);
     void launch_sample_eval();
@@ -132,15 +138,9 @@ private:
     void launch_eigen();
     void launch_history_stop();
     void host_evaluate();
-    void fetch_scal(std::vector<CmaScal> &out);
-    bool all_stopped();
 
-    bbo_params params_;
-    ObjectiveSpec obj_;
     CmaConst c_ {};
     CmaDev d_ {};
-    hipStream_t stream_ = nullptr;
-    bool inited_ = false;
     bool keep_bc_ = false;    // B and C survive a re-init of the same object (cmaes.cpp:53-54)
     bool basis_maybe_stale_ = false;   // some population's basis_ok may be 0 (refreshed at every poll)
     // the Householder reduction spread over several workgroups (128 < n <= 256, few populations):
@@ -156,22 +156,18 @@ private:
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;
-    std::vector<double> lower_h_, upper_h_, aux_h_;
 
     DevBuf<double> zn2_, csep_, A_;
     DevBuf<double> X_, f_, xmean_, xold_, pc_, ps_, C_, B_, D_, isc_, BDp_, ISp_, S_,
-            gram_part_, mean_part_, hist_best_, hist_kth_, eig_work_, weights_, lower_,
-            upper_, aux_, zinject_, zrecord_;
+            gram_part_, mean_part_, hist_best_, hist_kth_, eig_work_, weights_, zinject_, zrecord_;
     DevBuf<int> rank_, order_, chol_repairs_;
     DevBuf<long long> stamps_;
-    DevBuf<CmaScal> scal_;
     int *mw_fail_host_ = nullptr;   // pinned, device-visible: raised by a spread reduction that timed out
     long mw_reserved_ = 0;          // workgroups this engine holds of the device's MwBudget
     bool mw_launched_ = false;      // a spread kernel went out since the flag was last read
     bool mw_reserve(long workgroups);
     void mw_release();
     bool mw_check_failed();         // after a synchronisation: true once when the flag went up
-    KernelTimer timer_;
 };
 
 } // namespace bbo

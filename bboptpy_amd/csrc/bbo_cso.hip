@@ -15,28 +15,22 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:cso_mean", "bbo:cso_shuffle",
 }
 
 CsoEngine::CsoEngine(const bbo_params &p) :
-        params_(p)
+        Engine(checked(p))
+{
+}
+
+// the algorithm's own parameter checks and adjustments, ahead of the base's (populations, device)
+bbo_params CsoEngine::checked(bbo_params p)
 {
     BBO_REQUIRE(p.algo == BBO_ALGO_CSO, "CsoEngine: bad algo");
     BBO_REQUIRE(p.np >= 2, "CSO needs at least 2 particles");
-    BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
     // cso.cpp:53-64: at least two particles per competition, np rounded up to a multiple
-    if (params_.pcompete < 2) {
-        params_.pcompete = 2;
+    if (p.pcompete < 2) {
+        p.pcompete = 2;
         fprintf(stderr, "Warning [CSO]: particles per competition is too small - adjusted.\n");
     }
-    while (params_.np % params_.pcompete != 0) params_.np++;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(BBO_ERR_NO_DEVICE, "no HIP device visible: libbbopt_hip has no CPU path");
-    BBO_REQUIRE(p.device >= 0 && p.device < ndev, "device ordinal out of range");
-    BBO_HIP(hipSetDevice(p.device));
-    BBO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-}
-
-CsoEngine::~CsoEngine()
-{
-    if (stream_) (void) hipStreamDestroy(stream_);
+    while (p.np % p.pcompete != 0) p.np++;
+    return p;
 }
 
 void CsoEngine::init(int n, const double *lower, const double *upper, const double *guess,
@@ -44,9 +38,8 @@ void CsoEngine::init(int n, const double *lower, const double *upper, const doub
 {
     (void) guess;   // CSO never reads it (cso.cpp:67-112)
     BBO_REQUIRE(n >= 1 && n <= 1024, "CSO: dimension must be in [1, 1024]");
-    for (int j = 0; j < n; j++)
-        BBO_REQUIRE(std::isfinite(lower[j]) && std::isfinite(upper[j]),
-                "CSO draws its swarm from [lower, upper]: the bounds must be finite");
+    require_finite_box("CSO draws its swarm from [lower, upper]: the bounds must be finite", n,
+            lower, upper);
     BBO_HIP(hipSetDevice(params_.device));
     obj_ = obj;
     const int P = params_.populations;
@@ -97,18 +90,8 @@ void CsoEngine::init(int n, const double *lower, const double *upper, const doub
     c.nwg = fuse_g_ ? (c.ngroup + 256 / fuse_g_ - 1) / (256 / fuse_g_) : 1;
     wgpart_.alloc(fuse_g_ ? (size_t) P * c.nwg * ld : 1);
     fpart_.alloc((size_t) P * c.fparts * CSO_FPART);
-    lower_.alloc(ld);
-    upper_.alloc(ld);
-    aux_.alloc(ld);
     scal_.alloc(P);
-    std::vector<double> lo(ld, 0.), up(ld, 0.);
-    aux_h_.assign(ld, 0.);
-    std::copy(lower, lower + n, lo.begin());
-    std::copy(upper, upper + n, up.begin());
-    fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
-    lower_.upload(lo.data(), ld);
-    upper_.upload(up.data(), ld);
-    aux_.upload(aux_h_.data(), ld);
+    upload_box(n, c.ld, lower, upper, obj);
     std::vector<CsoScal> sc(P);
     for (auto &s : sc) {
         std::memset(&s, 0, sizeof(s));
@@ -165,7 +148,8 @@ void CsoEngine::host_evaluate(bool losers_only)
             const int row = occ[s];
             double f = 0.;
             obj_.eval_host(xh.data() + (size_t) row * c.ld, 1, c.n, c.ld, &f);
-            fh[row] = f != f ? std::numeric_limits<double>::infinity() : f;
+            nan_to_inf(&f, 1);
+            fh[row] = f;
         }
         f_.upload(fh.data(), c.np, (size_t) p * c.np);
     }
@@ -230,59 +214,9 @@ void CsoEngine::generation(bool honor_stop)
     BBO_HIP(hipGetLastError());
 }
 
-void CsoEngine::iterate()
-{
-    if (!inited_) throw Error(BBO_ERR_STATE, "iterate() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    generation(false);
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
-}
-
-bool CsoEngine::all_stopped()
-{
-    std::vector<CsoScal> sc(c_.npop);
-    scal_.download(sc.data(), c_.npop);
-    for (const auto &s : sc)
-        if (!s.stop) return false;
-    return true;
-}
-
-int CsoEngine::run(int max_generations)
-{
-    if (!inited_) throw Error(BBO_ERR_STATE, "run() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    {
-        // `while (_fev < _mfev)`, cso.cpp:167
-        std::vector<CsoScal> sc(c_.npop);
-        scal_.download(sc.data(), c_.npop);
-        bool touched = false;
-        for (auto &s : sc)
-            if (!s.stop && s.fev >= c_.mfev) {
-                s.stop = 2;
-                touched = true;
-            }
-        if (touched) scal_.upload(sc.data(), c_.npop);
-    }
-    const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
-    int done = 0;
-    while (done < max_generations) {
-        if (all_stopped()) break;
-        const int chunk = obj_.on_device() ? std::min(poll, max_generations - done) : 1;
-        for (int g = 0; g < chunk; g++) generation(true);
-        BBO_HIP(hipStreamSynchronize(stream_));
-        timer_.collect();
-        done += chunk;
-    }
-    return done;
-}
-
 void CsoEngine::solution(int population, double *x_out, int *n_evals, int *converged)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "solution() before initialize()");
-    BBO_REQUIRE(population >= 0 && population < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("solution()", population);
     CsoScal s;
     scal_.download(&s, 1, population);
     std::vector<double> x(c_.ld);
@@ -292,24 +226,9 @@ void CsoEngine::solution(int population, double *x_out, int *n_evals, int *conve
     *converged = s.conv;
 }
 
-void CsoEngine::optimize(int n, const double *lower, const double *upper, const double *guess,
-        const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged)
-{
-    init(n, lower, upper, guess, obj);
-    run(std::numeric_limits<int>::max());
-    int conv = 0;
-    solution(0, x_out, n_evals, &conv);
-    CsoScal s;
-    scal_.download(&s, 1, 0);
-    *converged = s.stop == 1 ? 1 : 0;
-}
-
 int CsoEngine::get(const std::string &k, int p, double *out, int cap)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "get() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("get()", p);
     const CsoConst &c = c_;
     CsoScal s;
     scal_.download(&s, 1, p);
@@ -318,7 +237,7 @@ int CsoEngine::get(const std::string &k, int p, double *out, int cap)
         if (out && cap >= 1) out[0] = v;
         return 1;
     };
-    if (k == "profile") return timer_.report(out, cap);
+    if (k == "profile") return profile_report(out, cap);
     // per-particle arrays are reported in SLOT order, like the reference's _swarm
     if (k == "x" || k == "v" || k == "pmean") {
         const int cnt = c.np * c.n;
@@ -368,13 +287,9 @@ int CsoEngine::get(const std::string &k, int p, double *out, int cap)
 
 int CsoEngine::set(const std::string &k, int p, const double *in, int count)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "set() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
+    enter_population("set()", p);
     (void) count;
-    if (k == "profile") {
-        timer_.enable(in[0] != 0., K_COUNT, K_NAMES);
-        return 1;
-    }
+    if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
     throw Error(BBO_ERR_KEY, "unknown or read-only state key '" + k + "'");
 }
 

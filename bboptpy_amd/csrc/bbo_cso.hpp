@@ -9,7 +9,7 @@
 // pointers keep referring to), the swarm ORDER is the permutation occ[slot] = row.
 #pragma once
 
-#include "bbo_common.hpp"
+#include "bbo_engine.hpp"
 
 namespace bbo {
 
@@ -39,38 +39,26 @@ struct CsoDev {
     CsoScal *scal;
 };
 
-class CsoEngine: public Optimizer {
+class CsoEngine: public Engine<CsoScal> {
 public:
     explicit CsoEngine(const bbo_params &p);
-    ~CsoEngine() override;
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
-    void iterate() override;
     void solution(int population, double *x_out, int *n_evals, int *converged) override;
-    void optimize(int n, const double *lower, const double *upper, const double *guess,
-            const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged) override;
-    int run(int max_generations) override;
     int get(const std::string &key, int population, double *out, int cap) override;
     int set(const std::string &key, int population, const double *in, int count) override;
     int dimension() const override { return c_.n; }
 
 private:
-    void generation(bool honor_stop);
+    static bbo_params checked(bbo_params p);
+    void generation(bool honor_stop) override;
     void host_evaluate(bool losers_only);
-    bool all_stopped();
 
-    bbo_params params_;
-    ObjectiveSpec obj_;
     CsoConst c_ {};
     CsoDev d_ {};
-    hipStream_t stream_ = nullptr;
-    bool inited_ = false;
-    std::vector<double> aux_h_;
-    DevBuf<double> X_, V_, PM_, f_, radius_, mean_, meanw_, colpart_, wgpart_, fpart_, lower_, upper_, aux_;
+    DevBuf<double> X_, V_, PM_, f_, radius_, mean_, meanw_, colpart_, wgpart_, fpart_;
     int fuse_g_ = 0;            // > 0: lanes per group of cso_compete, which then maintains the swarm mean's sums
     DevBuf<int> occ_, occ2_;
-    DevBuf<CsoScal> scal_;
-    KernelTimer timer_;
 };
 
 Optimizer* make_cso_engine(const bbo_params &p);

@@ -15,7 +15,12 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:de_generation", "bbo:de_bookk
 }
 
 DeEngine::DeEngine(const bbo_params &p) :
-        params_(p)
+        Engine(checked(p))
+{
+}
+
+// the algorithm's own parameter checks, ahead of the base's (populations, device)
+const bbo_params &DeEngine::checked(const bbo_params &p)
 {
     BBO_REQUIRE(p.algo == BBO_ALGO_SHADE || p.algo == BBO_ALGO_JADE || p.algo == BBO_ALGO_SANSDE,
             "DeEngine: bad algo");
@@ -23,22 +28,11 @@ DeEngine::DeEngine(const bbo_params &p) :
         BBO_REQUIRE(p.crref >= 1 && p.pupdate >= 1 && p.crupdate >= 1,
                 "SANSDE: crref, pupdate, crupdate must be >= 1");
     BBO_REQUIRE(p.np >= 4, "DE needs a population of at least 4");
-    BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
     if (p.algo == BBO_ALGO_SHADE) {
         BBO_REQUIRE(p.h >= 1, "SHADE: h must be >= 1");
         BBO_REQUIRE(p.npmin >= 4 && p.npmin <= p.np, "SHADE: need 4 <= npmin <= npinit");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(BBO_ERR_NO_DEVICE, "no HIP device visible: libbbopt_hip has no CPU path");
-    BBO_REQUIRE(p.device >= 0 && p.device < ndev, "device ordinal out of range");
-    BBO_HIP(hipSetDevice(p.device));
-    BBO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-}
-
-DeEngine::~DeEngine()
-{
-    if (stream_) (void) hipStreamDestroy(stream_);
+    return p;
 }
 
 void DeEngine::init(int n, const double *lower, const double *upper, const double *guess,
@@ -46,9 +40,8 @@ void DeEngine::init(int n, const double *lower, const double *upper, const doubl
 {
     (void) guess;   // JADE / SHADE never read it (jade.cpp:64-96, shade.cpp:56-94)
     BBO_REQUIRE(n >= 1 && n <= 2048, "DE: dimension must be in [1, 2048]");
-    for (int j = 0; j < n; j++)
-        BBO_REQUIRE(std::isfinite(lower[j]) && std::isfinite(upper[j]),
-                "DE draws its population from [lower, upper]: the bounds must be finite");
+    require_finite_box("DE draws its population from [lower, upper]: the bounds must be finite", n,
+            lower, upper);
     BBO_HIP(hipSetDevice(params_.device));
     obj_ = obj;
     const int P = params_.populations;
@@ -94,19 +87,8 @@ void DeEngine::init(int n, const double *lower, const double *upper, const doubl
     rec_flag_.alloc(rows);
     claim_.alloc(rows);
     slot_of_.alloc(rows);
-    lower_.alloc(ld);
-    upper_.alloc(ld);
-    aux_.alloc(ld);
     scal_.alloc(P);
-
-    std::vector<double> lo(ld, 0.), up(ld, 0.);
-    aux_h_.assign(ld, 0.);
-    std::copy(lower, lower + n, lo.begin());
-    std::copy(upper, upper + n, up.begin());
-    fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
-    lower_.upload(lo.data(), ld);
-    upper_.upload(up.data(), ld);
-    aux_.upload(aux_h_.data(), ld);
+    upload_box(n, c.ld, lower, upper, obj);
     std::vector<double> half((size_t) P * c.h, 0.5);
     MCR_.upload(half.data(), half.size());
     MF_.upload(half.data(), half.size());
@@ -189,8 +171,7 @@ void DeEngine::host_evaluate(int which, int rows)
         DevBuf<double> &F = buf == 0 ? fa_ : fb_;
         X.download(xh.data(), (size_t) cnt * c.ld, (size_t) p * c.npinit * c.ld);
         obj_.eval_host(xh.data(), cnt, c.n, c.ld, fh.data());
-        for (int r = 0; r < cnt; r++)
-            if (fh[r] != fh[r]) fh[r] = std::numeric_limits<double>::infinity();
+        nan_to_inf(fh.data(), cnt);
         F.upload(fh.data(), cnt, (size_t) p * c.npinit);
     }
 }
@@ -252,59 +233,9 @@ void DeEngine::generation(bool honor_stop)
     }
 }
 
-void DeEngine::iterate()
-{
-    if (!inited_) throw Error(BBO_ERR_STATE, "iterate() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    generation(false);
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
-}
-
-bool DeEngine::all_stopped()
-{
-    std::vector<DeScal> sc(c_.npop);
-    scal_.download(sc.data(), c_.npop);
-    for (const auto &s : sc)
-        if (!s.stop) return false;
-    return true;
-}
-
-int DeEngine::run(int max_generations)
-{
-    if (!inited_) throw Error(BBO_ERR_STATE, "run() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    {
-        // `while (_fev < _mfev)` (shade.cpp:247): no generation once the budget is spent
-        std::vector<DeScal> sc(c_.npop);
-        scal_.download(sc.data(), c_.npop);
-        bool touched = false;
-        for (auto &s : sc)
-            if (!s.stop && s.fev >= c_.mfev) {
-                s.stop = 2;
-                touched = true;
-            }
-        if (touched) scal_.upload(sc.data(), c_.npop);
-    }
-    const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
-    int done = 0;
-    while (done < max_generations) {
-        if (all_stopped()) break;
-        const int chunk = obj_.on_device() ? std::min(poll, max_generations - done) : 1;
-        for (int g = 0; g < chunk; g++) generation(true);
-        BBO_HIP(hipStreamSynchronize(stream_));
-        timer_.collect();
-        done += chunk;
-    }
-    return done;
-}
-
 void DeEngine::solution(int population, double *x_out, int *n_evals, int *converged)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "solution() before initialize()");
-    BBO_REQUIRE(population >= 0 && population < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("solution()", population);
     DeScal s;
     scal_.download(&s, 1, population);
     int best = 0;
@@ -316,38 +247,15 @@ void DeEngine::solution(int population, double *x_out, int *n_evals, int *conver
     *n_evals = s.fev;
     if (s.gen == 0) {
         // converged() before any generation: evaluate the radius spread of the initial swarm
-        std::vector<double> rad(s.np);
-        radius_.download(rad.data(), s.np, (size_t) population * c_.npinit);
-        double mean = 0.;
-        for (double r : rad) mean += r;
-        mean /= s.np;
-        double m2 = 0.;
-        for (double r : rad) m2 += (r - mean) * (r - mean);
-        *converged = m2 <= (s.np - 1) * c_.tol * c_.tol ? 1 : 0;
+        *converged = radius_spread_converged(radius_, (size_t) population * c_.npinit, s.np, c_.tol);
     } else {
         *converged = s.conv;
     }
 }
 
-void DeEngine::optimize(int n, const double *lower, const double *upper, const double *guess,
-        const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged)
-{
-    init(n, lower, upper, guess, obj);
-    // while (_fev < _mfev) { iterate(); if (converged()) break; }   shade.cpp:247-253
-    run(std::numeric_limits<int>::max());
-    int conv = 0;
-    solution(0, x_out, n_evals, &conv);
-    DeScal s;
-    scal_.download(&s, 1, 0);
-    *converged = s.stop == 1 ? 1 : 0;
-}
-
 int DeEngine::get(const std::string &k, int p, double *out, int cap)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "get() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("get()", p);
     const DeConst &c = c_;
     DeScal s;
     scal_.download(&s, 1, p);
@@ -356,7 +264,7 @@ int DeEngine::get(const std::string &k, int p, double *out, int cap)
         if (out && cap >= 1) out[0] = v;
         return 1;
     };
-    if (k == "profile") return timer_.report(out, cap);
+    if (k == "profile") return profile_report(out, cap);
     if (k == "x" || k == "f") {   // in sorted order, like the reference's _swarm
         const int cnt = k == "x" ? s.np * c.n : s.np;
         if (out && cap >= cnt) {
@@ -444,18 +352,12 @@ int DeEngine::get(const std::string &k, int p, double *out, int cap)
 
 int DeEngine::set(const std::string &k, int p, const double *in, int count)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "set() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("set()", p);
     const DeConst &c = c_;
     DeScal s;
     scal_.download(&s, 1, p);
     const size_t pbase = (size_t) p * c.npinit;
-    if (k == "profile") {
-        timer_.enable(in[0] != 0., K_COUNT, K_NAMES);
-        return 1;
-    }
+    if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
     if (k == "x") {   // rows in sorted order; follow with set("f") to re-rank
         BBO_REQUIRE(count % c.n == 0 && count / c.n <= c.npinit, "set x: bad element count");
         const int rows = count / c.n;

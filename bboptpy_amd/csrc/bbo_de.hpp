@@ -9,7 +9,7 @@
 // and restated on the CPU by oracle/bbo_oracle_pop.inc (De::iterate_sync).
 #pragma once
 
-#include "bbo_common.hpp"
+#include "bbo_engine.hpp"
 
 namespace bbo {
 
@@ -60,46 +60,33 @@ struct DeDev {
     DeScal *scal;
 };
 
-class DeEngine: public Optimizer {
+class DeEngine: public Engine<DeScal> {
 public:
     explicit DeEngine(const bbo_params &p);
-    ~DeEngine() override;
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
-    void iterate() override;
     void solution(int population, double *x_out, int *n_evals, int *converged) override;
-    void optimize(int n, const double *lower, const double *upper, const double *guess,
-            const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged) override;
-    int run(int max_generations) override;
     int get(const std::string &key, int population, double *out, int cap) override;
     int set(const std::string &key, int population, const double *in, int count) override;
     int dimension() const override { return c_.n; }
 
 private:
-    void generation(bool honor_stop);
+    static const bbo_params &checked(const bbo_params &p);
+    void generation(bool honor_stop) override;
     void launch_rank(int which_next, int np_bound);
     // threads of the one-workgroup-per-population kernels (bookkeeping, finish): one per
     // individual up to 1024 -- sums come out bit-identical whatever the choice as long as every
     // thread holds at most one individual, and small populations do not pay for 16 wavefronts
     int pop_threads() const { return c_.npinit <= 64 ? 64 : c_.npinit <= 256 ? 256 : 1024; }
     void host_evaluate(int which, int rows);
-    bool all_stopped();
 
-    bbo_params params_;
-    ObjectiveSpec obj_;
     DeConst c_ {};
     DeDev d_ {};
-    hipStream_t stream_ = nullptr;
-    bool inited_ = false;
     int np_host_ = 0;        // upper bound of the device np (exact while no population stopped)
     long fev_host_ = 0;
-    std::vector<double> aux_h_;
     DevBuf<double> cra_, crb_;
-    DevBuf<double> Xa_, Xb_, fa_, fb_, arch_, MCR_, MF_, rec_cr_, rec_f_, rec_df_, radius_,
-            lower_, upper_, aux_;
+    DevBuf<double> Xa_, Xb_, fa_, fb_, arch_, MCR_, MF_, rec_cr_, rec_f_, rec_df_, radius_;
     DevBuf<int> order_, rank_, rec_flag_, claim_, slot_of_;
-    DevBuf<DeScal> scal_;
-    KernelTimer timer_;
 };
 
 } // namespace bbo

@@ -1,0 +1,189 @@
+// bbo_engine.hpp -- the host lifecycle every engine shares: the device and stream of a handle, the
+// box and the objective's table in HBM, the guards of the entry points, and iterate() / run() /
+// optimize() as template methods over a handful of hooks.  An engine derives from Engine<its
+// per-population scalars>, writes init / generation / solution / get / set around its kernels and
+// overrides a hook only where its reference's loop differs (host side).
+#pragma once
+
+#include "bbo_common.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+namespace bbo {
+
+// a host objective's NaN ranks last (the device objectives do the same, bbo_objectives.hpp)
+inline void nan_to_inf(double *f, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (f[i] != f[i]) f[i] = std::numeric_limits<double>::infinity();
+}
+
+// converged() before any generation: the radius spread of the initial swarm, radius[off, off + np)
+inline int radius_spread_converged(const DevBuf<double> &radius, size_t off, int np, double tol)
+{
+    std::vector<double> rad(np);
+    radius.download(rad.data(), np, off);
+    double mean = 0.;
+    for (double r : rad) mean += r;
+    mean /= np;
+    double m2 = 0.;
+    for (double r : rad) m2 += (r - mean) * (r - mean);
+    return m2 <= (np - 1) * tol * tol ? 1 : 0;
+}
+
+// Scal: the engine's per-population scalars; the base reads its `stop` and `fev`.
+template<class Scal>
+class Engine: public Optimizer {
+public:
+    ~Engine() override
+    {
+        if (stream_) (void) hipStreamDestroy(stream_);
+    }
+
+    void iterate() override
+    {
+        enter("iterate()");
+        generation(false);
+        BBO_HIP(hipStreamSynchronize(stream_));
+        after_chunk(false);
+        timer_.collect();
+    }
+
+    int run(int max_generations) override
+    {
+        enter("run()");
+        {
+            // the references loop `while (_fev < _mfev)`: no generation once the budget is spent
+            std::vector<Scal> sc(params_.populations);
+            scal_.download(sc.data(), sc.size());
+            bool touched = false;
+            for (auto &s : sc)
+                if (!s.stop && budget_spent(s)) {
+                    s.stop = 2;
+                    touched = true;
+                }
+            if (touched) scal_.upload(sc.data(), sc.size());
+        }
+        const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
+        int done = 0;
+        while (done < max_generations) {
+            if (all_stopped()) break;
+            // (a host objective is polled every generation)
+            const int chunk = chunk_limit(obj_.on_device() ? std::min(poll, max_generations - done) : 1);
+            launch_chunk(chunk);
+            BBO_HIP(hipStreamSynchronize(stream_));
+            after_chunk(true);
+            timer_.collect();
+            done += chunk;
+        }
+        return done;
+    }
+
+    // init + loop until the algorithm's own stop rule or the evaluation budget
+    void optimize(int n, const double *lower, const double *upper, const double *guess,
+            const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged) override
+    {
+        init(n, lower, upper, guess, obj);
+        run(std::numeric_limits<int>::max());
+        int conv = 0;
+        solution(0, x_out, n_evals, &conv);
+        Scal s;
+        scal_.download(&s, 1, 0);
+        *converged = s.stop == 1 ? 1 : 0;
+    }
+
+protected:
+    // (an engine's own parameter checks run before this one: see the derived constructors)
+    explicit Engine(const bbo_params &p) :
+            params_(p)
+    {
+        BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+            throw Error(BBO_ERR_NO_DEVICE, "no HIP device visible: libbbopt_hip has no CPU path");
+        BBO_REQUIRE(p.device >= 0 && p.device < ndev, "device ordinal out of range");
+        BBO_HIP(hipSetDevice(p.device));
+        BBO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    }
+
+    // ---- the hooks ----------------------------------------------------------------------------
+    virtual void generation(bool honor_stop) = 0;
+    // run()'s pre-pass: this population must not take another generation
+    virtual bool budget_spent(const Scal &s) const { return s.fev >= params_.mfev; }
+    // every poll's download of the scalars, before their stop flags are tested
+    virtual void inspect(const std::vector<Scal>&) {}
+    virtual int chunk_limit(int want) { return want; }
+    virtual void launch_chunk(int gens)
+    {
+        for (int g = 0; g < gens; g++) generation(true);
+    }
+    // behind the synchronisation that ends iterate()'s generation (in_run false) or a chunk of run()
+    virtual void after_chunk(bool in_run) { (void) in_run; }
+
+    // ---- guards of the entry points -------------------------------------------------------------
+    void enter(const char *call)
+    {
+        if (!inited_) throw Error(BBO_ERR_STATE, std::string(call) + " before initialize()");
+        BBO_HIP(hipSetDevice(params_.device));
+    }
+    void enter_population(const char *call, int p)
+    {
+        enter(call);
+        BBO_REQUIRE(p >= 0 && p < params_.populations, "population index out of range");
+        BBO_HIP(hipStreamSynchronize(stream_));
+    }
+
+    void require_finite_box(const char *msg, int n, const double *lower, const double *upper) const
+    {
+        for (int j = 0; j < n; j++)
+            BBO_REQUIRE(std::isfinite(lower[j]) && std::isfinite(upper[j]), msg);
+    }
+
+    // the box and the objective's per-coordinate table, padded to ld, on the host and in HBM
+    void upload_box(int n, int ld, const double *lower, const double *upper, const ObjectiveSpec &obj)
+    {
+        lower_h_.assign(ld, 0.);
+        upper_h_.assign(ld, 0.);
+        aux_h_.assign(ld, 0.);
+        std::copy(lower, lower + n, lower_h_.begin());
+        std::copy(upper, upper + n, upper_h_.begin());
+        fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
+        lower_.alloc(ld);
+        upper_.alloc(ld);
+        aux_.alloc(ld);
+        lower_.upload(lower_h_.data(), ld);
+        upper_.upload(upper_h_.data(), ld);
+        aux_.upload(aux_h_.data(), ld);
+    }
+
+    bool all_stopped()
+    {
+        std::vector<Scal> sc(params_.populations);
+        scal_.download(sc.data(), sc.size());
+        inspect(sc);
+        for (const auto &s : sc)
+            if (!s.stop) return false;
+        return true;
+    }
+
+    // get("profile") / set("profile") with the engine's kernel slots
+    int profile_report(double *out, int cap) const { return timer_.report(out, cap); }
+    int profile_enable(const double *in, int nslots, const char *const *names)
+    {
+        timer_.enable(in[0] != 0., nslots, names);
+        return 1;
+    }
+
+    bbo_params params_;
+    ObjectiveSpec obj_;
+    hipStream_t stream_ = nullptr;
+    bool inited_ = false;
+    KernelTimer timer_;
+    std::vector<double> lower_h_, upper_h_, aux_h_;
+    DevBuf<double> lower_, upper_, aux_;
+    DevBuf<Scal> scal_;
+};
+
+} // namespace bbo

@@ -16,22 +16,16 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:pso_center", "bbo:pso_ese", "
 }
 
 PsoEngine::PsoEngine(const bbo_params &p) :
-        params_(p)
+        Engine(checked(p))
+{
+}
+
+// the algorithm's own parameter checks, ahead of the base's (populations, device)
+const bbo_params &PsoEngine::checked(const bbo_params &p)
 {
     BBO_REQUIRE(p.algo == BBO_ALGO_APSO, "PsoEngine: bad algo");
     BBO_REQUIRE(p.np >= 2, "APSO needs at least 2 particles");
-    BBO_REQUIRE(p.populations >= 1, "populations must be >= 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        throw Error(BBO_ERR_NO_DEVICE, "no HIP device visible: libbbopt_hip has no CPU path");
-    BBO_REQUIRE(p.device >= 0 && p.device < ndev, "device ordinal out of range");
-    BBO_HIP(hipSetDevice(p.device));
-    BBO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-}
-
-PsoEngine::~PsoEngine()
-{
-    if (stream_) (void) hipStreamDestroy(stream_);
+    return p;
 }
 
 void PsoEngine::init(int n, const double *lower, const double *upper, const double *guess,
@@ -39,9 +33,8 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
 {
     (void) guess;   // APSO never reads it (apso.cpp:48-103)
     BBO_REQUIRE(n >= 1 && n <= 2048, "APSO: dimension must be in [1, 2048]");
-    for (int j = 0; j < n; j++)
-        BBO_REQUIRE(std::isfinite(lower[j]) && std::isfinite(upper[j]),
-                "APSO draws its swarm from [lower, upper]: the bounds must be finite");
+    require_finite_box("APSO draws its swarm from [lower, upper]: the bounds must be finite", n,
+            lower, upper);
     BBO_HIP(hipSetDevice(params_.device));
     obj_ = obj;
     const int P = params_.populations;
@@ -84,18 +77,8 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
     colpart_.alloc((size_t) P * parts_ * ld);
     colpart2_.alloc((size_t) P * ((c.np + 127) / 128) * c.np);
     rowpart2_.alloc(rows);
-    lower_.alloc(ld);
-    upper_.alloc(ld);
-    aux_.alloc(ld);
     scal_.alloc(P);
-    std::vector<double> lo(ld, 0.), up(ld, 0.);
-    aux_h_.assign(ld, 0.);
-    std::copy(lower, lower + n, lo.begin());
-    std::copy(upper, upper + n, up.begin());
-    fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
-    lower_.upload(lo.data(), ld);
-    upper_.upload(up.data(), ld);
-    aux_.upload(aux_h_.data(), ld);
+    upload_box(n, c.ld, lower, upper, obj);
     std::vector<PsoScal> sc(P);
     for (auto &s : sc) {
         std::memset(&s, 0, sizeof(s));
@@ -146,8 +129,7 @@ void PsoEngine::host_evaluate_swarm(int i0, int i1)
         if (c.honor_stop && sc[p].stop) continue;
         X_.download(xh.data(), xh.size(), ((size_t) p * c.np + i0) * c.ld);
         obj_.eval_host(xh.data(), cnt, c.n, c.ld, fh.data());
-        for (auto &v : fh)
-            if (v != v) v = std::numeric_limits<double>::infinity();
+        nan_to_inf(fh.data(), cnt);
         f_.upload(fh.data(), cnt, (size_t) p * c.np + i0);
     }
 }
@@ -165,7 +147,8 @@ void PsoEngine::host_evaluate_elite()
         pvec_.download(pv.data(), c.ld, (size_t) p * c.ld);
         double f = 0.;
         obj_.eval_host(pv.data(), 1, c.n, c.ld, &f);
-        sc[p].nu = f != f ? std::numeric_limits<double>::infinity() : f;
+        nan_to_inf(&f, 1);
+        sc[p].nu = f;
         touched = true;
     }
     if (touched) scal_.upload(sc.data(), c.npop);
@@ -233,70 +216,25 @@ void PsoEngine::generation(bool honor_stop)
     BBO_HIP(hipGetLastError());
 }
 
-void PsoEngine::iterate()
+void PsoEngine::inspect(const std::vector<PsoScal> &sc)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "iterate() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    generation(false);
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
-    std::vector<PsoScal> sc(c_.npop);
-    scal_.download(sc.data(), c_.npop);
     for (const auto &s : sc)
         if (s.bad_rule)
             throw Error(BBO_ERR_ARG,
                     "Error [PSO]: Invalid rule base. Please report this issue on Github.");
 }
 
-bool PsoEngine::all_stopped()
+void PsoEngine::after_chunk(bool in_run)
 {
+    if (in_run) return;      // (run() sees the scalars at its next poll)
     std::vector<PsoScal> sc(c_.npop);
     scal_.download(sc.data(), c_.npop);
-    bool all = true;
-    for (const auto &s : sc) {
-        if (s.bad_rule)
-            throw Error(BBO_ERR_ARG,
-                    "Error [PSO]: Invalid rule base. Please report this issue on Github.");
-        if (!s.stop) all = false;
-    }
-    return all;
-}
-
-int PsoEngine::run(int max_generations)
-{
-    if (!inited_) throw Error(BBO_ERR_STATE, "run() before initialize()");
-    BBO_HIP(hipSetDevice(params_.device));
-    {
-        // `while (_it < _maxit && _fev < _mfev)`, apso.cpp:118
-        std::vector<PsoScal> sc(c_.npop);
-        scal_.download(sc.data(), c_.npop);
-        bool touched = false;
-        for (auto &s : sc)
-            if (!s.stop && (s.it >= s.maxit || s.fev >= c_.mfev)) {
-                s.stop = 2;
-                touched = true;
-            }
-        if (touched) scal_.upload(sc.data(), c_.npop);
-    }
-    const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
-    int done = 0;
-    while (done < max_generations) {
-        if (all_stopped()) break;
-        const int chunk = obj_.on_device() ? std::min(poll, max_generations - done) : 1;
-        for (int g = 0; g < chunk; g++) generation(true);
-        BBO_HIP(hipStreamSynchronize(stream_));
-        timer_.collect();
-        done += chunk;
-    }
-    return done;
+    inspect(sc);
 }
 
 void PsoEngine::solution(int population, double *x_out, int *n_evals, int *converged)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "solution() before initialize()");
-    BBO_REQUIRE(population >= 0 && population < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("solution()", population);
     PsoScal s;
     scal_.download(&s, 1, population);
     std::vector<double> x(c_.ld);
@@ -304,37 +242,15 @@ void PsoEngine::solution(int population, double *x_out, int *n_evals, int *conve
     std::copy(x.begin(), x.begin() + c_.n, x_out);
     *n_evals = s.fev;
     if (s.it == 0) {
-        std::vector<double> rad(c_.np);
-        radius_.download(rad.data(), c_.np, (size_t) population * c_.np);
-        double mean = 0.;
-        for (double r : rad) mean += r;
-        mean /= c_.np;
-        double m2 = 0.;
-        for (double r : rad) m2 += (r - mean) * (r - mean);
-        *converged = m2 <= (c_.np - 1) * c_.tol * c_.tol ? 1 : 0;
+        *converged = radius_spread_converged(radius_, (size_t) population * c_.np, c_.np, c_.tol);
     } else {
         *converged = s.conv;
     }
 }
 
-void PsoEngine::optimize(int n, const double *lower, const double *upper, const double *guess,
-        const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged)
-{
-    init(n, lower, upper, guess, obj);
-    run(std::numeric_limits<int>::max());
-    int conv = 0;
-    solution(0, x_out, n_evals, &conv);
-    PsoScal s;
-    scal_.download(&s, 1, 0);
-    *converged = s.stop == 1 ? 1 : 0;
-}
-
 int PsoEngine::get(const std::string &k, int p, double *out, int cap)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "get() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("get()", p);
     const PsoConst &c = c_;
     PsoScal s;
     scal_.download(&s, 1, p);
@@ -357,7 +273,7 @@ int PsoEngine::get(const std::string &k, int p, double *out, int cap)
         if (out && cap >= c.np) b.download(out, c.np, (size_t) p * c.np);
         return c.np;
     };
-    if (k == "profile") return timer_.report(out, cap);
+    if (k == "profile") return profile_report(out, cap);
     if (k == "x") return rowsof(X_);
     if (k == "v") return rowsof(V_);
     if (k == "xb") return rowsof(XB_);
@@ -388,19 +304,13 @@ int PsoEngine::get(const std::string &k, int p, double *out, int cap)
 
 int PsoEngine::set(const std::string &k, int p, const double *in, int count)
 {
-    if (!inited_) throw Error(BBO_ERR_STATE, "set() before initialize()");
-    BBO_REQUIRE(p >= 0 && p < c_.npop, "population index out of range");
-    BBO_HIP(hipSetDevice(params_.device));
-    BBO_HIP(hipStreamSynchronize(stream_));
+    enter_population("set()", p);
     const PsoConst &c = c_;
     if (k == "chunk") {        // 0 or >= np: the whole swarm sees the best of the generation start
         chunk_ = (int) in[0] <= 0 ? c.np : (int) in[0];
         return 1;
     }
-    if (k == "profile") {
-        timer_.enable(in[0] != 0., K_COUNT, K_NAMES);
-        return 1;
-    }
+    if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
     auto rows_in = [&](DevBuf<double> &b) {
         BBO_REQUIRE(count == c.np * c.n, "set: wrong element count");
         std::vector<double> tmp((size_t) c.np * c.ld, 0.);

@@ -11,7 +11,7 @@
 // oracle/bbo_oracle_pop.inc (Apso with sync = true).
 #pragma once
 
-#include "bbo_common.hpp"
+#include "bbo_engine.hpp"
 
 namespace bbo {
 
@@ -54,41 +54,32 @@ struct PsoDev {
     PsoScal *scal;
 };
 
-class PsoEngine: public Optimizer {
+class PsoEngine: public Engine<PsoScal> {
 public:
     explicit PsoEngine(const bbo_params &p);
-    ~PsoEngine() override;
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
-    void iterate() override;
     void solution(int population, double *x_out, int *n_evals, int *converged) override;
-    void optimize(int n, const double *lower, const double *upper, const double *guess,
-            const ObjectiveSpec &obj, double *x_out, int *n_evals, int *converged) override;
-    int run(int max_generations) override;
     int get(const std::string &key, int population, double *out, int cap) override;
     int set(const std::string &key, int population, const double *in, int count) override;
     int dimension() const override { return c_.n; }
 
 private:
-    void generation(bool honor_stop);
+    static const bbo_params &checked(const bbo_params &p);
+    void generation(bool honor_stop) override;
+    // `while (_it < _maxit && _fev < _mfev)`, apso.cpp:118
+    bool budget_spent(const PsoScal &s) const override { return s.it >= s.maxit || s.fev >= c_.mfev; }
+    void inspect(const std::vector<PsoScal> &sc) override;   // throws on a bad rule base
+    void after_chunk(bool in_run) override;                  // iterate() looks at the rule base too
     void host_evaluate_swarm(int i0 = 0, int i1 = -1);
     void host_evaluate_elite();
-    bool all_stopped();
 
-    bbo_params params_;
-    ObjectiveSpec obj_;
     PsoConst c_ {};
     PsoDev d_ {};
-    hipStream_t stream_ = nullptr;
-    bool inited_ = false;
     int parts_ = 1;
     int chunk_ = 0;           // particles between two refreshes of the swarm's best inside a generation
-    std::vector<double> aux_h_;
     DevBuf<double> colpart2_, rowpart2_, Xc_;
-    DevBuf<double> X_, V_, XB_, f_, fb_, xbest_, ws_, mean_, nrm_, pvec_, radius_, colpart_,
-            lower_, upper_, aux_;
-    DevBuf<PsoScal> scal_;
-    KernelTimer timer_;
+    DevBuf<double> X_, V_, XB_, f_, fb_, xbest_, ws_, mean_, nrm_, pvec_, radius_, colpart_;
 };
 
 } // namespace bbo
