@@ -6,11 +6,11 @@ Drop-in for the CMA-ES / DE / PSO classes of mike-gimelfarb/bboptpy
 of include/bbopt_hip.h.  See DESIGN.md.
 """
 from . import objectives
-from .objectives import vectorized
+from .objectives import vectorized, DeviceObjective
 from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, CMAES,
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
                            SANSDE, APSO, CSO, CCPSO)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
            "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "objectives",
-           "vectorized"]
+           "vectorized", "DeviceObjective"]

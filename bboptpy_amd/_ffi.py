@@ -15,7 +15,9 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES = range(12)
 # bbo_objective_kind
-OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB = 0, 1, 2
+OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
+# bbo_status (the ones Python tells apart)
+ERR_ARG = -1
 # bbo_cma_phase
 PHASE_SAMPLE_EVALUATE, PHASE_RANK, PHASE_UPDATE, PHASE_EIGEN, PHASE_HISTORY_STOP = range(5)
 
@@ -98,6 +100,9 @@ def lib():
     L.bbo_ccpso_table_record.argtypes = [C.c_void_p]
     L.bbo_ccpso_export_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.bbo_ccpso_merge_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.bbo_program_create.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int,
+                                     C.POINTER(C.c_void_p)]
+    L.bbo_program_destroy.argtypes = [C.c_void_p]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -106,7 +111,8 @@ def lib():
                  "bbo_solution", "bbo_solution_of", "bbo_optimize", "bbo_run", "bbo_get",
                  "bbo_set", "bbo_cma_phase_run", "bbo_cma_inject_normals", "bbo_cma_set_params",
                  "bbo_cma_set_seed", "bbo_cma_evaluate", "bbo_ccpso_set_shard", "bbo_ccpso_set_local", "bbo_ccpso_phase",
-                 "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables"):
+                 "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
+                 "bbo_program_create", "bbo_program_destroy"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -118,6 +124,7 @@ EXPORTED_SYMBOLS = (
     "bbo_set", "bbo_cma_phase_run", "bbo_cma_inject_normals", "bbo_cma_set_params",
     "bbo_cma_set_seed", "bbo_cma_evaluate", "bbo_ccpso_set_shard", "bbo_ccpso_set_local", "bbo_ccpso_phase",
     "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
+    "bbo_program_create", "bbo_program_destroy",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

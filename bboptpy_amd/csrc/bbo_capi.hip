@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <memory>
 #include <mutex>
+#include <set>
 
 namespace bbo {
 Optimizer* make_de_engine(const bbo_params &p);       // bbo_de.hip
@@ -15,6 +16,11 @@ Optimizer* make_cso_engine(const bbo_params &p);      // bbo_cso.hip
 Optimizer* make_ccpso_engine(const bbo_params &p);    // bbo_ccpso.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
+
+// the caller's share of a compiled objective program; handles initialised with it hold their own
+struct bbo_program_s {
+    std::shared_ptr<bbo::Program> prog;
+};
 
 struct bbo_handle_s {
     std::unique_ptr<bbo::Optimizer> opt;
@@ -26,6 +32,10 @@ namespace {
 
 std::string g_create_error;
 std::mutex g_create_mutex;
+
+// the live bbo_program objects: `user` of a PROGRAM objective is checked against them
+std::set<bbo_program> g_programs;
+std::mutex g_programs_mutex;
 
 template<class F>
 int guarded(bbo_handle h, F fn)
@@ -59,6 +69,12 @@ bbo::ObjectiveSpec to_spec(const bbo_objective *o)
         if (!s.scalar) throw bbo::Error(BBO_ERR_ARG, "scalar callback is NULL");
     } else if (s.kind == BBO_OBJECTIVE_BATCH_CALLBACK) {
         if (!s.batch) throw bbo::Error(BBO_ERR_ARG, "batch callback is NULL");
+    } else if (s.kind == BBO_OBJECTIVE_PROGRAM) {
+        std::lock_guard<std::mutex> lock(g_programs_mutex);
+        const auto it = g_programs.find(static_cast<bbo_program>(s.user));
+        if (it == g_programs.end())
+            throw bbo::Error(BBO_ERR_ARG, "objective kind PROGRAM: `user` is not a live bbo_program");
+        s.program = (*it)->prog;
     } else {
         throw bbo::Error(BBO_ERR_ARG, "unknown objective kind");
     }
@@ -224,6 +240,42 @@ int bbo_create_restart(const bbo_params *params, bbo_handle base, bbo_handle *ou
         g_create_error = e.what();
         return BBO_ERR_HIP;
     }
+}
+
+int bbo_program_create(const char *source, const char *arch, const double *data, int data_count,
+        bbo_program *out)
+{
+    std::lock_guard<std::mutex> lock(g_create_mutex);
+    if (!out) {
+        g_create_error = "bbo_program_create: NULL argument";
+        return BBO_ERR_ARG;
+    }
+    *out = nullptr;
+    try {
+        std::unique_ptr<bbo_program_s> p(new bbo_program_s());
+        p->prog = bbo::Program::compile(source, arch, data, data_count);
+        std::lock_guard<std::mutex> reg(g_programs_mutex);
+        g_programs.insert(p.get());
+        *out = p.release();
+        return BBO_OK;
+    } catch (const bbo::Error &e) {
+        g_create_error = e.what();
+        return e.status;
+    } catch (const std::exception &e) {
+        g_create_error = e.what();
+        return BBO_ERR_HIP;
+    }
+}
+
+int bbo_program_destroy(bbo_program p)
+{
+    if (!p) return BBO_OK;
+    {
+        std::lock_guard<std::mutex> reg(g_programs_mutex);
+        if (!g_programs.erase(p)) return BBO_ERR_ARG;
+    }
+    delete p;
+    return BBO_OK;
 }
 
 int bbo_destroy(bbo_handle h)

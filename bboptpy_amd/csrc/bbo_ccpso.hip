@@ -31,6 +31,7 @@ void CcpsoEngine::init(int n, const double *lower, const double *upper, const do
         const ObjectiveSpec &obj)
 {
     (void) guess;   // never read (ccpso.cpp:66-112)
+    reject_program(obj, "CCPSO");
     BBO_REQUIRE(n >= 1 && n <= 1024, "CCPSO: dimension must be in [1, 1024]");
     require_finite_box("CCPSO draws its swarm from [lower, upper]: the bounds must be finite", n,
             lower, upper);
@@ -54,7 +55,7 @@ void CcpsoEngine::init(int n, const double *lower, const double *upper, const do
     // (the reference reads an uninitialised member in this test, ccpso.cpp:60; the intended
     // reading is taken: adapt unless a probability in (0, 1) was given)
     c.adaptp = !(c.phat0 > 0. && c.phat0 < 1.) ? 1 : 0;
-    c.obj = obj.on_device() ? obj.builtin : OBJ_HOST;
+    c.obj = obj.fused() ? obj.builtin : OBJ_HOST;
     c.mfev = params_.mfev;
     c.npop = P;
     c.stol = params_.tol;
@@ -104,7 +105,7 @@ void CcpsoEngine::init(int n, const double *lower, const double *upper, const do
     hipLaunchKernelGGL(ccp_init, dim3((c.np + 15) / 16, P), dim3(256),
             (size_t) 16 * c.ld * sizeof(double), stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) {
+    if (obj_.needs_host()) {
         BBO_HIP(hipStreamSynchronize(stream_));
         std::vector<double> xh((size_t) c.np * c.ld), fh(c.np);
         for (int p = 0; p < P; p++) {
@@ -188,7 +189,7 @@ void CcpsoEngine::launch_regroup_eval()
     for (int k = 1; k < c.npps; k++) cpmin = std::min(cpmin, c.pps[k]);
     const int maxswarm = c.n / cpmin;
     timer_.begin(stream_, K_EVAL);
-    if (obj_.on_device()) {
+    if (obj_.fused()) {
         if (c.ld <= 256)
             hipLaunchKernelGGL(ccp_eval<16>, dim3((CCP_SPLIT * maxswarm + 15) / 16, P), dim3(256),
                     (size_t) 16 * c.ld * sizeof(double), stream_, d_, c_);
@@ -210,7 +211,7 @@ void CcpsoEngine::launch_rest()
     for (int k = 1; k < c.npps; k++) cpmin = std::min(cpmin, c.pps[k]);
     timer_.begin(stream_, K_UPDATE);
     hipLaunchKernelGGL(ccp_update, dim3(c.n / cpmin, P), dim3(64), 0, stream_, d_, c_);
-    if (!obj_.on_device()) host_eval_yhat();
+    if (obj_.needs_host()) host_eval_yhat();
     hipLaunchKernelGGL(ccp_yhat, dim3(P), dim3(256), (size_t) c.ld * sizeof(double), stream_, d_,
             c_);
     timer_.end(stream_);
@@ -258,7 +259,7 @@ void CcpsoEngine::phase(int which)
     // bbo_ccpso_export_tables, bbo_get -- is ordered behind it on the engine's stream and
     // synchronises itself (one host wait per exchange instead of two).  Phase 1 ends a generation
     // and waits, like bbo_iterate.
-    if (which == 0 && obj_.on_device() && !timer_.on()) return;
+    if (which == 0 && obj_.fused() && !timer_.on()) return;
     BBO_HIP(hipStreamSynchronize(stream_));
     timer_.collect();
 }
@@ -350,7 +351,7 @@ void CcpsoEngine::set_local(Optimizer *local, int localfreq)
 
 double CcpsoEngine::eval_full(const double *x)
 {
-    if (!obj_.on_device()) {
+    if (obj_.needs_host()) {
         double f = 0.;
         obj_.eval_host(x, 1, c_.n, c_.n, &f);
         nan_to_inf(&f, 1);

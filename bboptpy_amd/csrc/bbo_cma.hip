@@ -211,7 +211,7 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     // (16 < ld <= 128: the samplers there always hand down ||z||^2, so without a box nothing in
     // a generation reads C^-1/2 but cma_paths, which can work from B and D)
     c.lazy_isc = (dense && !c.bound && c.ld > 16 && c.ld <= 256) ? 1 : 0;
-    c.obj = obj.on_device() ? obj.builtin : OBJ_HOST;
+    c.obj = obj.fused() ? obj.builtin : OBJ_HOST;
     c.mfev = params_.mfev;
     c.mit = params_.mfev / lambda;
     c.npop = P;
@@ -411,6 +411,20 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     d.mw_fail_host = mw_fail_host_;
     d.mw_fault = mw_fault_from_env();
     mw_release();          // (the shape may have changed: reserved again at the first spread launch)
+
+    // an objective program: the plan is static (population p's candidates and fitness), a stopped
+    // population is skipped by its flag; the padding rows' +inf is written once, here
+    if (obj_.is_program()) {
+        prog_.bind(obj_.program, params_.device, n, P);
+        std::vector<ProgPlan> plan(P);
+        for (int p = 0; p < P; p++)
+            plan[p] = ProgPlan { X_.p + (size_t) p * c.lambda_pad * ld, f_.p + (size_t) p * c.lambda_pad, lambda,
+                    c.ld };
+        prog_.upload_plan(plan);
+        std::vector<double> finf((size_t) P * c.lambda_pad, std::numeric_limits<double>::infinity());
+        f_.upload(finf.data(), finf.size());
+    } else
+        prog_.unbind();
 
     // packed operands of the initial B, D, C^-1/2
     c.honor_stop = 0;
@@ -903,13 +917,20 @@ void CmaEngine::host_evaluate()
     f_.upload(fh.data(), rows);
 }
 
+// an objective program: X is evaluated where it lies, on the engine's stream, nothing is waited for
+void CmaEngine::program_evaluate()
+{
+    prog_.launch(stream_, c_.lambda, c_.honor_stop ? (const void*) &d_.scal->stop : nullptr, (int) sizeof(CmaScal),
+            &prog_timer_);
+}
+
 // n <= 16, lambda <= 64, on-device objective: whole generations in one launch
 // (cma_small_generations).  The per-kernel timers and the diagnostic bit 64 keep the nine-kernel
 // path, which computes the same bits.
 bool CmaEngine::small_fused_ok() const
 {
     const CmaConst &c = c_;
-    return c.variant < 2 && c.ld == 16 && c.n >= 2 && c.lambda_pad <= 64 && obj_.on_device()
+    return c.variant < 2 && c.ld == 16 && c.n >= 2 && c.lambda_pad <= 64 && obj_.fused()
             && c.npop <= SMALL_FUSED_MAXP && !timer_.on() && !(d_.dbg & (16 | 64));
 }
 
@@ -938,7 +959,8 @@ void CmaEngine::generation(bool honor_stop)
     }
     c_.honor_stop = honor_stop ? 1 : 0;
     launch_sample_eval();
-    if (!obj_.on_device()) host_evaluate();
+    if (obj_.needs_host()) host_evaluate();
+    else if (obj_.is_program()) program_evaluate();
     launch_rank();
     launch_update();
     launch_eigen();
@@ -954,7 +976,8 @@ void CmaEngine::phase(int which)
     switch (which) {
     case BBO_PHASE_SAMPLE_EVALUATE:
         launch_sample_eval();
-        if (!obj_.on_device()) host_evaluate();
+        if (obj_.needs_host()) host_evaluate();
+        else if (obj_.is_program()) program_evaluate();
         break;
     case BBO_PHASE_RANK: launch_rank(); break;
     case BBO_PHASE_UPDATE: launch_update(); break;
@@ -969,6 +992,7 @@ void CmaEngine::phase(int which)
         BBO_HIP(hipStreamSynchronize(stream_));
     }
     timer_.collect();
+    prog_timer_.collect();
 }
 
 void CmaEngine::inject_normals(const double *z, int count)
@@ -1067,10 +1091,14 @@ void CmaEngine::optimize(int n, const double *lower, const double *upper, const 
 
 double CmaEngine::evaluate_point(const double *x)
 {
-    if (!obj_.on_device()) {
+    if (obj_.needs_host()) {
         double f = 0.;
         obj_.eval_host(x, 1, c_.n, c_.n, &f);
         return f;
+    }
+    if (obj_.is_program()) {
+        BBO_HIP(hipSetDevice(params_.device));
+        return prog_.evaluate_point(stream_, x);
     }
     // restart drivers re-evaluate one point per restart (bipop_cmaes.cpp:86): host
     // arithmetic with the same definition and the same per-coordinate table
@@ -1178,6 +1206,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         return (int) cnt;
     }
     if (k == "profile") return profile_report(out, cap);
+    if (const int r = prog_get(k, out, cap); r >= 0) return r;
     if (k == "eig_work") {   // diagnostic: the eigensolver's global scratch of population p
         const size_t cnt = std::min((size_t) 4 * eig_slab(c.ld), eig_work_.count);
         if (out && (size_t) cap >= cnt) eig_work_.download(out, cnt, (size_t) p * 4 * eig_slab(c.ld));
@@ -1344,6 +1373,7 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
         return r;
     }
     if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
+    if (const int r = prog_set(k, in, count); r >= 0) return r;
     if (k == "dbg") {
         d_.dbg = (int) in[0];
         return 1;

@@ -138,6 +138,7 @@ private:
     void launch_eigen();
     void launch_history_stop();
     void host_evaluate();
+    void program_evaluate();
 
     CmaConst c_ {};
     CmaDev d_ {};

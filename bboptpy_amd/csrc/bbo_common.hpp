@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <mutex>
 #include <set>
@@ -192,6 +193,8 @@ inline void allow_lds(const void *fn, int bytes)
     done.insert({ dev, fn });
 }
 
+class Program;      // bbo_program.hpp
+
 // how the population's fitness is obtained
 struct ObjectiveSpec {
     int kind = BBO_OBJECTIVE_BUILTIN;
@@ -199,8 +202,14 @@ struct ObjectiveSpec {
     bbo_scalar_fn scalar = nullptr;
     bbo_batch_fn batch = nullptr;
     void *user = nullptr;
+    std::shared_ptr<Program> program;     // kind == BBO_OBJECTIVE_PROGRAM (shared with the caller's bbo_program)
 
-    bool on_device() const { return kind == BBO_OBJECTIVE_BUILTIN; }
+    // the three ways: a built-in is fused into the kernels that produce X; the callbacks need the host
+    // (X leaves HBM, one generation per poll); a program evaluates X where it lies, behind the same
+    // OBJ_HOST kernels the callbacks use
+    bool fused() const { return kind == BBO_OBJECTIVE_BUILTIN; }
+    bool is_program() const { return kind == BBO_OBJECTIVE_PROGRAM; }
+    bool needs_host() const { return !fused() && !is_program(); }
     // evaluates `rows` host-resident candidates through the callbacks
     void eval_host(const double *X, int rows, int n, int ld, double *f_out) const
     {

@@ -37,6 +37,7 @@ void CsoEngine::init(int n, const double *lower, const double *upper, const doub
         const ObjectiveSpec &obj)
 {
     (void) guess;   // CSO never reads it (cso.cpp:67-112)
+    reject_program(obj, "CSO");
     BBO_REQUIRE(n >= 1 && n <= 1024, "CSO: dimension must be in [1, 1024]");
     require_finite_box("CSO draws its swarm from [lower, upper]: the bounds must be finite", n,
             lower, upper);
@@ -52,7 +53,7 @@ void CsoEngine::init(int n, const double *lower, const double *upper, const doub
     c.ngroup = c.np / c.pc;
     c.ring = params_.ring ? 1 : 0;
     c.correct = params_.correct ? 1 : 0;
-    c.obj = obj.on_device() ? obj.builtin : OBJ_HOST;
+    c.obj = obj.fused() ? obj.builtin : OBJ_HOST;
     c.mfev = params_.mfev;
     c.npop = P;
     c.stol = params_.tol;
@@ -114,7 +115,7 @@ void CsoEngine::init(int n, const double *lower, const double *upper, const doub
     hipLaunchKernelGGL(cso_init, dim3((c.np + R - 1) / R, P), dim3(16 * R),
             (size_t) R * c.ld * sizeof(double), stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) host_evaluate(false);
+    if (obj_.needs_host()) host_evaluate(false);
     hipLaunchKernelGGL(cso_finish_part, dim3(c_.fparts, P), dim3(256), 0, stream_, d_, c_);
     hipLaunchKernelGGL(cso_finish, dim3(P), dim3(64), 0, stream_, d_, c_, 1);
     if (fuse_g_) {      // the sums cso_compete maintains from now on, of the initial swarm
@@ -206,7 +207,7 @@ void CsoEngine::generation(bool honor_stop)
     }
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) host_evaluate(true);
+    if (obj_.needs_host()) host_evaluate(true);
     timer_.begin(stream_, K_FINISH);
     hipLaunchKernelGGL(cso_finish_part, dim3(c_.fparts, P), dim3(256), 0, stream_, d_, c_);
     hipLaunchKernelGGL(cso_finish, dim3(P), dim3(64), 0, stream_, d_, c_, 0);

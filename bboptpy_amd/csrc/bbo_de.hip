@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <limits>
 
 namespace bbo {
@@ -58,7 +59,7 @@ void DeEngine::init(int n, const double *lower, const double *upper, const doubl
     c.h = c.variant == 0 ? params_.h : 1;
     c.archive = (params_.archive && c.variant != 2) ? 1 : 0;   // SaNSDE has no archive
     c.repaircr = params_.repaircr ? 1 : 0;
-    c.obj = obj.on_device() ? obj.builtin : OBJ_HOST;
+    c.obj = obj.fused() ? obj.builtin : OBJ_HOST;
     c.mfev = params_.mfev;
     c.npop = P;
     c.tol = params_.tol;
@@ -117,6 +118,9 @@ void DeEngine::init(int n, const double *lower, const double *upper, const doubl
     d.crow[0] = cra_.p; d.crow[1] = crb_.p;
     d.lower = lower_.p; d.upper = upper_.p; d.aux = aux_.p; d.scal = scal_.p;
 
+    if (obj_.is_program()) prog_.bind(obj_.program, params_.device, n, P);
+    else prog_.unbind();
+
     np_host_ = c.npinit;
     fev_host_ = c.npinit;
     c.honor_stop = 0;
@@ -127,7 +131,8 @@ void DeEngine::init(int n, const double *lower, const double *upper, const doubl
     hipLaunchKernelGGL(de_init, grid, dim3(16 * R), (size_t) R * c.ld * sizeof(double), stream_,
             d_, c_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) host_evaluate(0, c.npinit);
+    if (obj_.needs_host()) host_evaluate(0, c.npinit);
+    else if (obj_.is_program()) program_evaluate(0, c.npinit);
     launch_rank(0, c.npinit);
     BBO_HIP(hipStreamSynchronize(stream_));
 }
@@ -176,6 +181,17 @@ void DeEngine::host_evaluate(int which, int rows)
     }
 }
 
+// an objective program: the same rows, where they lie.  Which half holds them and how many are alive
+// are device-side scalars: a small kernel writes the plan from them, the host reads nothing back.
+void DeEngine::program_evaluate(int which, int rows)
+{
+    const DeConst &c = c_;
+    const ProgScalView sv { d_.scal, (int) sizeof(DeScal), (int) offsetof(DeScal, cur), (int) offsetof(DeScal, np),
+            (int) offsetof(DeScal, stop) };
+    prog_.fill_plan(stream_, sv, Xa_.p, Xb_.p, fa_.p, fb_.p, c.npinit, c.ld, which, rows, c.honor_stop);
+    prog_.launch(stream_, rows, nullptr, 0, &prog_timer_);
+}
+
 void DeEngine::generation(bool honor_stop)
 {
     DeConst &c = c_;
@@ -197,8 +213,9 @@ void DeEngine::generation(bool honor_stop)
     }
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) {
-        host_evaluate(-1, np_host_);
+    if (!obj_.fused()) {
+        if (obj_.is_program()) program_evaluate(-1, np_host_);
+        else host_evaluate(-1, np_host_);
         timer_.begin(stream_, K_SELECT);
         hipLaunchKernelGGL(de_select, g16, dim3(256), 0, stream_, d_, c_);
         timer_.end(stream_);
@@ -265,6 +282,7 @@ int DeEngine::get(const std::string &k, int p, double *out, int cap)
         return 1;
     };
     if (k == "profile") return profile_report(out, cap);
+    if (const int r = prog_get(k, out, cap); r >= 0) return r;
     if (k == "x" || k == "f") {   // in sorted order, like the reference's _swarm
         const int cnt = k == "x" ? s.np * c.n : s.np;
         if (out && cap >= cnt) {
@@ -358,6 +376,7 @@ int DeEngine::set(const std::string &k, int p, const double *in, int count)
     scal_.download(&s, 1, p);
     const size_t pbase = (size_t) p * c.npinit;
     if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
+    if (const int r = prog_set(k, in, count); r >= 0) return r;
     if (k == "x") {   // rows in sorted order; follow with set("f") to re-rank
         BBO_REQUIRE(count % c.n == 0 && count / c.n <= c.npinit, "set x: bad element count");
         const int rows = count / c.n;

@@ -79,6 +79,7 @@ private:
     // thread holds at most one individual, and small populations do not pay for 16 wavefronts
     int pop_threads() const { return c_.npinit <= 64 ? 64 : c_.npinit <= 256 ? 256 : 1024; }
     void host_evaluate(int which, int rows);
+    void program_evaluate(int which, int rows);
 
     DeConst c_ {};
     DeDev d_ {};

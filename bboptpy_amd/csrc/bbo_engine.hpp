@@ -6,6 +6,7 @@
 #pragma once
 
 #include "bbo_common.hpp"
+#include "bbo_program.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -49,6 +50,7 @@ public:
         BBO_HIP(hipStreamSynchronize(stream_));
         after_chunk(false);
         timer_.collect();
+        prog_timer_.collect();
     }
 
     int run(int max_generations) override
@@ -70,12 +72,13 @@ public:
         int done = 0;
         while (done < max_generations) {
             if (all_stopped()) break;
-            // (a host objective is polled every generation)
-            const int chunk = chunk_limit(obj_.on_device() ? std::min(poll, max_generations - done) : 1);
+            // (a host objective is polled every generation; a program like a built-in)
+            const int chunk = chunk_limit(obj_.needs_host() ? 1 : std::min(poll, max_generations - done));
             launch_chunk(chunk);
             BBO_HIP(hipStreamSynchronize(stream_));
             after_chunk(true);
             timer_.collect();
+            prog_timer_.collect();
             done += chunk;
         }
         return done;
@@ -135,6 +138,36 @@ protected:
         BBO_HIP(hipStreamSynchronize(stream_));
     }
 
+    // the engines that have no program path yet say which have
+    void reject_program(const ObjectiveSpec &obj, const char *who) const
+    {
+        if (obj.is_program())
+            throw Error(BBO_ERR_ARG, std::string(who) + ": objective programs are supported by the CMA-ES family "
+                    "(CMAES, ActiveCMAES, SepCMAES, CholeskyCMAES, IPOP / BIPOP over them) and the DE family "
+                    "(JADE, SHADE, SANSDE)");
+    }
+
+    // get / set of the keys every program-capable engine shares; < 0: not one of them
+    int prog_get(const std::string &k, double *out, int cap) const
+    {
+        double v;
+        if (k == "prog_stage") v = prog_.stage();
+        else if (k == "prog_staged") v = prog_.bound() && prog_.staged() ? 1. : 0.;
+        else if (k == "prog_stage_max_n") v = PROG_STAGE_MAX_N;
+        else if (k == "prog_profile") return prog_timer_.report(out, cap);
+        else return -1;
+        if (out && cap >= 1) out[0] = v;
+        return 1;
+    }
+    int prog_set(const std::string &k, const double *in, int count)
+    {
+        if (k != "prog_stage") return -1;
+        BBO_REQUIRE(count == 1 && (in[0] == -1. || in[0] == 0. || in[0] == 1.),
+                "prog_stage: -1 (automatic), 0 (direct) or 1 (staged)");
+        prog_.set_stage((int) in[0]);
+        return 1;
+    }
+
     void require_finite_box(const char *msg, int n, const double *lower, const double *upper) const
     {
         for (int j = 0; j < n; j++)
@@ -149,7 +182,7 @@ protected:
         aux_h_.assign(ld, 0.);
         std::copy(lower, lower + n, lower_h_.begin());
         std::copy(upper, upper + n, upper_h_.begin());
-        fill_objective_aux(obj.on_device() ? obj.builtin : -1, n, aux_h_.data());
+        fill_objective_aux(obj.fused() ? obj.builtin : -1, n, aux_h_.data());
         lower_.alloc(ld);
         upper_.alloc(ld);
         aux_.alloc(ld);
@@ -173,6 +206,8 @@ protected:
     int profile_enable(const double *in, int nslots, const char *const *names)
     {
         timer_.enable(in[0] != 0., nslots, names);
+        static const char *const prog_names[1] = { "bbo:prog_eval" };
+        prog_timer_.enable(in[0] != 0., 1, prog_names);     // (its own report: "prog_profile")
         return 1;
     }
 
@@ -181,6 +216,8 @@ protected:
     hipStream_t stream_ = nullptr;
     bool inited_ = false;
     KernelTimer timer_;
+    ProgEval prog_;             // the objective program's evaluation launches (obj_.is_program())
+    KernelTimer prog_timer_;    // their time, outside the engine's own slots
     std::vector<double> lower_h_, upper_h_, aux_h_;
     DevBuf<double> lower_, upper_, aux_;
     DevBuf<Scal> scal_;

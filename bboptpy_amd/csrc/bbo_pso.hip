@@ -32,6 +32,7 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
         const ObjectiveSpec &obj)
 {
     (void) guess;   // APSO never reads it (apso.cpp:48-103)
+    reject_program(obj, "APSO");
     BBO_REQUIRE(n >= 1 && n <= 2048, "APSO: dimension must be in [1, 2048]");
     require_finite_box("APSO draws its swarm from [lower, upper]: the bounds must be finite", n,
             lower, upper);
@@ -46,7 +47,7 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
     c.ldc = round_up(n, 16);
     c.npad = round_up(params_.np, 128);
     c.correct = params_.correct ? 1 : 0;
-    c.obj = obj.on_device() ? obj.builtin : OBJ_HOST;
+    c.obj = obj.fused() ? obj.builtin : OBJ_HOST;
     c.mfev = params_.mfev;
     c.npop = P;
     c.tol = params_.tol;
@@ -104,7 +105,7 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
     hipLaunchKernelGGL(pso_init, dim3((c.np + R - 1) / R, P), dim3(16 * R),
             (size_t) R * c.ld * sizeof(double), stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) {
+    if (obj_.needs_host()) {
         host_evaluate_swarm();
         hipLaunchKernelGGL(pso_copy_fb, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_,
                 c_);
@@ -182,7 +183,7 @@ void PsoEngine::generation(bool honor_stop)
     timer_.begin(stream_, K_CTRL);
     hipLaunchKernelGGL(pso_control_a, dim3(P), dim3(256), 0, stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (!obj_.on_device()) host_evaluate_elite();
+    if (obj_.needs_host()) host_evaluate_elite();
     hipLaunchKernelGGL(pso_control_b, dim3(P), dim3(256), 0, stream_, d_, c_);
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
@@ -198,7 +199,7 @@ void PsoEngine::generation(bool honor_stop)
         hipLaunchKernelGGL(pso_update, dim3((i1 - i0 + R - 1) / R, P), dim3(16 * R), ldsR, stream_, d_,
                 c_, i0, i1);
         timer_.end(stream_);
-        if (!obj_.on_device()) {
+        if (obj_.needs_host()) {
             host_evaluate_swarm(i0, i1);
             hipLaunchKernelGGL(pso_pbest, dim3((i1 - i0 + 15) / 16, P), dim3(256), 0, stream_, d_, c_, i0,
                     i1);

@@ -21,7 +21,7 @@ import sys
 import numpy as _np
 
 from . import _ffi
-from .objectives import Builtin
+from .objectives import Builtin, DeviceObjective
 
 
 class MultivariateSolution:
@@ -73,6 +73,11 @@ class _ObjectiveBinding:
         self.error = None
         self.struct = _ffi.Objective()
         self._keep = None
+        if isinstance(f, DeviceObjective):
+            self._keep = f       # the program lives as long as the optimizer holds this binding
+            self.struct.kind = _ffi.OBJ_PROGRAM
+            self.struct.user = f._handle
+            return
         if isinstance(f, Builtin):
             self.struct.kind = _ffi.OBJ_BUILTIN
             self.struct.builtin = f.builtin_id
@@ -116,10 +121,15 @@ class _ObjectiveBinding:
             self.struct.scalar = self._keep
 
 
+PROGRAM_FAMILIES = ("CMAES, ActiveCMAES, SepCMAES, CholeskyCMAES (and IPopCMAES / BiPopCMAES over them), "
+                    "JADE, SHADE, SANSDE")
+
+
 class MultivariateSearch:
     """MultivariateOptimizer (multivariate.h:132-146) as bound at multivariate_py.cpp:374-420"""
 
     _algo = None
+    _accepts_program = False     # DeviceObjective: the CMA-ES and DE families
 
     def __init__(self, *, seed=None, device=0, populations=1, poll_every=None):
         _ffi.lib()   # fail loudly at construction when the HIP library is missing
@@ -179,6 +189,9 @@ class MultivariateSearch:
         pops = self._params.populations
         if upper.size < n or guess.size < n * pops:
             raise ValueError("upper/guess are shorter than lower (n = %d)" % n)
+        if isinstance(f, DeviceObjective) and not self._accepts_program:
+            raise ValueError("%s does not take a DeviceObjective yet: objective programs are supported by %s"
+                             % (type(self).__name__, PROGRAM_FAMILIES))
         self._binding = _ObjectiveBinding(f, n)
         self._n = n
         return n, lower, _np.ascontiguousarray(upper[:n]), _np.ascontiguousarray(
@@ -243,6 +256,7 @@ class MultivariateSearch:
 
 class BaseCMAES(MultivariateSearch):
     """BaseCmaes, multivariate_py.cpp:99-101 (abstract in the reference)"""
+    _accepts_program = True
 
     def phase(self, which):
         self._check(_ffi.lib().bbo_cma_phase_run(self._handle, int(which)))
@@ -336,6 +350,8 @@ class CholeskyCMAES(BaseCMAES):
 
 
 class _RestartDriver(MultivariateSearch):
+    _accepts_program = True
+
     def __init__(self, base, **ext):
         if not isinstance(base, BaseCMAES):
             raise TypeError("base must be a CMA-ES optimizer (CMAES / ActiveCMAES / SepCMAES / "
@@ -407,6 +423,7 @@ class JADE(MultivariateSearch):
     """JADE(mfev, np, tol, archive=True, repaircr=True, pelite=0.05, cdamp=0.1, sigma=0.07)
     -- :159-164"""
     _algo = _ffi.ALGO_JADE
+    _accepts_program = True
 
     def __init__(self, mfev, np, tol, archive=True, repaircr=True, pelite=0.05, cdamp=0.1,
                  sigma=0.07, **ext):
@@ -420,6 +437,7 @@ class JADE(MultivariateSearch):
 class SHADE(MultivariateSearch):
     """SHADE(mfev, npinit, tol, archive=True, repaircr=True, h=100, npmin=4) -- :166-171"""
     _algo = _ffi.ALGO_SHADE
+    _accepts_program = True
 
     def __init__(self, mfev, npinit, tol, archive=True, repaircr=True, h=100, npmin=4, **ext):
         super().__init__(**ext)
@@ -433,6 +451,7 @@ class SANSDE(MultivariateSearch):
     """SANSDE(mfev, np, tol, repaircr=True, crref=5, pupdate=50, crupdate=25) -- :174-177
     (self-adaptive DE with neighbourhood search, Yang et al. 2008; sansde.cpp)"""
     _algo = _ffi.ALGO_SANSDE
+    _accepts_program = True
 
     def __init__(self, mfev, np, tol, repaircr=True, crref=5, pupdate=50, crupdate=25, **ext):
         super().__init__(**ext)

@@ -7,6 +7,8 @@ vector evaluates the same formula on the host -- a convenience for inspecting re
 optimizer code that uses it is CCPSO's optional local search (multivariate.py), whose objective
 (the built-in composed with per-swarm weights) is a host callable by construction.
 """
+import ctypes as _C
+
 import numpy as _np
 
 
@@ -51,3 +53,53 @@ def vectorized(f):
     rows values (one host call per generation instead of one per candidate)"""
     f._bbo_vectorized = True
     return f
+
+
+class DeviceObjective:
+    """The user's own objective on the device: HIP source that defines ONE function,
+
+        extern "C" __device__ double bbo_user_objective(const double *x, int n, const double *data)
+
+    compiled here, in the constructor, with the run-time compiler (hiprtc) for `arch` -- default: the
+    architecture of device 0; a given `arch` such as "gfx950" needs no GPU.  `data` is an optional
+    table of doubles handed to every call.  Accepted wherever an objective is, by the CMA-ES classes
+    (and IPopCMAES / BiPopCMAES over them), JADE, SHADE and SANSDE: whole populations are evaluated
+    on the optimizer's own stream, candidates and fitness never leave the GPU.  A source that does
+    not compile raises ValueError carrying the compiler's log (lines and columns are the source's
+    own, file name "objective.hip").  One object can serve any number of optimizers, on any GPU."""
+
+    def __init__(self, source, data=None, arch=None):
+        from . import _ffi
+        if not isinstance(source, (str, bytes)):
+            raise TypeError("DeviceObjective: source must be a string of HIP code")
+        self.source = source.decode() if isinstance(source, bytes) else source
+        self.arch = arch
+        self.data = None if data is None else _np.ascontiguousarray(
+            _np.asarray(data, dtype=_np.float64)).ravel()
+        self._handle = None
+        L = _ffi.lib()
+        h = _C.c_void_p()
+        cnt = 0 if self.data is None else self.data.size
+        st = L.bbo_program_create(self.source.encode(), None if arch is None else arch.encode(),
+                                  self.data.ctypes.data_as(_C.c_void_p) if cnt else None, cnt,
+                                  _C.byref(h))
+        if st < 0:
+            msg = L.bbo_last_error(None)
+            msg = msg.decode(errors="replace") if msg else ""
+            if st == _ffi.ERR_ARG:
+                raise ValueError("DeviceObjective: " + msg)
+            raise _ffi.BboError(st, msg)
+        self._handle = h
+
+    def __del__(self):
+        # (optimizers initialised with this program share its ownership inside the library)
+        try:
+            if getattr(self, "_handle", None) is not None:
+                from . import _ffi
+                _ffi.lib().bbo_program_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return "<device objective program (%s)>" % (self.arch or "device 0")

@@ -84,7 +84,8 @@ typedef int (*bbo_batch_fn)(const double *X, int rows, int n, int ld, double *f_
 typedef enum {
     BBO_OBJECTIVE_BUILTIN = 0,
     BBO_OBJECTIVE_SCALAR_CALLBACK = 1,
-    BBO_OBJECTIVE_BATCH_CALLBACK = 2
+    BBO_OBJECTIVE_BATCH_CALLBACK = 2,
+    BBO_OBJECTIVE_PROGRAM = 3   /* a bbo_program (below) in `user`: evaluated on the device     */
 } bbo_objective_kind;
 
 typedef struct {
@@ -92,8 +93,35 @@ typedef struct {
     int builtin;           /* bbo_objective_id when kind == BUILTIN               */
     bbo_scalar_fn scalar;
     bbo_batch_fn batch;
-    void *user;
+    void *user;            /* the callbacks' cookie; the bbo_program when kind == PROGRAM */
 } bbo_objective;
+
+/* ---- objective programs (extension): the caller's own objective on the device -----------------
+ * The caller hands over HIP source that defines ONE device function,
+ *     extern "C" __device__ double bbo_user_objective(const double *x, int n, const double *data);
+ * (x: the candidate, n coordinates, in global memory or in LDS -- a plain pointer serves both;
+ * data: the caller's table).  bbo_program_create compiles it at run time (hiprtc, opened with
+ * dlopen at the first call: the library loads and everything else works without it) with
+ * -O3 -ffp-contract=off, the rule of the library's own kernels: a function written in the operation
+ * order of a host function returns the same bits.  A handle initialised with
+ * { kind = BBO_OBJECTIVE_PROGRAM, user = program } evaluates whole populations with it on its own
+ * stream: candidates and fitness never leave device memory, bbo_run polls every `poll_every`
+ * generations as for a built-in.  A NaN result ranks last (+inf), as for the callbacks.
+ *   arch   NULL: the architecture string device 0 reports, unchanged; else e.g. "gfx950" -- then no
+ *          device is touched, the call works on a machine without a GPU.  xnack+ is refused.
+ *   data   data_count doubles, copied (data_count may be 0); uploaded to every device the program
+ *          is used on.  The code object is loaded once per device at the first bbo_init using it.
+ * Errors: BBO_ERR_ARG when the source does not compile, does not define bbo_user_objective, or
+ * hiprtc is absent; bbo_last_error(NULL) then carries the compiler's log with the caller's own
+ * lines and columns ("objective.hip:LINE:COL").  Supported by CMAES, ActiveCMAES, SepCMAES,
+ * CholeskyCMAES, IPOP / BIPOP over them, JADE, SHADE, SANSDE; APSO, CSO, CCPSO return BBO_ERR_ARG
+ * from bbo_init.  A handle shares ownership of the program from bbo_init on:
+ * bbo_program_destroy may be called while handles still use it.  The function must read only
+ * x[0, n) and its table, and must terminate. */
+typedef struct bbo_program_s *bbo_program;
+int bbo_program_create(const char *source, const char *arch, const double *data, int data_count,
+        bbo_program *out);
+int bbo_program_destroy(bbo_program p);
 
 /* Constructor arguments.  Field names and defaults are the reference's keyword
  * arguments (py/multivariate_py.cpp): zero-initialise, call bbo_params_default(),
