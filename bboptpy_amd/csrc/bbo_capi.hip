@@ -3,6 +3,7 @@
 // plus a message retrievable with bbo_last_error(), so no C++ exception crosses the ABI.
 #include "bbo_cma.hpp"
 #include "bbo_ccpso.hpp"
+#include "bbo_jaya.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -14,6 +15,7 @@ Optimizer* make_de_engine(const bbo_params &p);       // bbo_de.hip
 Optimizer* make_pso_engine(const bbo_params &p);      // bbo_pso.hip
 Optimizer* make_cso_engine(const bbo_params &p);      // bbo_cso.hip
 Optimizer* make_ccpso_engine(const bbo_params &p);    // bbo_ccpso.hip
+Optimizer* make_jaya_engine(const bbo_params &p);     // bbo_jaya.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -197,6 +199,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_CCPSO:
             h->opt.reset(bbo::make_ccpso_engine(*params));
+            break;
+        case BBO_ALGO_JAYA:
+            h->opt.reset(bbo::make_jaya_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -460,6 +465,29 @@ int bbo_ccpso_merge_tables(bbo_handle h, const double *gathered, int world, int 
     return guarded(h, [&] {
         if (!gathered) throw bbo::Error(BBO_ERR_ARG, "NULL source");
         as_ccpso(h)->merge_tables(gathered, world, device_memory != 0);
+    });
+}
+
+void bbo_jaya_params_default(bbo_jaya_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp:226-234
+    p->adapt = 1;
+    p->k0 = 2;
+    p->mutation = BBO_JAYA_LOGISTIC;
+    p->kcheb = 2;
+    p->scale = 0.01;
+    p->beta = 1.5;
+    p->temper = 10.;
+}
+
+int bbo_jaya_configure(bbo_handle h, const bbo_jaya_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_jaya_configure: NULL parameters");
+        auto *e = dynamic_cast<bbo::JayaEngine*>(h->opt.get());
+        if (!e) throw bbo::Error(BBO_ERR_ARG, "not a JAYA handle");
+        e->configure(*p);
     });
 }
 

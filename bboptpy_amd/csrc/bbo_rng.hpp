@@ -24,7 +24,11 @@ enum Stream : uint32_t {
     STREAM_PSO_R = 5,
     STREAM_PSO_CTRL = 6,
     STREAM_RESTART = 7,
-    STREAM_DE_ARCH = 8
+    STREAM_DE_ARCH = 8,
+    STREAM_JAYA_R = 9,
+    STREAM_JAYA_CTRL = 10,
+    STREAM_JAYA_PERM = 11,
+    STREAM_JAYA_LEVY = 12
 };
 
 struct u32x4 {

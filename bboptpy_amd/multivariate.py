@@ -15,6 +15,7 @@ supported through the host-callback path (X leaves HBM once per generation); the
 `bboptpy_amd.objectives` select the built-in on-device objectives instead.
 """
 import ctypes as C
+import enum
 import os
 import sys
 
@@ -662,6 +663,42 @@ class CCPSO(MultivariateSearch):
                 self.set_state("fyhat", [fwy])
                 self.set_state("improved", [1.])
         self.set_state("fev", [float(fev)])
+
+
+class JAYA(MultivariateSearch):
+    """JAYA(mfev, tol, np, npmin, adapt=True, k0=2, mutation=JAYA.JAYA_Mutation.logistic,
+    scale=0.01, beta=1.5, kcheb=2, temper=10.) -- :213-234 (self-adaptive multi-population Jaya
+    with Levy-flight and chaotic mutations, Rao 2016, Rao & Saroj 2017; jaya.cpp).  `guess` is
+    ignored, as in the reference; `kcheb` is stored and unused, as in the reference."""
+    _algo = _ffi.ALGO_JAYA
+
+    class JAYA_Mutation(enum.IntEnum):
+        """JayaSearch::jaya_mutation_method, bound with export_values (:214-219)"""
+        original = 0
+        levy = 1
+        tent_map = 2
+        logistic = 3
+
+    original, levy, tent_map, logistic = (JAYA_Mutation.original, JAYA_Mutation.levy,
+                                          JAYA_Mutation.tent_map, JAYA_Mutation.logistic)
+
+    def __init__(self, mfev, tol, np, npmin, adapt=True, k0=2, mutation=JAYA_Mutation.logistic,
+                 scale=0.01, beta=1.5, kcheb=2, temper=10., **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.np, p.npmin = int(mfev), float(tol), int(np), int(npmin)
+        j = self._jaya = _ffi.JayaParams()
+        j.adapt, j.k0, j.mutation = int(bool(adapt)), int(k0), int(self.JAYA_Mutation(mutation))
+        j.kcheb, j.scale, j.beta, j.temper = int(kcheb), float(scale), float(beta), float(temper)
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_jaya_configure(h, C.byref(self._jaya))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
 
 
 class APSO(MultivariateSearch):

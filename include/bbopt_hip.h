@@ -53,7 +53,8 @@ typedef enum {
     BBO_ALGO_SANSDE = 8,       /* SaNSDESearch src/multivariate/de/sansde.h:40        */
     BBO_ALGO_CSO = 9,          /* CSOSearch    src/multivariate/pso/cso.h:44          */
     BBO_ALGO_CCPSO = 10,       /* CCPSOSearch  src/multivariate/pso/ccpso.h:46        */
-    BBO_ALGO_CHOLESKY_CMAES = 11 /* CholeskyCmaes src/multivariate/cma/cholesky_cmaes.h:37 */
+    BBO_ALGO_CHOLESKY_CMAES = 11, /* CholeskyCmaes src/multivariate/cma/cholesky_cmaes.h:37 */
+    BBO_ALGO_JAYA = 12         /* JayaSearch   src/multivariate/jaya/jaya.h:50        */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -328,6 +329,23 @@ int bbo_ccpso_phase(bbo_handle h, int phase);
 int bbo_ccpso_table_record(bbo_handle h);
 int bbo_ccpso_export_tables(bbo_handle h, double *dst, int device_memory);
 int bbo_ccpso_merge_tables(bbo_handle h, const double *gathered, int world, int device_memory);
+
+/* ---- JAYA (BBO_ALGO_JAYA): JAYA(mfev,tol,np,npmin,adapt=True,k0=2,mutation=logistic,scale=0.01,
+ * beta=1.5,kcheb=2,temper=10.)  py/multivariate_py.cpp:213-234.  `mfev`, `tol`, `np` and `npmin`
+ * travel in bbo_params (whose layout stays as it is); the seven other constructor arguments travel
+ * here.  bbo_jaya_configure is legal between bbo_create and bbo_init; without it the defaults
+ * hold.  BBO_ERR_ARG: not a JAYA handle, k0 outside 1..nks (nks = the number of k >= 1 with
+ * np >= npmin k), beta outside (0, 2] or an unknown mutation; BBO_ERR_STATE after bbo_init.
+ * `kcheb` is stored and unused, as in the reference. */
+typedef enum {
+    BBO_JAYA_ORIGINAL = 0,
+    BBO_JAYA_LEVY = 1,
+    BBO_JAYA_TENT_MAP = 2,
+    BBO_JAYA_LOGISTIC = 3
+} bbo_jaya_mutation;
+typedef struct { int adapt, k0, mutation, kcheb; double scale, beta, temper; } bbo_jaya_params;
+void bbo_jaya_params_default(bbo_jaya_params *p);   /* 1, 2, 3 (logistic), 2, 0.01, 1.5, 10. */
+int bbo_jaya_configure(bbo_handle h, const bbo_jaya_params *p);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
