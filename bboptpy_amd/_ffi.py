@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
-    ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA = range(13)
+    ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA = range(14)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -53,6 +53,11 @@ class JayaParams(C.Structure):
     """bbo_jaya_params: JAYA's constructor arguments that bbo_params has no field for"""
     _fields_ = [("adapt", C.c_int), ("k0", C.c_int), ("mutation", C.c_int), ("kcheb", C.c_int),
                 ("scale", C.c_double), ("beta", C.c_double), ("temper", C.c_double)]
+
+
+class DsaParams(C.Structure):
+    """bbo_dsa_params: DSA's constructor arguments that bbo_params has no field for"""
+    _fields_ = [("adapt", C.c_int), ("nbatch", C.c_int)]
 
 
 class Objective(C.Structure):
@@ -112,6 +117,9 @@ def lib():
     L.bbo_jaya_params_default.argtypes = [C.POINTER(JayaParams)]
     L.bbo_jaya_params_default.restype = None
     L.bbo_jaya_configure.argtypes = [C.c_void_p, C.POINTER(JayaParams)]
+    L.bbo_dsa_params_default.argtypes = [C.POINTER(DsaParams)]
+    L.bbo_dsa_params_default.restype = None
+    L.bbo_dsa_configure.argtypes = [C.c_void_p, C.POINTER(DsaParams)]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -121,7 +129,8 @@ def lib():
                  "bbo_set", "bbo_cma_phase_run", "bbo_cma_inject_normals", "bbo_cma_set_params",
                  "bbo_cma_set_seed", "bbo_cma_evaluate", "bbo_ccpso_set_shard", "bbo_ccpso_set_local", "bbo_ccpso_phase",
                  "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
-                 "bbo_program_create", "bbo_program_destroy", "bbo_jaya_configure"):
+                 "bbo_program_create", "bbo_program_destroy", "bbo_jaya_configure",
+                 "bbo_dsa_configure"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -135,6 +144,7 @@ EXPORTED_SYMBOLS = (
     "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
     "bbo_program_create", "bbo_program_destroy",
     "bbo_jaya_params_default", "bbo_jaya_configure",
+    "bbo_dsa_params_default", "bbo_dsa_configure",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

@@ -4,6 +4,7 @@
 #include "bbo_cma.hpp"
 #include "bbo_ccpso.hpp"
 #include "bbo_jaya.hpp"
+#include "bbo_dsa.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -16,6 +17,7 @@ Optimizer* make_pso_engine(const bbo_params &p);      // bbo_pso.hip
 Optimizer* make_cso_engine(const bbo_params &p);      // bbo_cso.hip
 Optimizer* make_ccpso_engine(const bbo_params &p);    // bbo_ccpso.hip
 Optimizer* make_jaya_engine(const bbo_params &p);     // bbo_jaya.hip
+Optimizer* make_dsa_engine(const bbo_params &p);      // bbo_dsa.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -85,15 +87,21 @@ bbo::ObjectiveSpec to_spec(const bbo_objective *o)
 
 // bbo_params as a caller built against an earlier header knows it ends where `stol` begins.  Such a
 // caller can only name the algorithms of its header, so the fields appended for CholeskyCMAES are
-// read and written for BBO_ALGO_CHOLESKY_CMAES alone: nothing here touches memory past the struct
-// the caller allocated.
+// read and written for BBO_ALGO_CHOLESKY_CMAES and BBO_ALGO_DSA (whose `stol` travels there: a
+// caller that can name algorithm 13 has the long struct) alone: nothing here touches memory past
+// the struct the caller allocated.
 constexpr size_t PARAMS_BASE_BYTES = offsetof(bbo_params, stol);
+
+inline bool has_long_params(int algo)
+{
+    return algo == BBO_ALGO_CHOLESKY_CMAES || algo == BBO_ALGO_DSA;
+}
 
 bbo_params own_copy(const bbo_params *params)
 {
     bbo_params p;
     std::memset(&p, 0, sizeof(p));
-    std::memcpy(&p, params, params->algo == BBO_ALGO_CHOLESKY_CMAES ? sizeof(p) : PARAMS_BASE_BYTES);
+    std::memcpy(&p, params, has_long_params(params->algo) ? sizeof(p) : PARAMS_BASE_BYTES);
     return p;
 }
 
@@ -126,7 +134,7 @@ extern "C" {
 void bbo_params_default(bbo_params *p, int algo)
 {
     if (!p) return;
-    std::memset(p, 0, algo == BBO_ALGO_CHOLESKY_CMAES ? sizeof(*p) : PARAMS_BASE_BYTES);
+    std::memset(p, 0, has_long_params(algo) ? sizeof(*p) : PARAMS_BASE_BYTES);
     p->algo = algo;
     // defaults of py/multivariate_py.cpp:103-171,265-269
     p->sigma0 = 2.;
@@ -160,7 +168,7 @@ void bbo_params_default(bbo_params *p, int algo)
     p->vmax = 0.2;
     p->npps = 0;
     p->pcauchy = -1.;
-    if (algo == BBO_ALGO_CHOLESKY_CMAES) {     // (see PARAMS_BASE_BYTES)
+    if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
     }
@@ -202,6 +210,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_JAYA:
             h->opt.reset(bbo::make_jaya_engine(*params));
+            break;
+        case BBO_ALGO_DSA:
+            h->opt.reset(bbo::make_dsa_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -487,6 +498,24 @@ int bbo_jaya_configure(bbo_handle h, const bbo_jaya_params *p)
         if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_jaya_configure: NULL parameters");
         auto *e = dynamic_cast<bbo::JayaEngine*>(h->opt.get());
         if (!e) throw bbo::Error(BBO_ERR_ARG, "not a JAYA handle");
+        e->configure(*p);
+    });
+}
+
+void bbo_dsa_params_default(bbo_dsa_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp:189-191
+    p->adapt = 1;
+    p->nbatch = 100;
+}
+
+int bbo_dsa_configure(bbo_handle h, const bbo_dsa_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_dsa_configure: NULL parameters");
+        auto *e = dynamic_cast<bbo::DsaEngine*>(h->opt.get());
+        if (!e) throw bbo::Error(BBO_ERR_ARG, "not a DSA handle");
         e->configure(*p);
     });
 }

@@ -28,7 +28,12 @@ enum Stream : uint32_t {
     STREAM_JAYA_R = 9,
     STREAM_JAYA_CTRL = 10,
     STREAM_JAYA_PERM = 11,
-    STREAM_JAYA_LEVY = 12
+    STREAM_JAYA_LEVY = 12,
+    STREAM_DSA_CTRL = 13,
+    STREAM_DSA_PERM = 14,
+    STREAM_DSA_DIR = 15,
+    STREAM_DSA_MAP = 16,
+    STREAM_DSA_R = 17
 };
 
 struct u32x4 {

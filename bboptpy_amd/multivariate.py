@@ -701,6 +701,29 @@ class JAYA(MultivariateSearch):
         return h
 
 
+class DSA(MultivariateSearch):
+    """DSA(mfev, tol, stol, np, adapt=True, nbatch=100) -- :189-191 (Differential Search,
+    Civicioglu 2012, with the reference's Rexp3 bandit over the four direction methods; ds.cpp).
+    `guess` is ignored, as in the reference."""
+    _algo = _ffi.ALGO_DSA
+
+    def __init__(self, mfev, tol, stol, np, adapt=True, nbatch=100, **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.stol, p.np = int(mfev), float(tol), float(stol), int(np)
+        d = self._dsa = _ffi.DsaParams()
+        d.adapt, d.nbatch = int(bool(adapt)), int(nbatch)
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_dsa_configure(h, C.byref(self._dsa))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

@@ -54,7 +54,8 @@ typedef enum {
     BBO_ALGO_CSO = 9,          /* CSOSearch    src/multivariate/pso/cso.h:44          */
     BBO_ALGO_CCPSO = 10,       /* CCPSOSearch  src/multivariate/pso/ccpso.h:46        */
     BBO_ALGO_CHOLESKY_CMAES = 11, /* CholeskyCmaes src/multivariate/cma/cholesky_cmaes.h:37 */
-    BBO_ALGO_JAYA = 12         /* JayaSearch   src/multivariate/jaya/jaya.h:50        */
+    BBO_ALGO_JAYA = 12,        /* JayaSearch   src/multivariate/jaya/jaya.h:50        */
+    BBO_ALGO_DSA = 13          /* DSSearch     src/multivariate/pso/ds.h:33           */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -186,11 +187,14 @@ typedef struct {
     int pps[16];           /* the candidate swarm sizes (each must divide n)       */
     double pcauchy;        /* fixed Cauchy rate in (0,1), else adaptive            */
     /* ---- appended for CholeskyCMAES: keeps the layout of everything above.  The library reads
-     * and writes these two fields only when algo == BBO_ALGO_CHOLESKY_CMAES, so a caller compiled
-     * against an earlier header (a shorter struct, none of whose algorithms is this one) stays
+     * and writes these two fields only when algo == BBO_ALGO_CHOLESKY_CMAES or BBO_ALGO_DSA (a
+     * caller that can name algorithm 13 was compiled against this struct), so a caller compiled
+     * against an earlier header (a shorter struct, none of whose algorithms is one of these) stays
      * binary compatible: bbo_params_default and bbo_create* never touch memory past its struct.
-     * CholeskyCMAES(mfev,tol,stol,np,sigma0=2,bound=False)              :118-120 */
-    double stol;           /* tolerance on the spread of the candidates' radii (its stop rule) */
+     * CholeskyCMAES(mfev,tol,stol,np,sigma0=2,bound=False)              :118-120
+     * DSA(mfev,tol,stol,np,adapt=True,nbatch=100)                       :189-191
+     * (`adapt` and `nbatch`: bbo_dsa_params below) */
+    double stol;           /* tolerance on the spread of the candidates' (DSA: the members') radii */
     int ranked;            /* (extension, default 0) rank-mu term of the factor update:
                               0 = the reference's (cholesky_cmaes.cpp:91-94): the FIRST mu
                                   candidates in sampling order, centred on the NEW mean;
@@ -346,6 +350,16 @@ typedef enum {
 typedef struct { int adapt, k0, mutation, kcheb; double scale, beta, temper; } bbo_jaya_params;
 void bbo_jaya_params_default(bbo_jaya_params *p);   /* 1, 2, 3 (logistic), 2, 0.01, 1.5, 10. */
 int bbo_jaya_configure(bbo_handle h, const bbo_jaya_params *p);
+
+/* ---- DSA (BBO_ALGO_DSA): DSA(mfev,tol,stol,np,adapt=True,nbatch=100)  py/multivariate_py.cpp:189-191,
+ * Differential Search with a Rexp3 bandit over its four direction methods (ds.cpp).  `mfev`, `tol`,
+ * `stol` and `np` travel in bbo_params (np >= 1, a finite box, `guess` is ignored); `adapt` and
+ * `nbatch` travel here.  bbo_dsa_configure is legal between bbo_create and bbo_init; without it the
+ * defaults hold.  BBO_ERR_ARG: not a DSA handle or nbatch < 1; BBO_ERR_STATE after bbo_init.
+ * Objective programs are refused by bbo_init (BBO_ERR_ARG); DSA is no base of a restart driver. */
+typedef struct { int adapt, nbatch; } bbo_dsa_params;
+void bbo_dsa_params_default(bbo_dsa_params *p);     /* 1, 100 */
+int bbo_dsa_configure(bbo_handle h, const bbo_dsa_params *p);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
