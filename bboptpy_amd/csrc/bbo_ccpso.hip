@@ -501,15 +501,9 @@ void CcpsoEngine::solution(int population, double *x_out, int *n_evals, int *con
     enter_population("solution()", population);
     CcpScal s;
     scal_.download(&s, 1, population);
-    std::vector<double> x(c_.ld);
-    yhat_.download(x.data(), c_.ld, (size_t) population * c_.ld);
-    std::copy(x.begin(), x.begin() + c_.n, x_out);
-    *n_evals = s.fev;
-    if (s.gen == 0) {
+    report_solution(s, yhat_, (size_t) population * c_.ld, c_.n, c_.ld, x_out, n_evals, converged);
+    if (s.gen == 0)
         *converged = radius_spread_converged(radius_, (size_t) population * c_.np, c_.np, c_.stol);
-    } else {
-        *converged = s.conv;
-    }
 }
 
 void CcpsoEngine::optimize(int n, const double *lower, const double *upper, const double *guess,
@@ -525,59 +519,27 @@ int CcpsoEngine::get(const std::string &k, int p, double *out, int cap)
     const CcpConst &c = c_;
     CcpScal s;
     scal_.download(&s, 1, p);
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
+    const StateOut o { out, cap };
     if (k == "profile") return profile_report(out, cap);
-    if (k == "x" || k == "y") {
-        const int cnt = c.np * c.n;
-        if (out && cap >= cnt) {
-            std::vector<double> M((size_t) c.np * c.ld);
-            (k == "x" ? X_ : Y_).download(M.data(), M.size(), (size_t) p * c.np * c.ld);
-            for (int i = 0; i < c.np; i++)
-                std::copy(M.begin() + (size_t) i * c.ld, M.begin() + (size_t) i * c.ld + c.n,
-                        out + (size_t) i * c.n);
-        }
-        return cnt;
-    }
-    if (k == "yhat") {
-        if (out && cap >= c.n) {
-            std::vector<double> v(c.ld);
-            yhat_.download(v.data(), c.ld, (size_t) p * c.ld);
-            std::copy(v.begin(), v.begin() + c.n, out);
-        }
-        return c.n;
-    }
-    if (k == "fx" || k == "fy") {
-        const int cnt = s.nswarm * c.np;
-        if (out && cap >= cnt && cnt > 0)
-            (k == "fx" ? fX_ : fY_).download(out, cnt, (size_t) p * c.n * c.np);
-        return cnt;
-    }
-    if (k == "ibest" || k == "strat" || k == "k") {
-        const int cnt = k == "k" ? c.n : s.nswarm * c.np;
-        if (out && cap >= cnt && cnt > 0) {
-            std::vector<int> v(cnt);
-            if (k == "k") range_.download(v.data(), cnt, (size_t) p * c.n);
-            else (k == "ibest" ? ibest_ : strat_).download(v.data(), cnt, (size_t) p * c.n * c.np);
-            for (int q = 0; q < cnt; q++) out[q] = v[q];
-        }
-        return cnt;
-    }
-    if (k == "fyhat") return one(s.fyhat);
-    if (k == "phat") return one(s.phat);
-    if (k == "fev") return one(s.fev);
-    if (k == "it") return one(s.gen);
-    if (k == "is") return one(s.is);
-    if (k == "nswarm") return one(s.nswarm);
-    if (k == "cpswarm") return one(s.cpswarm);
-    if (k == "improved") return one(s.improved);
-    if (k == "np") return one(c.np);
-    if (k == "stop") return one(s.stop);
-    if (k == "conv") return one(s.conv);
-    if (k == "m2") return one(s.m2);
-    if (k == "n") return one(c.n);
+    if (k == "x" || k == "y") return o.rows(k == "x" ? X_ : Y_, (size_t) p * c.np, c.np, c.n, c.ld);
+    if (k == "yhat") return o.vec(yhat_, (size_t) p * c.ld, c.n);
+    if (k == "fx" || k == "fy") return o.vec(k == "fx" ? fX_ : fY_, (size_t) p * c.n * c.np, s.nswarm * c.np);
+    if (k == "ibest" || k == "strat")
+        return o.ints(k == "ibest" ? ibest_ : strat_, (size_t) p * c.n * c.np, s.nswarm * c.np);
+    if (k == "k") return o.ints(range_, (size_t) p * c.n, c.n);
+    if (k == "fyhat") return o.one(s.fyhat);
+    if (k == "phat") return o.one(s.phat);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "it") return o.one(s.gen);
+    if (k == "is") return o.one(s.is);
+    if (k == "nswarm") return o.one(s.nswarm);
+    if (k == "cpswarm") return o.one(s.cpswarm);
+    if (k == "improved") return o.one(s.improved);
+    if (k == "np") return o.one(c.np);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "conv") return o.one(s.conv);
+    if (k == "m2") return o.one(s.m2);
+    if (k == "n") return o.one(c.n);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 

@@ -24,19 +24,6 @@ namespace bbo {
 #define CCP_INF (__builtin_huge_val())
 constexpr double CCP_PI = 3.14159265358979323846;
 
-__device__ inline bool ccp_frozen(const CcpConst &c, const CcpScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
-template<int G>
-__device__ inline double ccp_group_sum(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
-
 // grid (ceil(np/16), P), 256 threads, LDS 16 * ld doubles (n <= 1024) -- init only
 __global__ __launch_bounds__(256) void ccp_init(CcpDev d, CcpConst c)
 {
@@ -62,7 +49,7 @@ __global__ __launch_bounds__(256) void ccp_init(CcpDev d, CcpConst c)
         }
     }
     __syncthreads();
-    ssq = ccp_group_sum<16>(ssq);
+    ssq = group_sum<16>(ssq);
     double f = CCP_INF;
     if (c.obj >= 0) {
         f = eval_row_group<16>(c.obj, c.n, row, d.aux, g);
@@ -102,7 +89,7 @@ __global__ __launch_bounds__(256) void ccp_regroup(CcpDev d, CcpConst c)
 {
     const int p = blockIdx.x;
     CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ int s_changed, s_cp;
     const int tid = threadIdx.x, gen = sc->gen;
     const uint32_t sw = stream_word(STREAM_PSO_CTRL, (uint32_t) p);
@@ -138,13 +125,6 @@ __global__ __launch_bounds__(256) void ccp_regroup(CcpDev d, CcpConst c)
     for (int j = tid; j < c.ld; j += 256) d.ysave[(size_t) p * c.ld + j] = d.yhat[(size_t) p * c.ld + j];
 }
 
-// orders a wavefront's LDS accesses among its own lanes
-__device__ inline void ccp_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // candidate (j, i, which): yhat with the coordinates of swarm j taken from X_i (which = 0) or
 // Y_i (1) -- ccpso.cpp:241-260, 2 np nswarm context evaluations per generation.  CCP_SPLIT TEAMS
 // of G lanes per SWARM j: a team stages yhat in its LDS row once and then walks its share of the
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(256) void ccp_eval(CcpDev d, CcpConst c)
 {
     const int p = blockIdx.y;
     const CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     constexpr int R = 256 / G;
     constexpr int MAXQ = 256 / G;                // coordinates of the swarm held in registers: 256
@@ -196,7 +176,7 @@ __global__ __launch_bounds__(256) void ccp_eval(CcpDev d, CcpConst c)
         for (int u = 0; u < MAXQ; u++) val[u] = coord[u] >= 0 ? src[coord[u]] : 0.;
     }
     for (int t = part; t < 2 * np; t += CCP_SPLIT) {
-        ccp_wave_sync();                         // the previous evaluation has read the row
+        wave_sync();                             // the previous evaluation has read the row
 #pragma unroll
         for (int u = 0; u < MAXQ; u++)
             if (coord[u] >= 0) row[coord[u]] = val[u];
@@ -212,7 +192,7 @@ __global__ __launch_bounds__(256) void ccp_eval(CcpDev d, CcpConst c)
 #pragma unroll
             for (int u = 0; u < MAXQ; u++) val[u] = coord[u] >= 0 ? src[coord[u]] : 0.;
         }
-        ccp_wave_sync();
+        wave_sync();
         if (c.obj >= 0) {
             double f = eval_row_group<G, false, 4>(c.obj, c.n, row, d.aux, g);
             if (f != f) f = CCP_INF;
@@ -268,7 +248,7 @@ __global__ __launch_bounds__(64) void ccp_update(CcpDev d, CcpConst c)
 {
     const int p = blockIdx.y, j = blockIdx.x;
     CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     if (j >= sc->nswarm) return;
     const int tid = threadIdx.x, np = c.np, ld = c.ld, cp = sc->cpswarm;
     const size_t fb = (size_t) p * c.n * np + (size_t) j * np;
@@ -314,7 +294,7 @@ __global__ __launch_bounds__(256) void ccp_yhat(CcpDev d, CcpConst c)
 {
     const int p = blockIdx.x;
     CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     __shared__ double red[4][4];
     const int tid = threadIdx.x, ld = c.ld, np = c.np;
@@ -382,7 +362,7 @@ __global__ __launch_bounds__(256) void ccp_strategy(CcpDev d, CcpConst c)
 {
     const int p = blockIdx.y;
     const CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int q = blockIdx.x * 256 + threadIdx.x, np = c.np;
     if (q >= sc->nswarm * np) return;
     const int j = q / np, i = q - j * np;
@@ -400,7 +380,7 @@ __global__ __launch_bounds__(256) void ccp_position(CcpDev d, CcpConst c)
     // squared radius leaves as one partial per workgroup; ccp_finish adds them in order.
     const int p = blockIdx.z, i = blockIdx.y;
     const CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double red[4];
     const int tid = threadIdx.x, np = c.np, ld = c.ld, gen = sc->gen;
     const int pj = blockIdx.x * 256 + tid;
@@ -453,7 +433,7 @@ __global__ __launch_bounds__(256) void ccp_finish(CcpDev d, CcpConst c, int rpar
 {
     const int p = blockIdx.x;
     CcpScal *sc = d.scal + p;
-    if (ccp_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double red[4];
     const int tid = threadIdx.x, np = c.np;
     if (rparts > 0)
@@ -463,23 +443,15 @@ __global__ __launch_bounds__(256) void ccp_finish(CcpDev d, CcpConst c, int rpar
             for (int k = 1; k < rparts; k++) s2 += rp[k];
             d.radius[(size_t) p * np + q] = sqrt(s2);
         }
-    auto block_sum = [&](double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = v;
-        __syncthreads();
-        return red[0] + red[1] + red[2] + red[3];
-    };
     double s = 0.;
     for (int q = tid; q < np; q += 256) s += d.radius[(size_t) p * np + q];
-    const double mean = block_sum(s) / np;
+    const double mean = block_sum<4>(s, red) / np;
     double m2 = 0.;
     for (int q = tid; q < np; q += 256) {
         const double dd = d.radius[(size_t) p * np + q] - mean;
         m2 += dd * dd;
     }
-    m2 = block_sum(m2);
+    m2 = block_sum<4>(m2, red);
     if (tid == 0) {
         sc->gen += 1;
         sc->m2 = m2;

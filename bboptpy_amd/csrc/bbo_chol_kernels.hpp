@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void chol_paths(CmaDev d, CmaConst c)
         ps[j] = v;
         ssq += v * v;
     }
-    ssq = wave_sum(ssq);
+    ssq = group_sum<64>(ssq);
     if ((tid & 63) == 0) red[tid >> 6] = ssq;
     __syncthreads();
     if (tid == 0) sc->pslen = sqrt(red[0] + red[1] + red[2] + red[3]);
@@ -236,11 +236,11 @@ __global__ __launch_bounds__(256) void chol_factor(CmaDev d, CmaConst c, int in_
                     M[(k0 + r) * lm + k0 + j] = l;
                 }
                 if (r == j) M[(k0 + j) * lm + k0 + j] = ljj;
-                cma_wave_sync();
+                wave_sync();
                 if (r > j && r < 16)
                     for (int k = j + 1; k <= r; k++)
                         M[(k0 + r) * lm + k0 + k] -= l * M[(k0 + k) * lm + k0 + j];
-                cma_wave_sync();
+                wave_sync();
             }
         }
         __syncthreads();
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void chol_history_stop(CmaDev d, CmaConst c)
                 hb[head] = f[order[0]];
                 hk[head] = f[order[c.ik]];
             }
-            cma_wave_sync();
+            wave_sync();
             if (len == c.hlen) {
                 double lo = BBO_INF, hi = -BBO_INF;
                 for (int k = lane; k < c.hlen; k += 64) {
@@ -365,14 +365,14 @@ __global__ __launch_bounds__(256) void chol_history_stop(CmaDev d, CmaConst c)
         __syncthreads();
         double s = 0.;
         for (int k = tid; k < c.lambda; k += 256) s += rad[k];
-        s = wave_sum(s);
+        s = group_sum<64>(s);
         if (lane == 0) red[tid >> 6] = s;
         __syncthreads();
         const double mean = (((red[0] + red[1]) + red[2]) + red[3]) / c.lambda;
         __syncthreads();
         s = 0.;
         for (int k = tid; k < c.lambda; k += 256) s += (rad[k] - mean) * (rad[k] - mean);
-        s = wave_sum(s);
+        s = group_sum<64>(s);
         if (lane == 0) red[tid >> 6] = s;
         __syncthreads();
         const double m2 = ((red[0] + red[1]) + red[2]) + red[3];

@@ -1111,41 +1111,23 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     enter_population("get()", p);
     const CmaConst &c = c_;
     const size_t ld = c.ld, n = c.n;
-    auto vec = [&](const DevBuf<double> &b) {   // [P][ld] -> n
-        if (out && cap >= (int) n) b.download(out, n, p * ld);
-        return (int) n;
-    };
-    auto mat = [&](const DevBuf<double> &b, size_t rows, size_t rstride, size_t cols,
-            size_t base) {
-        if (out && cap >= (int) (rows * cols)) {
-            std::vector<double> tmp(rows * rstride);
-            b.download(tmp.data(), rows * rstride, base);
-            for (size_t i = 0; i < rows; i++)
-                std::copy(tmp.begin() + i * rstride, tmp.begin() + i * rstride + cols,
-                        out + i * cols);
-        }
-        return (int) (rows * cols);
-    };
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
+    const StateOut o { out, cap };
     if (c.variant == 2 && (k == "B" || k == "C" || k == "invsqrtC" || k == "ycoeff"))
         throw Error(BBO_ERR_KEY, "SepCMAES keeps a diagonal covariance: read 'csep' and 'D'");
     if (c.variant == 3 && (k == "B" || k == "C" || k == "D" || k == "invsqrtC" || k == "ycoeff" || k == "csep"))
         throw Error(BBO_ERR_KEY, "CholeskyCMAES keeps the factor: read 'A'");
     if (k == "A") {
         if (c.variant != 3) throw Error(BBO_ERR_KEY, "'A' belongs to CholeskyCMAES");
-        return mat(A_, n, ld, n, p * ld * ld);
+        return o.rows(A_, p * ld, c.n, c.n, c.ld);
     }
-    if (k == "xmean") return vec(xmean_);
-    if (k == "xold") return vec(xold_);
-    if (k == "pc") return vec(pc_);
-    if (k == "ps") return vec(ps_);
-    if (k == "D") return vec(D_);
-    if (k == "csep") return vec(csep_);
-    if (k == "B") return mat(B_, n, ld, n, p * ld * ld);
-    if (k == "C") return mat(C_, n, ld, n, p * ld * ld);
+    if (k == "xmean") return o.vec(xmean_, p * ld, (int) n);
+    if (k == "xold") return o.vec(xold_, p * ld, (int) n);
+    if (k == "pc") return o.vec(pc_, p * ld, (int) n);
+    if (k == "ps") return o.vec(ps_, p * ld, (int) n);
+    if (k == "D") return o.vec(D_, p * ld, (int) n);
+    if (k == "csep") return o.vec(csep_, p * ld, (int) n);
+    if (k == "B") return o.rows(B_, p * ld, c.n, c.n, c.ld);
+    if (k == "C") return o.rows(C_, p * ld, c.n, c.n, c.ld);
     if (k == "invsqrtC") {
         if (c.lazy_isc && out) {         // not kept current by the generations: form it now
             const int hs = c_.honor_stop;
@@ -1155,7 +1137,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
             BBO_HIP(hipGetLastError());
             BBO_HIP(hipStreamSynchronize(stream_));
         }
-        return mat(isc_, n, ld, n, p * ld * ld);
+        return o.rows(isc_, p * ld, c.n, c.n, c.ld);
     }
     if (k == "BD") {
         // the sampler's operand B diag(D) as the kernels hold it (bfrag_index), unpacked to n x n row-major
@@ -1167,7 +1149,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         }
         return (int) (n * n);
     }
-    if (k == "arx") return mat(X_, c.lambda, ld, n, (size_t) p * c.lambda_pad * ld);
+    if (k == "arx") return o.rows(X_, (size_t) p * c.lambda_pad, c.lambda, c.n, c.ld);
     if (k == "weights") {
         if (out && cap >= c.mu) weights_.download(out, c.mu);
         return c.mu;
@@ -1228,60 +1210,60 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     }
     CmaScal s;
     scal_.download(&s, 1, p);
-    if (k == "sigma") return one(s.sigma);
-    if (k == "it") return one(s.it);
-    if (k == "fev") return one(s.fev);
-    if (k == "flag") return one(s.flag);
-    if (k == "stop") return one(s.stop);
-    if (k == "hsig") return one(s.hsig);
-    if (k == "pslen") return one(s.pslen);
-    if (k == "fbest") return one(s.fbest);
-    if (k == "fworst") return one(s.fworst);
-    if (k == "eigenlastev") return one(s.eigenlastev);
-    if (k == "eigen_done") return one(s.eigen_done);
-    if (k == "basis_ok") return one(s.basis_ok);
-    if (k == "eig_stage") return one(s.eig_stage);
-    if (k == "eig_mw_fail") return one(s.eig_mw_fail);     // (bbo_eig_mw.hpp: sticky)
+    if (k == "sigma") return o.one(s.sigma);
+    if (k == "it") return o.one(s.it);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "flag") return o.one(s.flag);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "hsig") return o.one(s.hsig);
+    if (k == "pslen") return o.one(s.pslen);
+    if (k == "fbest") return o.one(s.fbest);
+    if (k == "fworst") return o.one(s.fworst);
+    if (k == "eigenlastev") return o.one(s.eigenlastev);
+    if (k == "eigen_done") return o.one(s.eigen_done);
+    if (k == "basis_ok") return o.one(s.basis_ok);
+    if (k == "eig_stage") return o.one(s.eig_stage);
+    if (k == "eig_mw_fail") return o.one(s.eig_mw_fail);     // (bbo_eig_mw.hpp: sticky)
     if (k == "chol_repairs") {                             // (chol_factor: sticky)
         if (c.variant != 3) throw Error(BBO_ERR_KEY, "'chol_repairs' belongs to CholeskyCMAES");
         int r = 0;
         chol_repairs_.download(&r, 1, p);
-        return one(r);
+        return o.one(r);
     }
-    if (c.variant == 3 && k == "chol_tri") return one(chol_tri_ ? 1 : 0);
-    if (c.variant == 3 && k == "stol") return one(c.stol);
-    if (c.variant == 3 && k == "ranked") return one(c.ranked);
-    if (k == "eig_mw_off") return one(mw_disabled_ ? 1 : 0);
-    if (k == "eig_split_maxp") return one(split_maxp_);
-    if (k == "eig_mw_reserved") return one((double) mw_reserved_);       // this engine's share of the device's ...
+    if (c.variant == 3 && k == "chol_tri") return o.one(chol_tri_ ? 1 : 0);
+    if (c.variant == 3 && k == "stol") return o.one(c.stol);
+    if (c.variant == 3 && k == "ranked") return o.one(c.ranked);
+    if (k == "eig_mw_off") return o.one(mw_disabled_ ? 1 : 0);
+    if (k == "eig_split_maxp") return o.one(split_maxp_);
+    if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups
         MwBudget &b = MwBudget::get();
         std::lock_guard<std::mutex> lock(b.m);
-        return one((double) b.capacity(params_.device));
+        return o.one((double) b.capacity(params_.device));
     }
-    if (k == "best_len") return one(s.hist_len);
-    if (k == "best_buffer") return one(s.hist_head);
-    if (k == "ibest") return one(s.ibw[0]);
-    if (k == "n") return one(c.n);
-    if (k == "lambda") return one(c.lambda);
-    if (k == "mu") return one(c.mu);
-    if (k == "mueff") return one(c.mueff);
-    if (k == "cc") return one(c.cc);
-    if (k == "cs") return one(c.cs);
-    if (k == "c1") return one(c.c1);
-    if (k == "cmu") return one(c.cmu);
-    if (k == "cneg") return one(c.cneg);
-    if (k == "alphaold") return one(c.alphaold);
-    if (k == "cm") return one(c.cm);
-    if (k == "ccov") return one(c.ccov);
-    if (k == "damps") return one(c.damps);
-    if (k == "chi") return one(c.chi);
-    if (k == "eigenfreq") return one(c.eigenfreq);
-    if (k == "hlen") return one(c.hlen);
-    if (k == "ik") return one(c.ik);
-    if (k == "mit") return one(c.mit);
-    if (k == "mfev") return one(c.mfev);
-    if (k == "sigma0") return one(c.sigma0);
+    if (k == "best_len") return o.one(s.hist_len);
+    if (k == "best_buffer") return o.one(s.hist_head);
+    if (k == "ibest") return o.one(s.ibw[0]);
+    if (k == "n") return o.one(c.n);
+    if (k == "lambda") return o.one(c.lambda);
+    if (k == "mu") return o.one(c.mu);
+    if (k == "mueff") return o.one(c.mueff);
+    if (k == "cc") return o.one(c.cc);
+    if (k == "cs") return o.one(c.cs);
+    if (k == "c1") return o.one(c.c1);
+    if (k == "cmu") return o.one(c.cmu);
+    if (k == "cneg") return o.one(c.cneg);
+    if (k == "alphaold") return o.one(c.alphaold);
+    if (k == "cm") return o.one(c.cm);
+    if (k == "ccov") return o.one(c.ccov);
+    if (k == "damps") return o.one(c.damps);
+    if (k == "chi") return o.one(c.chi);
+    if (k == "eigenfreq") return o.one(c.eigenfreq);
+    if (k == "hlen") return o.one(c.hlen);
+    if (k == "ik") return o.one(c.ik);
+    if (k == "mit") return o.one(c.mit);
+    if (k == "mfev") return o.one(c.mfev);
+    if (k == "sigma0") return o.one(c.sigma0);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 
@@ -1291,14 +1273,12 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
     rank_wrote_norms_ = false;      // (S of a ranking before this call may not match the new state)
     const CmaConst &c = c_;
     const size_t ld = c.ld, n = c.n;
-    auto vec = [&](DevBuf<double> &b) {
+    auto vec_in = [&](DevBuf<double> &b) {          // n -> [P][ld]
         BBO_REQUIRE(count == (int) n, "set: wrong element count");
-        std::vector<double> tmp(ld, 0.);
-        std::copy(in, in + n, tmp.begin());
-        b.upload(tmp.data(), ld, p * ld);
+        upload_rows(b, p, 1, c.n, c.ld, in);
         return count;
     };
-    auto mat = [&](DevBuf<double> &b) {
+    auto mat_in = [&](DevBuf<double> &b) {          // [n][n] -> [ld][ld]: the padding ROWS are zeroed too
         BBO_REQUIRE(count == (int) (n * n), "set: wrong element count");
         std::vector<double> tmp(ld * ld, 0.);
         for (size_t i = 0; i < n; i++) std::copy(in + i * n, in + (i + 1) * n, tmp.begin() + i * ld);
@@ -1325,9 +1305,7 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
     }
     if (c.variant == 3 && k == "arx") {          // (crafted stop states of the Cholesky variant's rule)
         BBO_REQUIRE(count == (int) (c.lambda * n), "set: wrong element count");
-        std::vector<double> tmp((size_t) c.lambda * ld, 0.);
-        for (size_t i = 0; i < (size_t) c.lambda; i++) std::copy(in + i * n, in + (i + 1) * n, tmp.begin() + i * ld);
-        X_.upload(tmp.data(), tmp.size(), (size_t) p * c.lambda_pad * ld);
+        upload_rows(X_, (size_t) p * c.lambda_pad, c.lambda, c.n, c.ld, in);
         return count;
     }
     if (c.variant == 3 && k == "fitness") {      // (the same; the ranking is NOT redone: fit_idx keeps its order)
@@ -1335,19 +1313,19 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
         f_.upload(in, c.lambda, (size_t) p * c.lambda_pad);
         return count;
     }
-    if (k == "xmean") return vec(xmean_);
-    if (k == "xold") return vec(xold_);
-    if (k == "pc") return vec(pc_);
-    if (k == "ps") return vec(ps_);
+    if (k == "xmean") return vec_in(xmean_);
+    if (k == "xold") return vec_in(xold_);
+    if (k == "pc") return vec_in(pc_);
+    if (k == "ps") return vec_in(ps_);
     if (k == "csep") {
         BBO_REQUIRE(c.variant == 2, "csep belongs to SepCMAES");
-        const int r = vec(csep_);
+        const int r = vec_in(csep_);
         std::vector<double> dd(ld, 1.);
         for (size_t i = 0; i < n; i++) dd[i] = std::sqrt(in[i]);
         D_.upload(dd.data(), ld, p * ld);
         return r;
     }
-    if (k == "C") return mat(C_);
+    if (k == "C") return mat_in(C_);
     if (k == "best_hist" || k == "kth_hist") {   // cmaes_history rings (crafted stop states)
         BBO_REQUIRE(count == c.hlen, "set: wrong element count");
         (k == "best_hist" ? hist_best_ : hist_kth_).upload(in, c.hlen, (size_t) p * c.hlen);
@@ -1363,7 +1341,7 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
             D_.upload(tmp.data(), ld, p * ld);
             r = count;
         } else {
-            r = mat(B_);
+            r = mat_in(B_);
         }
         // refresh C^-1/2 and the packed MFMA operands
         c_.honor_stop = 0;

@@ -29,27 +29,6 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 
 #define BBO_INF (__builtin_huge_val())
 
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// hand-over point between the lanes of ONE wavefront (single-wavefront bodies: the hardware
-// keeps a wavefront's memory operations in order, the fence stops the compiler from moving
-// loads across the point)
-__device__ inline void cma_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline bool pop_frozen(const CmaConst &c, const CmaScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
 // The four normals Philox call q of candidate `row` delivers: columns cma_quad_col0(q) + 4 i,
 // i = 0..3 -- one lane's A-fragment elements of four consecutive k-steps.  Injected Z
 // (parity tests) and the Z recorder go through the same mapping.  tab: normal_table_fill'ed.
@@ -1380,7 +1359,7 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
     coef_link1(2);
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) load_step(0, ks, ks);
-    cma_wave_sync();
+    wave_sync();
     for (int ch = 0; ch < nch; ch++) {
         const int buf = ch & 1;
         // (this k-step's coefficients were read from the strip a k-step ago: with the scheduling
@@ -1405,7 +1384,7 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
         put_coef(buf ^ 1);                // chunk ch + 1, loaded during chunk ch - 1 / the prologue
         coef_link2();                     // chunk ch + 2, from the rank loaded a chunk ago
         coef_link1(ch + 3);
-        cma_wave_sync();
+        wave_sync();
         // Pacing, not synchronisation: the four wavefronts share no data, but they read the same
         // rows, and left alone they drift apart until a row one of them fetched has left L1 / L2
         // when the next one asks for it (1.49 x the algorithmic bytes from HBM, round-3 counters).
@@ -1566,7 +1545,7 @@ __device__ __forceinline__ void paths_body(const CmaDev &d, const CmaConst &c, i
             ssq += v * v;
         }
     }
-    ssq = wave_sum(ssq);
+    ssq = group_sum<64>(ssq);
     if ((tid & 63) == 0) red[tid >> 6] = ssq;
     __syncthreads();
     double rsum = 0.;
@@ -1892,7 +1871,7 @@ __device__ __forceinline__ void history_stop_body(const CmaDev &d, const CmaCons
             hk[head] = f[order[c.ik]];
         }
         if (len < c.hlen) len++;
-        cma_wave_sync();
+        wave_sync();
         if (len == c.hlen) {
             double lo = BBO_INF, hi = -BBO_INF;
             for (int k = lane; k < c.hlen; k += 64) {
@@ -1909,7 +1888,7 @@ __device__ __forceinline__ void history_stop_body(const CmaDev &d, const CmaCons
         }
     }
     it++;
-    cma_wave_sync();
+    wave_sync();
 
     const double sigma = sc->sigma;
     const double *pc = d.pc + (size_t) p * ld, *xm = d.xmean + (size_t) p * ld;

@@ -130,30 +130,12 @@ void CsoEngine::init(int n, const double *lower, const double *upper, const doub
 }
 
 // host objective: every particle (init) or the losers of this generation (slots that are not
-// the first of their group), so that the callable is called exactly `fev` times
+// the first of their group: the winner of a group does not move), in slot order
 void CsoEngine::host_evaluate(bool losers_only)
 {
-    const CsoConst &c = c_;
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<CsoScal> sc(c.npop);
-    scal_.download(sc.data(), c.npop);
-    std::vector<double> xh((size_t) c.np * c.ld), fh(c.np);
-    std::vector<int> occ(c.np);
-    for (int p = 0; p < c.npop; p++) {
-        if (c.honor_stop && sc[p].stop) continue;
-        X_.download(xh.data(), xh.size(), (size_t) p * c.np * c.ld);
-        f_.download(fh.data(), c.np, (size_t) p * c.np);
-        occ_.download(occ.data(), c.np, (size_t) p * c.np);
-        for (int s = 0; s < c.np; s++) {
-            if (losers_only && s % c.pc == 0) continue;   // the winner of a group does not move
-            const int row = occ[s];
-            double f = 0.;
-            obj_.eval_host(xh.data() + (size_t) row * c.ld, 1, c.n, c.ld, &f);
-            nan_to_inf(&f, 1);
-            fh[row] = f;
-        }
-        f_.upload(fh.data(), c.np, (size_t) p * c.np);
-    }
+    const int pc = c_.pc;
+    host_evaluate_rows(X_, f_, c_.np, c_.n, c_.ld, c_.honor_stop, &occ_,
+            [=](int s) { return losers_only && s % pc == 0; });
 }
 
 void CsoEngine::generation(bool honor_stop)
@@ -174,12 +156,8 @@ void CsoEngine::generation(bool honor_stop)
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
     timer_.begin(stream_, K_SHUFFLE);
-    {
-        int bits = 1;
-        while ((1u << bits) < (unsigned) c.np) bits++;
-        hipLaunchKernelGGL(cso_shuffle, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_, c_,
-                (bits + 1) / 2);
-    }
+    hipLaunchKernelGGL(cso_shuffle, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_, c_,
+            shuffle_key_bits(c.np));
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
     timer_.begin(stream_, K_GROUPS);
@@ -220,11 +198,8 @@ void CsoEngine::solution(int population, double *x_out, int *n_evals, int *conve
     enter_population("solution()", population);
     CsoScal s;
     scal_.download(&s, 1, population);
-    std::vector<double> x(c_.ld);
-    X_.download(x.data(), c_.ld, ((size_t) population * c_.np + s.ibest) * c_.ld);
-    std::copy(x.begin(), x.begin() + c_.n, x_out);
-    *n_evals = s.fev;
-    *converged = s.conv;
+    report_solution(s, X_, ((size_t) population * c_.np + s.ibest) * c_.ld, c_.n, c_.ld, x_out, n_evals,
+            converged);
 }
 
 int CsoEngine::get(const std::string &k, int p, double *out, int cap)
@@ -234,55 +209,28 @@ int CsoEngine::get(const std::string &k, int p, double *out, int cap)
     CsoScal s;
     scal_.download(&s, 1, p);
     const size_t pb = (size_t) p * c.np;
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
+    const StateOut o { out, cap };
     if (k == "profile") return profile_report(out, cap);
     // per-particle arrays are reported in SLOT order, like the reference's _swarm
     if (k == "x" || k == "v" || k == "pmean") {
-        const int cnt = c.np * c.n;
         if (k == "pmean" && !c.ring) return 0;
-        if (out && cap >= cnt) {
-            std::vector<int> occ(c.np);
-            occ_.download(occ.data(), c.np, pb);
-            std::vector<double> M((size_t) c.np * c.ld);
-            (k == "x" ? X_ : k == "v" ? V_ : PM_).download(M.data(), M.size(), pb * c.ld);
-            for (int sl = 0; sl < c.np; sl++)
-                std::copy(M.begin() + (size_t) occ[sl] * c.ld,
-                        M.begin() + (size_t) occ[sl] * c.ld + c.n, out + (size_t) sl * c.n);
-        }
-        return cnt;
+        return o.rows_by_slot(k == "x" ? X_ : k == "v" ? V_ : PM_, occ_, pb, c.np, c.np, c.n, c.ld);
     }
-    if (k == "f" || k == "home") {
-        if (out && cap >= c.np) {
-            std::vector<int> occ(c.np);
-            occ_.download(occ.data(), c.np, pb);
-            std::vector<double> f(c.np);
-            f_.download(f.data(), c.np, pb);
-            for (int sl = 0; sl < c.np; sl++) out[sl] = k == "f" ? f[occ[sl]] : (double) occ[sl];
-        }
-        return c.np;
-    }
-    if (k == "mean" || k == "meanw" || k == "xbest") {
-        if (out && cap >= c.n) {
-            std::vector<double> v(c.ld);
-            if (k == "xbest") X_.download(v.data(), c.ld, (pb + s.ibest) * c.ld);
-            else (k == "mean" ? mean_ : meanw_).download(v.data(), c.ld, (size_t) p * c.ld);
-            std::copy(v.begin(), v.begin() + c.n, out);
-        }
-        return c.n;
-    }
-    if (k == "fbest") return one(s.fbest);
-    if (k == "np") return one(c.np);
-    if (k == "fev") return one(s.fev);
-    if (k == "it") return one(s.gen);
-    if (k == "stop") return one(s.stop);
-    if (k == "conv") return one(s.conv);
-    if (k == "m2") return one(s.m2);
-    if (k == "phil") return one(c.phil);
-    if (k == "phih") return one(c.phih);
-    if (k == "n") return one(c.n);
+    if (k == "f") return o.vec_by_slot(f_, occ_, pb, c.np, c.np);
+    if (k == "home") return o.ints(occ_, pb, c.np);
+    if (k == "xbest") return o.vec(X_, (pb + s.ibest) * c.ld, c.n);
+    if (k == "mean") return o.vec(mean_, (size_t) p * c.ld, c.n);
+    if (k == "meanw") return o.vec(meanw_, (size_t) p * c.ld, c.n);
+    if (k == "fbest") return o.one(s.fbest);
+    if (k == "np") return o.one(c.np);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "it") return o.one(s.gen);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "conv") return o.one(s.conv);
+    if (k == "m2") return o.one(s.m2);
+    if (k == "phil") return o.one(c.phil);
+    if (k == "phih") return o.one(c.phih);
+    if (k == "n") return o.one(c.n);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 

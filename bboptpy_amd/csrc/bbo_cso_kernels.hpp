@@ -20,27 +20,6 @@ namespace bbo {
 
 #define CSO_INF (__builtin_huge_val())
 
-__device__ inline bool cso_frozen(const CsoConst &c, const CsoScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
-// orders a wavefront's LDS accesses among its own lanes (hardware keeps them in order; the fence
-// stops the compiler from moving loads across the point)
-__device__ inline void cso_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-template<int G>
-__device__ inline double cso_group_sum(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
-
 // grid (ceil(np/16), P), 256 threads, LDS 16 * ld doubles
 __global__ __launch_bounds__(256) void cso_init(CsoDev d, CsoConst c)
 {
@@ -66,7 +45,7 @@ __global__ __launch_bounds__(256) void cso_init(CsoDev d, CsoConst c)
         }
     }
     __syncthreads();
-    ssq = cso_group_sum<16>(ssq);
+    ssq = group_sum<16>(ssq);
     double f = CSO_INF;
     if (c.obj >= 0) {
         f = eval_row_group<16>(c.obj, c.n, row, d.aux, g);
@@ -84,7 +63,7 @@ __global__ __launch_bounds__(256) void cso_init(CsoDev d, CsoConst c)
 __global__ __launch_bounds__(256) void cso_ring_mean(CsoDev d, CsoConst c)
 {
     const int p = blockIdx.y;
-    if (cso_frozen(c, d.scal + p)) return;
+    if (pop_frozen(c, d.scal + p)) return;
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = blockIdx.x * 16 + r, ld = c.ld, np = c.np;
     if (i >= np) return;
@@ -110,7 +89,7 @@ __global__ __launch_bounds__(256) void cso_ring_mean(CsoDev d, CsoConst c)
 __global__ __launch_bounds__(256) void cso_colsum(CsoDev d, CsoConst c, int step, int count)
 {
     const int p = blockIdx.y, part = blockIdx.x;
-    if (cso_frozen(c, d.scal + p)) return;
+    if (pop_frozen(c, d.scal + p)) return;
     const int per = (count + c.parts - 1) / c.parts;
     const int q0 = part * per, q1 = min(count, q0 + per);
     const size_t pb = (size_t) p * c.np;
@@ -145,7 +124,7 @@ __global__ __launch_bounds__(256) void cso_colsum(CsoDev d, CsoConst c, int step
 __global__ __launch_bounds__(256) void cso_mean(CsoDev d, CsoConst c, int winners, int count)
 {
     const int p = blockIdx.x;
-    if (cso_frozen(c, d.scal + p)) return;
+    if (pop_frozen(c, d.scal + p)) return;
     double *dst = (winners ? d.meanw : d.mean) + (size_t) p * c.ld;
     for (int j = threadIdx.x; j < c.ld; j += 256) {
         double s = 0.;
@@ -178,7 +157,7 @@ __global__ __launch_bounds__(256) void cso_shuffle(CsoDev d, CsoConst c, int kb)
 {
     const int p = blockIdx.y;
     const CsoScal *sc = d.scal + p;
-    if (cso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= c.np) return;
     const size_t pb = (size_t) p * c.np;
@@ -192,7 +171,7 @@ __global__ __launch_bounds__(256) void cso_shuffle(CsoDev d, CsoConst c, int kb)
 __global__ __launch_bounds__(256) void cso_groups(CsoDev d, CsoConst c)
 {
     const int p = blockIdx.y;
-    if (cso_frozen(c, d.scal + p)) return;
+    if (pop_frozen(c, d.scal + p)) return;
     const int gI = blockIdx.x * 256 + threadIdx.x;
     if (gI >= c.ngroup) return;
     const size_t pb = (size_t) p * c.np;
@@ -239,7 +218,7 @@ __global__ __launch_bounds__(256) void cso_compete(CsoDev d, CsoConst c)
 {
     const int p = blockIdx.y;
     const CsoScal *sc = d.scal + p;
-    if (cso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     const int tid = threadIdx.x, r = tid / G, g = tid % G;
     const int gI = blockIdx.x * (blockDim.x / G) + r, ld = c.ld, n = c.n, gen = sc->gen;
@@ -333,8 +312,8 @@ __global__ __launch_bounds__(256) void cso_compete(CsoDev d, CsoConst c)
                 }
             }
         }
-        cso_wave_sync();          // (a team sits inside one wavefront: its row is its own)
-        ssq = cso_group_sum<G>(ssq);
+        wave_sync();              // (a team sits inside one wavefront: its row is its own)
+        ssq = group_sum<G>(ssq);
         double f = CSO_INF;
         if (c.obj >= 0) {
             f = eval_row_group<G>(c.obj, n, trial, d.aux, g);
@@ -346,7 +325,7 @@ __global__ __launch_bounds__(256) void cso_compete(CsoDev d, CsoConst c)
         }
         // the next (better) loser of this group reads x of its own parent only; its own row
         // was last written in an earlier generation.  The wavefront barrier orders the LDS reuse.
-        cso_wave_sync();
+        wave_sync();
     }
     if (FUSE) {
         // the teams' sums through their (now free) LDS rows, then the workgroup's teams in order
@@ -395,7 +374,7 @@ __global__ __launch_bounds__(256) void cso_team_colsum(CsoDev d, CsoConst c)
 __global__ __launch_bounds__(256) void cso_wgsum(CsoDev d, CsoConst c)
 {
     const int p = blockIdx.y, part = blockIdx.x;
-    if (cso_frozen(c, d.scal + p)) return;
+    if (pop_frozen(c, d.scal + p)) return;
     const int per = (c.nwg + c.parts - 1) / c.parts;
     const int q0 = part * per, q1 = min(c.nwg, q0 + per);
     const double *src = d.wgpart + (size_t) p * c.nwg * c.ld;
@@ -423,7 +402,7 @@ __global__ __launch_bounds__(256) void cso_finish_part(CsoDev d, CsoConst c)
 {
     const int p = blockIdx.y, part = blockIdx.x;
     const CsoScal *sc = d.scal + p;
-    if (cso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double sval[4];
     __shared__ int sidx[4];
     __shared__ double scratch[4];
@@ -518,7 +497,7 @@ __global__ __launch_bounds__(64) void cso_finish(CsoDev d, CsoConst c, int init_
 {
     const int p = blockIdx.x;
     CsoScal *sc = d.scal + p;
-    if (cso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     if (threadIdx.x != 0) return;
     const size_t pb = (size_t) p * c.np;
     const double *in = d.fpart + (size_t) p * c.fparts * CSO_FPART;

@@ -257,17 +257,10 @@ void DeEngine::solution(int population, double *x_out, int *n_evals, int *conver
     scal_.download(&s, 1, population);
     int best = 0;
     order_.download(&best, 1, (size_t) population * c_.npinit);
-    std::vector<double> x(c_.ld);
-    (s.cur == 0 ? Xa_ : Xb_).download(x.data(), c_.ld,
-            ((size_t) population * c_.npinit + best) * c_.ld);
-    std::copy(x.begin(), x.begin() + c_.n, x_out);
-    *n_evals = s.fev;
-    if (s.gen == 0) {
-        // converged() before any generation: evaluate the radius spread of the initial swarm
+    report_solution(s, s.cur == 0 ? Xa_ : Xb_, ((size_t) population * c_.npinit + best) * c_.ld, c_.n, c_.ld,
+            x_out, n_evals, converged);
+    if (s.gen == 0)     // converged() before any generation: the radius spread of the initial swarm
         *converged = radius_spread_converged(radius_, (size_t) population * c_.npinit, s.np, c_.tol);
-    } else {
-        *converged = s.conv;
-    }
 }
 
 int DeEngine::get(const std::string &k, int p, double *out, int cap)
@@ -277,69 +270,18 @@ int DeEngine::get(const std::string &k, int p, double *out, int cap)
     DeScal s;
     scal_.download(&s, 1, p);
     const size_t pbase = (size_t) p * c.npinit;
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
+    const StateOut o { out, cap };
     if (k == "profile") return profile_report(out, cap);
     if (const int r = prog_get(k, out, cap); r >= 0) return r;
-    if (k == "x" || k == "f") {   // in sorted order, like the reference's _swarm
-        const int cnt = k == "x" ? s.np * c.n : s.np;
-        if (out && cap >= cnt) {
-            std::vector<int> ord(s.np);
-            order_.download(ord.data(), s.np, pbase);
-            if (k == "f") {
-                std::vector<double> f(c.npinit);
-                (s.cur == 0 ? fa_ : fb_).download(f.data(), c.npinit, pbase);
-                for (int i = 0; i < s.np; i++) out[i] = f[ord[i]];
-            } else {
-                std::vector<double> X((size_t) c.npinit * c.ld);
-                (s.cur == 0 ? Xa_ : Xb_).download(X.data(), X.size(), pbase * c.ld);
-                for (int i = 0; i < s.np; i++)
-                    std::copy(X.begin() + (size_t) ord[i] * c.ld,
-                            X.begin() + (size_t) ord[i] * c.ld + c.n, out + (size_t) i * c.n);
-            }
-        }
-        return cnt;
-    }
-    if (k == "arch") {
-        const int cnt = s.larch * c.n;
-        if (out && cap >= cnt && cnt > 0) {
-            std::vector<double> A((size_t) s.larch * c.ld);
-            arch_.download(A.data(), A.size(), pbase * c.ld);
-            for (int i = 0; i < s.larch; i++)
-                std::copy(A.begin() + (size_t) i * c.ld, A.begin() + (size_t) i * c.ld + c.n,
-                        out + (size_t) i * c.n);
-        }
-        return cnt;
-    }
-    if (k == "MCR" || k == "MF") {
-        if (out && cap >= c.h) (k == "MCR" ? MCR_ : MF_).download(out, c.h, (size_t) p * c.h);
-        return c.h;
-    }
-    if (k == "rec_flag" || k == "rec_cr" || k == "rec_f" || k == "rec_df") {
-        if (out && cap >= s.np) {
-            if (k == "rec_flag") {
-                std::vector<int> fl(s.np);
-                rec_flag_.download(fl.data(), s.np, pbase);
-                for (int i = 0; i < s.np; i++) out[i] = fl[i];
-            } else {
-                (k == "rec_cr" ? rec_cr_ : k == "rec_f" ? rec_f_ : rec_df_).download(out, s.np,
-                        pbase);
-            }
-        }
-        return s.np;
-    }
-    if (k == "cr") {   // SaNSDE: per-individual CR in sorted order
-        if (out && cap >= s.np) {
-            std::vector<int> ord(s.np);
-            order_.download(ord.data(), s.np, pbase);
-            std::vector<double> crv(c.npinit);
-            (s.cur == 0 ? cra_ : crb_).download(crv.data(), c.npinit, pbase);
-            for (int i = 0; i < s.np; i++) out[i] = crv[ord[i]];
-        }
-        return s.np;
-    }
+    // "x", "f" and "cr" (SaNSDE's per-individual CR) in sorted order, like the reference's _swarm
+    if (k == "x") return o.rows_by_slot(s.cur == 0 ? Xa_ : Xb_, order_, pbase, s.np, c.npinit, c.n, c.ld);
+    if (k == "f") return o.vec_by_slot(s.cur == 0 ? fa_ : fb_, order_, pbase, s.np, c.npinit);
+    if (k == "cr") return o.vec_by_slot(s.cur == 0 ? cra_ : crb_, order_, pbase, s.np, c.npinit);
+    if (k == "arch") return o.rows(arch_, pbase, s.larch, c.n, c.ld);
+    if (k == "MCR" || k == "MF") return o.vec(k == "MCR" ? MCR_ : MF_, (size_t) p * c.h, c.h);
+    if (k == "rec_flag") return o.ints(rec_flag_, pbase, s.np);
+    if (k == "rec_cr" || k == "rec_f" || k == "rec_df")
+        return o.vec(k == "rec_cr" ? rec_cr_ : k == "rec_f" ? rec_f_ : rec_df_, pbase, s.np);
     if (k == "pns" || k == "pnf" || k == "fpns" || k == "fpnf") {
         if (out && cap >= 2)
             for (int q = 0; q < 2; q++)
@@ -347,24 +289,24 @@ int DeEngine::get(const std::string &k, int p, double *out, int cap)
                                                                                      : s.fpnf[q];
         return 2;
     }
-    if (k == "p") return one(s.sp);
-    if (k == "fp") return one(s.sfp);
-    if (k == "crm") return one(s.crm);
-    if (k == "crrec") return one(s.crrec);
-    if (k == "crdeltaf") return one(s.crdeltaf);
-    if (k == "it") return one(s.gen);
-    if (k == "k") return one(s.k);
-    if (k == "np") return one(s.np);
-    if (k == "fev") return one(s.fev);
-    if (k == "gen") return one(s.gen);
-    if (k == "larch") return one(s.larch);
-    if (k == "mucr") return one(s.mucr);
-    if (k == "muf") return one(s.muf);
-    if (k == "stop") return one(s.stop);
-    if (k == "conv") return one(s.conv);
-    if (k == "m2") return one(s.m2);
-    if (k == "nsucc") return one(s.nsucc);
-    if (k == "n") return one(c.n);
+    if (k == "p") return o.one(s.sp);
+    if (k == "fp") return o.one(s.sfp);
+    if (k == "crm") return o.one(s.crm);
+    if (k == "crrec") return o.one(s.crrec);
+    if (k == "crdeltaf") return o.one(s.crdeltaf);
+    if (k == "it") return o.one(s.gen);
+    if (k == "k") return o.one(s.k);
+    if (k == "np") return o.one(s.np);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "gen") return o.one(s.gen);
+    if (k == "larch") return o.one(s.larch);
+    if (k == "mucr") return o.one(s.mucr);
+    if (k == "muf") return o.one(s.muf);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "conv") return o.one(s.conv);
+    if (k == "m2") return o.one(s.m2);
+    if (k == "nsucc") return o.one(s.nsucc);
+    if (k == "n") return o.one(c.n);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 
@@ -380,10 +322,7 @@ int DeEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "x") {   // rows in sorted order; follow with set("f") to re-rank
         BBO_REQUIRE(count % c.n == 0 && count / c.n <= c.npinit, "set x: bad element count");
         const int rows = count / c.n;
-        std::vector<double> X((size_t) rows * c.ld, 0.);
-        for (int i = 0; i < rows; i++)
-            std::copy(in + (size_t) i * c.n, in + (size_t) (i + 1) * c.n, X.begin() + (size_t) i * c.ld);
-        (s.cur == 0 ? Xa_ : Xb_).upload(X.data(), X.size(), pbase * c.ld);
+        upload_rows(s.cur == 0 ? Xa_ : Xb_, pbase, rows, c.n, c.ld, in);
         s.np = rows;
         scal_.upload(&s, 1, p);
         np_host_ = std::max(np_host_, rows);
@@ -401,13 +340,7 @@ int DeEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "arch") {
         BBO_REQUIRE(count % c.n == 0 && count / c.n <= c.npinit, "set arch: bad element count");
         const int rows = count / c.n;
-        if (rows > 0) {
-            std::vector<double> A((size_t) rows * c.ld, 0.);
-            for (int i = 0; i < rows; i++)
-                std::copy(in + (size_t) i * c.n, in + (size_t) (i + 1) * c.n,
-                        A.begin() + (size_t) i * c.ld);
-            arch_.upload(A.data(), A.size(), pbase * c.ld);
-        }
+        if (rows > 0) upload_rows(arch_, pbase, rows, c.n, c.ld, in);
         s.larch = rows;
         scal_.upload(&s, 1, p);
         return count;

@@ -24,19 +24,6 @@ namespace bbo {
 constexpr double DE_PI = 3.14159265358979323846;
 constexpr int DE_MAX_TRIES = 64;
 
-__device__ inline bool de_frozen(const DeConst &c, const DeScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
-template<int G>
-__device__ inline double group_sum_d(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
-
 // ---------------------------------------------------------------------------
 // initial population: x = lb + u (ub - lb), f = objective(x)
 // grid (ceil(npinit/16), P), 256 threads; dynamic LDS 16 * ld doubles
@@ -65,7 +52,7 @@ __global__ __launch_bounds__(256) void de_init(DeDev d, DeConst c)
         }
     }
     __syncthreads();
-    ssq = group_sum_d<16>(ssq);
+    ssq = group_sum<16>(ssq);
     if (c.obj >= 0) {
         double f = eval_row_group<16>(c.obj, c.n, row, d.aux, g);
         if (g == 0 && i < c.npinit) {
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(256) void de_rank(DeDev d, DeConst c, int which_nex
 {
     const int p = blockIdx.y;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ __attribute__((aligned(16))) double tile[RANK_TILE];
     const int np = sc->np;
     const int which = which_next ? (sc->cur ^ 1) : sc->cur;
@@ -103,7 +90,7 @@ __global__ __launch_bounds__(1024) void de_rank_sort(DeDev d, DeConst c, int whi
 {
     const int p = blockIdx.x;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ __attribute__((aligned(16))) double sortbuf[];
     double *keys = sortbuf;
     int *idx = reinterpret_cast<int*>(sortbuf + max(m, 1024));   // the sort pads to >= 1024
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(256) void de_rank_wave(DeDev d, DeConst c, int whic
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (p >= c.npop) return;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int which = which_next ? (sc->cur ^ 1) : sc->cur;
     const double *f = d.f[which] + (size_t) p * c.npinit;
     const int np = sc->np;
@@ -160,7 +147,7 @@ __global__ __launch_bounds__(256) void de_generation(DeDev d, DeConst c)
 {
     const int p = blockIdx.y;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = blockIdx.x * (blockDim.x >> 4) + r;
@@ -360,7 +347,7 @@ __global__ __launch_bounds__(256) void de_generation(DeDev d, DeConst c)
         }
     }
     __syncthreads();
-    cnt = group_sum_d<16>(cnt);
+    cnt = group_sum<16>(cnt);
 
     // ---- evaluate, select into the other buffer ---------------------------------------------
     double ft = BBO_INF_D;
@@ -403,7 +390,7 @@ __global__ __launch_bounds__(256) void de_generation(DeDev d, DeConst c)
             ssq += v.x * v.x + v.y * v.y;
         }
     }
-    ssq = group_sum_d<16>(ssq);
+    ssq = group_sum<16>(ssq);
     if (live && g == 0) {
         d.f[cur ^ 1][pbase + i] = accept ? ft : fold;
         d.radius[pbase + i] = sqrt(ssq);
@@ -426,7 +413,7 @@ __global__ __launch_bounds__(256) void sansde_generation(DeDev d, DeConst c)
 {
     const int p = blockIdx.y;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = blockIdx.x * (blockDim.x >> 4) + r;
@@ -584,7 +571,7 @@ __global__ __launch_bounds__(256) void sansde_generation(DeDev d, DeConst c)
         }
     }
     __syncthreads();
-    cnt = group_sum_d<16>(cnt);
+    cnt = group_sum<16>(cnt);
     if (live && g == 0) {
         d.crow[cur ^ 1][pbase + i] = CR;
         d.rec_cr[pbase + i] = c.repaircr ? cnt / n : CR;
@@ -624,7 +611,7 @@ __global__ __launch_bounds__(256) void sansde_generation(DeDev d, DeConst c)
             ssq += v.x * v.x + v.y * v.y;
         }
     }
-    ssq = group_sum_d<16>(ssq);
+    ssq = group_sum<16>(ssq);
     if (live && g == 0) {
         d.f[cur ^ 1][pbase + i] = accept ? ft : fold;
         d.radius[pbase + i] = sqrt(ssq);
@@ -639,7 +626,7 @@ __global__ __launch_bounds__(256) void de_select(DeDev d, DeConst c)
 {
     const int p = blockIdx.y;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = blockIdx.x * 16 + r;
     const int ld = c.ld, np = sc->np, cur = sc->cur;
@@ -666,7 +653,7 @@ __global__ __launch_bounds__(256) void de_select(DeDev d, DeConst c)
             ssq += v.x * v.x + v.y * v.y;
         }
     }
-    ssq = group_sum_d<16>(ssq);
+    ssq = group_sum<16>(ssq);
     if (live && g == 0) {
         d.f[cur ^ 1][pbase + i] = accept ? ft : fold;
         d.radius[pbase + i] = sqrt(ssq);
@@ -680,6 +667,7 @@ __global__ __launch_bounds__(256) void de_select(DeDev d, DeConst c)
 // drawn slot, the later index wins) and the success-history / adaptive-mean update.
 // one workgroup of 1024 threads per population
 // ---------------------------------------------------------------------------
+// (not block_sum<NW>: the number of wavefronts is the launch's, and the sum starts from 0.)
 __device__ inline double block_sum_1024(double v, double *scratch)
 {
     const int tid = threadIdx.x;
@@ -698,7 +686,7 @@ __global__ __launch_bounds__(1024) void de_bookkeep(DeDev d, DeConst c)
 {
     const int p = blockIdx.x;
     DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ int wave_tot[16];
     __shared__ int carry;
     __shared__ double scratch[16];
@@ -826,7 +814,7 @@ __global__ __launch_bounds__(1024) void sansde_bookkeep(DeDev d, DeConst c)
 {
     const int p = blockIdx.x;
     DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double scratch[16];
     const int tid = threadIdx.x, T = blockDim.x;
     const int np = sc->np;
@@ -893,7 +881,7 @@ __global__ __launch_bounds__(256) void de_archive_copy(DeDev d, DeConst c)
 {
     const int p = blockIdx.y;
     const DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc) || !c.archive) return;
+    if (pop_frozen(c, sc) || !c.archive) return;
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = blockIdx.x * 16 + r;
     if (i >= sc->np) return;
@@ -914,7 +902,7 @@ __global__ __launch_bounds__(1024) void de_finish(DeDev d, DeConst c)
 {
     const int p = blockIdx.x;
     DeScal *sc = d.scal + p;
-    if (de_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double scratch[16];
     __shared__ int sh_idx;
     const int tid = threadIdx.x, T = blockDim.x;

@@ -63,11 +63,7 @@ void DsaEngine::init(int n, const double *lower, const double *upper, const doub
     c.seed = params_.seed;
     c.force_method = c.force_map = -1;
     c.mcap = round_up((int) std::ceil(0.3 * n) + 1, 4);     // mapmax = ceil(p2 n), p2 < 0.3
-    {
-        int bits = 1;
-        while ((1u << bits) < (unsigned) c.np) bits++;
-        c.kb = (bits + 1) / 2;
-    }
+    c.kb = shuffle_key_bits(c.np);
 
     const size_t rows = (size_t) P * c.np, ld = c.ld;
     X0_.alloc(rows * ld);
@@ -117,21 +113,10 @@ void DsaEngine::init(int n, const double *lower, const double *upper, const doub
 }
 
 // host objective: the pool (init) or the trials of this generation, in row order like the
-// reference's loop, so that the callable is called exactly `fev` times
+// reference's loop
 void DsaEngine::host_evaluate(bool init)
 {
-    const DsaConst &c = c_;
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<DsaScal> sc(c.npop);
-    scal_.download(sc.data(), c.npop);
-    std::vector<double> xh((size_t) c.np * c.ld), fh(c.np);
-    for (int p = 0; p < c.npop; p++) {
-        if (c.honor_stop && sc[p].stop) continue;
-        (init ? X0_ : T_).download(xh.data(), xh.size(), (size_t) p * c.np * c.ld);
-        obj_.eval_host(xh.data(), c.np, c.n, c.ld, fh.data());
-        nan_to_inf(fh.data(), c.np);
-        (init ? f_ : ftrial_).upload(fh.data(), c.np, (size_t) p * c.np);
-    }
+    host_evaluate_rows(init ? X0_ : T_, init ? f_ : ftrial_, c_.np, c_.n, c_.ld, c_.honor_stop);
 }
 
 void DsaEngine::generation(bool honor_stop)
@@ -168,11 +153,7 @@ void DsaEngine::solution(int population, double *x_out, int *n_evals, int *conve
     enter_population("solution()", population);
     DsaScal s;
     scal_.download(&s, 1, population);
-    std::vector<double> x(c_.ld);
-    bestx_.download(x.data(), c_.ld, (size_t) population * c_.ld);
-    std::copy(x.begin(), x.begin() + c_.n, x_out);
-    *n_evals = s.fev;
-    *converged = s.conv;
+    report_solution(s, bestx_, (size_t) population * c_.ld, c_.n, c_.ld, x_out, n_evals, converged);
 }
 
 // the buffers of "record_draws": the draws, the maps and the trial rows of a generation
@@ -193,57 +174,27 @@ int DsaEngine::get(const std::string &k, int p, double *out, int cap)
     DsaScal s;
     scal_.download(&s, 1, p);
     const size_t pb = (size_t) p * c.np;
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
-    auto ints = [&](const DevBuf<int> &b, size_t off, int cnt) {
-        if (out && cap >= cnt) {
-            std::vector<int> v(cnt);
-            b.download(v.data(), cnt, off);
-            for (int i = 0; i < cnt; i++) out[i] = v[i];
-        }
-        return cnt;
-    };
-    auto rows = [&](const DevBuf<double> &b) {        // [np][ld] -> [np][n]
-        const int cnt = c.np * c.n;
-        if (out && cap >= cnt) {
-            std::vector<double> M((size_t) c.np * c.ld);
-            b.download(M.data(), M.size(), pb * c.ld);
-            for (int i = 0; i < c.np; i++)
-                std::copy(M.begin() + (size_t) i * c.ld, M.begin() + (size_t) i * c.ld + c.n,
-                        out + (size_t) i * c.n);
-        }
-        return cnt;
-    };
-    auto vec = [&](const DevBuf<double> &b, size_t off, int cnt) {
-        if (out && cap >= cnt) b.download(out, cnt, off);
-        return cnt;
-    };
-    auto four = [&](const double *v) {
-        if (out && cap >= 4) std::copy(v, v + 4, out);
-        return 4;
-    };
+    const StateOut o { out, cap };
     if (k == "profile") return profile_report(out, cap);
-    if (k == "X") return rows(s.cur ? X1_ : X0_);
-    if (k == "f") return vec(f_, pb, c.np);
-    if (k == "p") return four(s.p);
-    if (k == "w") return four(s.w);
-    if (k == "bestx") return vec(bestx_, (size_t) p * c.ld, c.n);
+    if (k == "X") return o.rows(s.cur ? X1_ : X0_, pb, c.np, c.n, c.ld);
+    if (k == "f") return o.vec(f_, pb, c.np);
+    if (k == "p") return o.copy(s.p, 4);
+    if (k == "w") return o.copy(s.w, 4);
+    if (k == "bestx") return o.vec(bestx_, (size_t) p * c.ld, c.n);
     if (k == "scalars" || k == "dirdraws" || k == "dirrow" || k == "mapdraws" || k == "map"
             || k == "bounddraws" || k == "trial" || k == "ftrial" || k == "nsucc") {
-        if (!c.record) throw Error(BBO_ERR_STATE, "'" + k + "' needs record_draws");
-        if (k == "trial") return rows(T_);
-        if (k == "ftrial") return vec(ftrial_, pb, c.np);
-        if (k == "nsucc") return one(s.nsucc);
-        if (k == "dirrow") return ints(dirrow_, pb, c.np);
-        if (k == "map") return ints(map_, pb * c.n, c.np * c.n);
-        if (k == "dirdraws") return vec(dirdraws_, pb * 2, c.np * 2);
-        if (k == "mapdraws") return vec(mapdraws_, pb * (c.n + 2 + c.mcap), c.np * (c.n + 2 + c.mcap));
-        if (k == "bounddraws") return vec(bounddraws_, pb * c.n * 2, c.np * c.n * 2);
+        require_record(c.record, k);
+        if (k == "trial") return o.rows(T_, pb, c.np, c.n, c.ld);
+        if (k == "ftrial") return o.vec(ftrial_, pb, c.np);
+        if (k == "nsucc") return o.one(s.nsucc);
+        if (k == "dirrow") return o.ints(dirrow_, pb, c.np);
+        if (k == "map") return o.ints(map_, pb * c.n, c.np * c.n);
+        if (k == "dirdraws") return o.vec(dirdraws_, pb * 2, c.np * 2);
+        if (k == "mapdraws") return o.vec(mapdraws_, pb * (c.n + 2 + c.mcap), c.np * (c.n + 2 + c.mcap));
+        if (k == "bounddraws") return o.vec(bounddraws_, pb * c.n * 2, c.np * c.n * 2);
         // the raw uniforms behind p1, p2, the method, the coin, the strategy and R; then what
         // was decided: p1, p2, method, strategy, mapmax, R
-        if (out && cap >= N_SCALARS) {
+        if (o.fits(N_SCALARS)) {
             std::copy(s.raw, s.raw + 6, out);
             out[6] = s.p1;
             out[7] = s.p2;
@@ -254,20 +205,20 @@ int DsaEngine::get(const std::string &k, int p, double *out, int cap)
         }
         return N_SCALARS;
     }
-    if (k == "record_draws") return one(c.record);
-    if (k == "force_method") return one(c.force_method);
-    if (k == "force_map") return one(c.force_map);
-    if (k == "mcap") return one(c.mcap);
-    if (k == "it") return one(s.it);
-    if (k == "fev") return one(s.fev);
-    if (k == "gen") return one(s.gen);
-    if (k == "stop") return one(s.stop);
-    if (k == "conv") return one(s.conv);
-    if (k == "m2") return one(s.m2);
-    if (k == "np") return one(c.np);
-    if (k == "n") return one(c.n);
-    if (k == "gamma") return one(c.gamma);
-    if (k == "fbest") return one(s.fbest);
+    if (k == "record_draws") return o.one(c.record);
+    if (k == "force_method") return o.one(c.force_method);
+    if (k == "force_map") return o.one(c.force_map);
+    if (k == "mcap") return o.one(c.mcap);
+    if (k == "it") return o.one(s.it);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "gen") return o.one(s.gen);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "conv") return o.one(s.conv);
+    if (k == "m2") return o.one(s.m2);
+    if (k == "np") return o.one(c.np);
+    if (k == "n") return o.one(c.n);
+    if (k == "gamma") return o.one(c.gamma);
+    if (k == "fbest") return o.one(s.fbest);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 
@@ -299,18 +250,7 @@ int DsaEngine::set(const std::string &k, int p, const double *in, int count)
     scal_.download(&s, 1, p);
     if (k == "X") {             // the radii follow, f does not
         BBO_REQUIRE(count == c.np * c.n, "X: np * n values");
-        std::vector<double> M((size_t) c.np * c.ld, 0.), rad(c.np);
-        for (int i = 0; i < c.np; i++) {
-            double ssq = 0.;
-            for (int j = 0; j < c.n; j++) {
-                const double v = in[(size_t) i * c.n + j];
-                M[(size_t) i * c.ld + j] = v;
-                ssq += v * v;
-            }
-            rad[i] = std::sqrt(ssq);
-        }
-        (s.cur ? X1_ : X0_).upload(M.data(), M.size(), pb * c.ld);
-        radius_.upload(rad.data(), c.np, pb);
+        upload_rows(s.cur ? X1_ : X0_, pb, c.np, c.n, c.ld, in, &radius_);
         return count;
     }
     if (k == "f") {

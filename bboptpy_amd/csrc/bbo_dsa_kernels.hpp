@@ -27,17 +27,6 @@ namespace bbo {
 enum { DSA_CTRL_P = 0, DSA_CTRL_METHOD = 1, DSA_CTRL_MAP = 2 };
 enum { DSA_MAP_RANDOM1 = 0, DSA_MAP_DIFFERENTIAL = 1, DSA_MAP_RANDOM2 = 2 };
 
-__device__ inline bool dsa_frozen(const DsaConst &c, const DsaScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
-__device__ inline void dsa_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // The method index of this generation (ds.cpp:94-101) and the two uniforms of its Philox call.
 // `adapt`: std::discrete_distribution over p -- probabilities p[i] / sum, their running sums, the
 // first one above u (the last counts as 1).  Else uniform in 0..3.  A function of (generation,
@@ -57,20 +46,6 @@ __device__ inline int dsa_method(const DsaConst &c, const DsaScal *sc, int p, do
         m = (int) (u * 4.);
     }
     return c.force_method >= 0 ? c.force_method : m;
-}
-
-// (f, row) of the first minimum in row order over a wavefront
-__device__ inline void dsa_wave_argmin(double &v, int &s)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int os = __shfl_xor(s, off, 64);
-        if (ov < v || (ov == v && os < s)) {
-            v = ov;
-            s = os;
-        }
-    }
 }
 
 // genPop, ds.cpp:294-302: a wavefront per member.  grid (ceil(np / 4), P), 256 threads, LDS
@@ -94,7 +69,7 @@ __global__ __launch_bounds__(256) void dsa_init(DsaDev d, DsaConst c)
         row[j] = v;
         ssq += v * v;
     }
-    dsa_wave_sync();
+    wave_sync();
     ssq = group_sum<64>(ssq);
     double f = DSA_INF;
     if (c.obj >= 0) {
@@ -114,7 +89,7 @@ __global__ __launch_bounds__(256) void dsa_rank(DsaDev d, DsaConst c)
 {
     const int p = blockIdx.y;
     const DsaScal *sc = d.scal + p;
-    if (dsa_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     double u, ucoin;
     const int m = dsa_method(c, sc, p, u, ucoin);
     if (m != 1 && m != 2) return;
@@ -133,7 +108,7 @@ __global__ __launch_bounds__(256) void dsa_plan(DsaDev d, DsaConst c)
 #pragma clang fp contract(off)
     const int p = blockIdx.x;
     DsaScal *sc = d.scal + p;
-    if (dsa_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ int s_method;
     __shared__ double smin[4];
     __shared__ int srow[4];
@@ -220,7 +195,7 @@ __global__ __launch_bounds__(256) void dsa_plan(DsaDev d, DsaConst c)
                 rmin = i;
             }
         }
-        dsa_wave_argmin(fmin, rmin);
+        wave_argmin(fmin, rmin);
         if (lane == 0) {
             smin[wave] = fmin;
             srow[wave] = rmin;
@@ -255,7 +230,7 @@ __global__ __launch_bounds__(256) void dsa_evolve(DsaDev d, DsaConst c)
 #pragma clang fp contract(off)
     const int p = blockIdx.y;
     const DsaScal *sc = d.scal + p;
-    if (dsa_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wave, n = c.n, ld = c.ld;
@@ -284,7 +259,7 @@ __global__ __launch_bounds__(256) void dsa_evolve(DsaDev d, DsaConst c)
     }
     if (strategy == DSA_MAP_RANDOM2) {
         for (int j = lane; j < n; j += 64) trial[j] = 0.;
-        dsa_wave_sync();
+        wave_sync();
         for (int q = lane; 4 * q < mapmax; q += 64) {
             const u32x4 w = philox4x32_10(c.seed, (uint32_t) i, (uint32_t) (1 + q), gen, swm);
             const uint32_t ws[4] = { w.x, w.y, w.z, w.w };
@@ -297,7 +272,7 @@ __global__ __launch_bounds__(256) void dsa_evolve(DsaDev d, DsaConst c)
                 }
             }
         }
-        dsa_wave_sync();
+        wave_sync();
     }
     double ssq = 0.;
     for (int j = lane; j < n; j += 64) {
@@ -322,7 +297,7 @@ __global__ __launch_bounds__(256) void dsa_evolve(DsaDev d, DsaConst c)
         ssq += t * t;
     }
     if (c.obj < 0) return;      // a host objective: dsa_select finishes the member
-    dsa_wave_sync();
+    wave_sync();
     ssq = group_sum<64>(ssq);
     double ft = eval_row_group<64>(c.obj, n, trial, d.aux, lane);
     if (ft != ft) ft = DSA_INF;
@@ -344,7 +319,7 @@ __global__ __launch_bounds__(256) void dsa_select(DsaDev d, DsaConst c)
 {
     const int p = blockIdx.y;
     const DsaScal *sc = d.scal + p;
-    if (dsa_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wave, n = c.n, ld = c.ld, cur = sc->cur;
     if (i >= c.np) return;
@@ -378,7 +353,7 @@ __global__ __launch_bounds__(256) void dsa_finish(DsaDev d, DsaConst c, int init
 #pragma clang fp contract(off)
     const int p = blockIdx.x;
     DsaScal *sc = d.scal + p;
-    if (dsa_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double smin[4], smax[4], ssum[4];
     __shared__ int srow[4], scnt[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, np = c.np;
@@ -396,7 +371,7 @@ __global__ __launch_bounds__(256) void dsa_finish(DsaDev d, DsaConst c, int init
         rsum += d.radius[pb + i];
         if (!init_only) cnt += d.acc[pb + i];
     }
-    dsa_wave_argmin(fmin, rmin);
+    wave_argmin(fmin, rmin);
     rsum = group_sum<64>(rsum);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {

@@ -2123,7 +2123,7 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
     if (lane < 20) {
         dv[lane - 2] = 0.; ev[lane - 2] = 0.; uv[lane - 2] = 0.; wv[lane - 2] = 0.; hv[lane - 2] = 0.;
     }
-    dc_wave_sync();
+    wave_sync();
     // ---- Householder tridiagonalisation (cmaes.cpp:285-381; reflectors left unscaled) --------
     for (int i = n - 1; i > 0; i--) {
         const double dk = lane < i ? A[i * EIGS_LD + lane] : 0.;
@@ -2134,7 +2134,7 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
                 ev[i] = f;
                 hv[i] = 0.;
             }
-            dc_wave_sync();
+            wave_sync();
             continue;
         }
         double g = sqrt(h0);
@@ -2142,7 +2142,7 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
         const double h = h0 - f * g;
         if (lane < 16) uv[lane] = lane < i ? (lane == i - 1 ? f - g : dk) : 0.;
         if (lane == 0) ev[i] = g;
-        dc_wave_sync();
+        wave_sync();
         // p = A u / h over the block [0, i)^2, w = p - (u^T p / 2h) u
         double acc = 0.;
         if (j < i)
@@ -2152,26 +2152,26 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
         const double pj = acc / h;
         const double hh = eig_wave_sum((lane < 16 && lane < i) ? pj * uv[lane] : 0.) / (h + h);
         if (lane < 16) wv[lane] = lane < i ? pj - hh * uv[lane] : 0.;
-        dc_wave_sync();
+        wave_sync();
         if (j < i) {
             const double uj = uv[j], wj = wv[j];
             for (int k = q; k < i; k += 4)
                 A[j * EIGS_LD + k] -= uj * wv[k] + wj * uv[k];
         }
-        dc_wave_sync();
+        wave_sync();
         if (lane < i) A[i * EIGS_LD + lane] = uv[lane];        // stash: row i = u_i
         if (lane == 0) hv[i] = h;
-        dc_wave_sync();
+        wave_sync();
     }
     if (lane < 16) td[lane] = lane < n ? A[lane * EIGS_LD + lane] : 0.;
-    dc_wave_sync();
+    wave_sync();
     // tql2's prologue: the sub-diagonal shifted down (cmaes.cpp:384-387)
     {
         const double t = (lane + 1 < n && lane < 16) ? ev[lane + 1] : 0.;
-        dc_wave_sync();
+        wave_sync();
         if (lane < 16) ev[lane] = t;
     }
-    dc_wave_sync();
+    wave_sync();
     // ---- the reference's implicit QL on (td, ev) ----------------------------------------------
     DcMat Qm { Qs, EIGS_LD };
     if (d.stamps && lane == 0) d.stamps[26] = wall_clock64();
@@ -2187,11 +2187,11 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
             acc += __shfl_xor(acc, 16, 64);
             acc += __shfl_xor(acc, 32, 64);
             const double gq = -(acc / h);
-            dc_wave_sync();
+            wave_sync();
             if (j < n)
                 for (int k = q; k < i; k += 4)
                     Qs[k * EIGS_LD + j] = fma(gq, A[i * EIGS_LD + k], Qs[k * EIGS_LD + j]);
-            dc_wave_sync();
+            wave_sync();
         }
     }
     // ---- ascending order (cmaes.cpp:459-477), repair (:250-266), sqrt (:269-271) ----------------
@@ -2205,26 +2205,26 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
         perm[lane] = r;
         gv[r] = dj;
     }
-    dc_wave_sync();
+    wave_sync();
     const double lo = gv[0], hi = gv[n - 1];
-    dc_wave_sync();
+    wave_sync();
     if (lo <= 0.) {
         const double shift = fmax(hi, 0.) / 1e14;
         if (lane < n) {
             gv[lane] = fmax(gv[lane], 0.) + shift;
             C[(size_t) lane * ld + lane] += shift;
         }
-        dc_wave_sync();
+        wave_sync();
     }
     const double lo2 = gv[0], hi2 = gv[n - 1];
-    dc_wave_sync();
+    wave_sync();
     if (hi2 > 1e14 * lo2) {
         const double shift = hi2 / 1e14 - lo2;
         if (lane < n) {
             gv[lane] += shift;
             C[(size_t) lane * ld + lane] += shift;
         }
-        dc_wave_sync();
+        wave_sync();
     }
     double *Dp = d.D + (size_t) p * ld;
     double *Bp = d.B + (size_t) p * ld * ld;
@@ -2242,13 +2242,13 @@ __device__ __forceinline__ void eigen_small_body(const CmaDev &d, const CmaConst
     // term by term in the reference's order (cmaes.cpp:274-282), the packed MFMA operands of the
     // sampler (B D) and of the whitening GEMM (C^-1/2); ld = 16 here.  B in sorted column order
     // goes to the work matrix (the reflectors are spent), D to dv.
-    dc_wave_sync();
+    wave_sync();
     for (int x = lane; x < 16 * 16; x += 64) {
         const int k = x >> 4, jj = x & 15;
         if (k < n && jj < n) A[k * EIGS_LD + perm[jj]] = Qs[k * EIGS_LD + jj];
     }
     if (lane < 16) dv[lane] = lane < n ? sqrt(gv[lane]) : 1.;
-    dc_wave_sync();
+    wave_sync();
     double *isc = d.isc + (size_t) p * ld * ld;
     double *ISp = d.ISp + (size_t) p * ld * ld, *BDp = d.BDp + (size_t) p * ld * ld;
     const int KS = ld >> 2;

@@ -42,12 +42,6 @@ struct DcMat {
     __device__ double& operator()(int i, int j) const { return a[(size_t) i * ld + j]; }
 };
 
-__device__ inline void dc_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // the synchronisation of a team inside a merge: a team of ONE wavefront (the lowest merge level:
 // 16-pole merges of 8 x 8 leaves, a wavefront each) only has to order its own LDS traffic -- its
 // ~25 phase boundaries cost a wavefront fence each instead of a workgroup barrier that waits for
@@ -55,7 +49,7 @@ __device__ inline void dc_wave_sync()
 // workgroup (all teams of a level have the same number of wavefronts).
 __device__ inline void dc_sync(bool wv)
 {
-    if (wv) dc_wave_sync();
+    if (wv) wave_sync();
     else __syncthreads();
 }
 
@@ -205,7 +199,7 @@ struct DcWork {
 };
 
 // (wavefront stage on the cross-lane data path, eig_wave_sum / dc_wave_max: six ds_bpermute round
-// trips through the LDS crossbar before)
+// trips through the LDS crossbar before; a maximum, and no index: not wave_argmax)
 __device__ inline double dc_wave_max(double v)
 {
     v = fmax(v, eig_dpp<0x128>(v));   // row_ror:8
@@ -1102,7 +1096,7 @@ __device__ inline void dc_leaf_ql(const DcMat &Q, int a, int s, const double *dv
         const int r = q / s, c = q - r * s;
         Q(a + r, a + c) = r == c ? 1. : 0.;
     }
-    dc_wave_sync();
+    wave_sync();
     EigMat blk { &Q(a, a), Q.ld };
     QlState st { 0, 0, 1, 0, 0., 0., 0 };
     // QL has no iteration limit in the reference; ql_produce_reg<true> stops after 30 sweeps per
@@ -1111,7 +1105,7 @@ __device__ inline void dc_leaf_ql(const DcMat &Q, int a, int s, const double *dv
     const int sweeps = ql_produce_reg<true>(st, s, d, e, rot, desc, 64, lane, blk);
     if (dbgout && lane == 0) dbgout[0] = sweeps;
     if (lane < s) dv_out[a + lane] = d;
-    dc_wave_sync();
+    wave_sync();
 }
 
 // two leaves by one wavefront, one in each 32-lane half (ql_leaf_pair): blocks [a0, a0 + s0) and
@@ -1127,11 +1121,11 @@ __device__ inline void dc_leaf_ql_pair(const DcMat &Q, int a0, int s0, int a1, i
         const int r = q / s, c = q - r * s;
         Q(a + r, a + c) = r == c ? 1. : 0.;
     }
-    dc_wave_sync();
+    wave_sync();
     double *zrow = &Q(a + (hl < s ? hl : 0), a);
     ql_leaf_pair(s, d, e, zrow, lane);
     if (hl < s) dv_out[a + hl] = d;
-    dc_wave_sync();
+    wave_sync();
 }
 
 // T factors of the reflector panels (see dc_apply_reflectors): T_b for panel b = reflectors
@@ -1179,7 +1173,7 @@ __device__ __forceinline__ void dc_build_T(int n, const double *V, const double 
         }
 #pragma unroll
         for (int r = 0; r < 4; r++) Sb[(fk + 4 * r) * LS + fr] = acc[r];    // S = V_b^T V_b
-        dc_wave_sync();
+        wave_sync();
         if (lane < 16) {
             double t[16];
 #pragma unroll
@@ -1193,7 +1187,7 @@ __device__ __forceinline__ void dc_build_T(int n, const double *V, const double 
 #pragma unroll
             for (int i = 0; i < 16; i++) Tg[(size_t) b * 256 + lane * 16 + i] = t[i];
         }
-        dc_wave_sync();
+        wave_sync();
     }
 }
 

@@ -281,7 +281,7 @@ __device__ __forceinline__ void tred_mw_body(const CmaDev &d, const CmaConst &c,
     reflector(na - 1, av, f, gg, h, rh, none, uvv);
 #pragma unroll
     for (int v = 0; v < NV; v++) ub[lane + 64 * v] = uvv[v];
-    dc_wave_sync();
+    wave_sync();
 
     for (int i = na - 1; i >= istop && !failed; i--) {
         const unsigned long long epoch = launch * 1024ull + (unsigned long long) (na - i);
@@ -309,7 +309,7 @@ __device__ __forceinline__ void tred_mw_body(const CmaDev &d, const CmaConst &c,
 #pragma unroll
                 for (int t = 0; t < NT; t++) *reinterpret_cast<double2*>(&wb[16 * t + 2 * s]) = a2[t];
             }
-            dc_wave_sync();
+            wave_sync();
 #pragma unroll
             for (int v = 0; v < NV; v++) mw_store_d(rbuf + NMAX * par + lane + 64 * v, wb[lane + 64 * v]);
         }
@@ -373,7 +373,7 @@ __device__ __forceinline__ void tred_mw_body(const CmaDev &d, const CmaConst &c,
             wvv[v] = idx < i ? ev_[v] - hh * uvv[v] : 0.;
             wb[idx] = wvv[v];
         }
-        dc_wave_sync();
+        wave_sync();
         // ---- the next pivot row, by every wavefront: row' = row - u_{i-1} w - w_{i-1} u ------------
         const double um = none ? 0. : f - gg, wm = mw_entry(wvv, i - 1);
         double an[NV];
@@ -422,7 +422,7 @@ __device__ __forceinline__ void tred_mw_body(const CmaDev &d, const CmaConst &c,
             uvv[v] = u2[v];
             ub[lane + 64 * v] = u2[v];
         }
-        dc_wave_sync();
+        wave_sync();
         MW_CK(5);
     }
 #ifdef BBO_MW_CLOCKS

@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "bbo_wave.hpp"
+
 namespace bbo {
 
 constexpr int EIG_MAXSEQ = 64;
@@ -47,6 +49,7 @@ __device__ inline double eig_readlane(double v, int l)
     return __hiloint2double(hi, lo);
 }
 
+// (not group_sum<64>: DPP rotations inside a 16-lane row, then the four rows left to right)
 __device__ inline double eig_wave_sum(double v)
 {
     v += eig_dpp<0x128>(v);   // row_ror:8
@@ -87,12 +90,7 @@ __device__ inline double eig_wave_sum_bf(double v)
 // the diagonal and search for the split).  The hardware keeps a wavefront's LDS operations in
 // order, but the COMPILER reasons per thread: on the path that skips the `if (lane == 0)` block
 // it may hoist a later load above the block and so read what lane 0 is about to overwrite.
-// Every hand-over point therefore carries a wavefront-scope fence.
-__device__ inline void ql_wave_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+// Every hand-over point therefore carries a wavefront-scope fence: wave_sync (bbo_wave.hpp).
 
 // reciprocal and reciprocal root from the hardware estimates + Newton corrections (full fp64 to
 // a rounding error).  The sweep's shift and its closing quotient sit on the serial path of the
@@ -131,7 +129,7 @@ __device__ inline int ql_produce(QlState &st, int n, double *dv, double *ev, dou
     const double eps = 0x1.0p-52;
     int count = 0, ns = 0;
     while (!st.done) {
-        ql_wave_fence();
+        wave_sync();
         if (st.need_m) {
             const double dl = dv[st.l], el = ev[st.l];
             st.tst1 = fmax(st.tst1, fabs(dl) + fabs(el));
@@ -181,10 +179,10 @@ __device__ inline int ql_produce(QlState &st, int n, double *dv, double *ev, dou
         const double dl_new = el * ql_rcp(p0 + r0);
         const double dl1 = el * (p0 + r0);
         const double h0 = g0 - dl_new;
-        ql_wave_fence();
+        wave_sync();
         for (int i = l + 2 + lane; i < n; i += 64) dv[i] -= h0;
         st.f += h0;
-        ql_wave_fence();
+        wave_sync();
 
         if (lane == 0) {
             dv[l] = dl_new;
@@ -222,7 +220,7 @@ __device__ inline int ql_produce(QlState &st, int n, double *dv, double *ev, dou
             ev[l] = s * pp;
             dv[l] = cth * pp;
         }
-        ql_wave_fence();
+        wave_sync();
         desc[3 * ns + 0] = l;
         desc[3 * ns + 1] = m;
         desc[3 * ns + 2] = count;

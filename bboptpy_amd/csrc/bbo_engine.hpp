@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <limits>
 
 namespace bbo {
@@ -34,7 +35,112 @@ inline int radius_spread_converged(const DevBuf<double> &radius, size_t off, int
     return m2 <= (np - 1) * tol * tol ? 1 : 0;
 }
 
-// Scal: the engine's per-population scalars; the base reads its `stop` and `fev`.
+// Where get() puts the values of a key: every member returns the key's count and writes only when
+// the caller's buffer takes all of it (a call with out == nullptr asks for the count).
+struct StateOut {
+    double *out;
+    int cap;
+
+    bool fits(int cnt) const { return out && cap >= cnt; }
+    int one(double v) const
+    {
+        if (fits(1)) out[0] = v;
+        return 1;
+    }
+    int copy(const double *v, int cnt) const
+    {
+        if (fits(cnt)) std::copy(v, v + cnt, out);
+        return cnt;
+    }
+    int vec(const DevBuf<double> &b, size_t off, int cnt) const
+    {
+        if (fits(cnt) && cnt > 0) b.download(out, cnt, off);
+        return cnt;
+    }
+    int ints(const DevBuf<int> &b, size_t off, int cnt) const
+    {
+        if (fits(cnt) && cnt > 0) {
+            std::vector<int> v(cnt);
+            b.download(v.data(), cnt, off);
+            std::copy(v.begin(), v.end(), out);
+        }
+        return cnt;
+    }
+    // [np][ld] -> [np][n]: np rows of a matrix with leading dimension ld, from its row `row0` on
+    int rows(const DevBuf<double> &b, size_t row0, int np, int n, int ld) const
+    {
+        const int cnt = np * n;
+        if (fits(cnt) && cnt > 0) {
+            std::vector<double> M((size_t) np * ld);
+            b.download(M.data(), M.size(), row0 * ld);
+            for (int i = 0; i < np; i++)
+                std::copy(M.begin() + (size_t) i * ld, M.begin() + (size_t) i * ld + n, out + (size_t) i * n);
+        }
+        return cnt;
+    }
+    // the same in another order: place i takes row order[row0 + i] of the `nrows` rows from row0 on
+    int rows_by_slot(const DevBuf<double> &b, const DevBuf<int> &order, size_t row0, int nslots, int nrows,
+            int n, int ld) const
+    {
+        const int cnt = nslots * n;
+        if (fits(cnt)) {
+            std::vector<int> ord(nslots);
+            order.download(ord.data(), nslots, row0);
+            std::vector<double> M((size_t) nrows * ld);
+            b.download(M.data(), M.size(), row0 * ld);
+            for (int i = 0; i < nslots; i++)
+                std::copy(M.begin() + (size_t) ord[i] * ld, M.begin() + (size_t) ord[i] * ld + n,
+                        out + (size_t) i * n);
+        }
+        return cnt;
+    }
+    int vec_by_slot(const DevBuf<double> &b, const DevBuf<int> &order, size_t row0, int nslots, int nrows) const
+    {
+        if (fits(nslots)) {
+            std::vector<int> ord(nslots);
+            order.download(ord.data(), nslots, row0);
+            std::vector<double> v(nrows);
+            b.download(v.data(), nrows, row0);
+            for (int i = 0; i < nslots; i++) out[i] = v[ord[i]];
+        }
+        return nslots;
+    }
+};
+
+// set() of a row matrix, [np][n] -> [np][ld] from row `row0` on (the padding columns zero); with
+// `radius`, the rows' Euclidean norms go to radius[row0, row0 + np)
+inline void upload_rows(DevBuf<double> &b, size_t row0, int np, int n, int ld, const double *in,
+        DevBuf<double> *radius = nullptr)
+{
+    std::vector<double> M((size_t) np * ld, 0.), rad(np);
+    for (int i = 0; i < np; i++) {
+        double ssq = 0.;
+        for (int j = 0; j < n; j++) {
+            const double v = in[(size_t) i * n + j];
+            M[(size_t) i * ld + j] = v;
+            ssq += v * v;
+        }
+        rad[i] = std::sqrt(ssq);
+    }
+    b.upload(M.data(), M.size(), row0 * ld);
+    if (radius) radius->upload(rad.data(), np, row0);
+}
+
+// the key width of the slot shuffle (cso_perm): half the bits of np, rounded up
+inline int shuffle_key_bits(int np)
+{
+    int bits = 1;
+    while ((1u << bits) < (unsigned) np) bits++;
+    return (bits + 1) / 2;
+}
+
+// the keys that exist only while the draws of a generation are recorded
+inline void require_record(bool record, const std::string &k)
+{
+    if (!record) throw Error(BBO_ERR_STATE, "'" + k + "' needs record_draws");
+}
+
+// Scal: the engine's per-population scalars; the base reads its `stop`, `fev` and `conv`.
 template<class Scal>
 class Engine: public Optimizer {
 public:
@@ -189,6 +295,54 @@ protected:
         lower_.upload(lower_h_.data(), ld);
         upper_.upload(upper_h_.data(), ld);
         aux_.upload(aux_h_.data(), ld);
+    }
+
+    // solution(): the row at b[off, off + n), the evaluations and the stop rule's verdict
+    void report_solution(const Scal &s, const DevBuf<double> &b, size_t off, int n, int ld, double *x_out,
+            int *n_evals, int *converged) const
+    {
+        std::vector<double> x(ld);
+        b.download(x.data(), ld, off);
+        std::copy(x.begin(), x.begin() + n, x_out);
+        *n_evals = s.fev;
+        *converged = s.conv;
+    }
+
+    // A host objective over the rows of src ([P][np][ld]), the values to dst ([P][np]); a stopped
+    // population is left out under honor_stop.  Without `order` a population is one call of
+    // eval_host in row order; with it (slot -> row) the rows are evaluated one by one in slot
+    // order, the slots that `skip` names keeping the value dst holds.  Either way the callable is
+    // called in the reference's order and exactly `fev` times.
+    void host_evaluate_rows(const DevBuf<double> &src, DevBuf<double> &dst, int np, int n, int ld,
+            bool honor_stop, const DevBuf<int> *order = nullptr,
+            const std::function<bool(int)> &skip = nullptr)
+    {
+        BBO_HIP(hipStreamSynchronize(stream_));
+        const int P = params_.populations;
+        std::vector<Scal> sc(P);
+        scal_.download(sc.data(), P);
+        std::vector<double> xh((size_t) np * ld), fh(np);
+        std::vector<int> occ(np);
+        for (int p = 0; p < P; p++) {
+            if (honor_stop && sc[p].stop) continue;
+            src.download(xh.data(), xh.size(), (size_t) p * np * ld);
+            if (!order) {
+                obj_.eval_host(xh.data(), np, n, ld, fh.data());
+                nan_to_inf(fh.data(), np);
+            } else {
+                if (skip) dst.download(fh.data(), np, (size_t) p * np);
+                order->download(occ.data(), np, (size_t) p * np);
+                for (int s = 0; s < np; s++) {
+                    if (skip && skip(s)) continue;
+                    const int row = occ[s];
+                    double f = 0.;
+                    obj_.eval_host(xh.data() + (size_t) row * ld, 1, n, ld, &f);
+                    nan_to_inf(&f, 1);
+                    fh[row] = f;
+                }
+            }
+            dst.upload(fh.data(), np, (size_t) p * np);
+        }
     }
 
     bool all_stopped()

@@ -86,11 +86,7 @@ void JayaEngine::init(int n, const double *lower, const double *upper, const dou
     // jaya.cpp:86-89
     c.sigmau = std::pow((std::tgamma(1. + c.beta) * std::sin(c.beta * M_PI / 2.))
             / (std::tgamma((1. + c.beta) / 2.) * c.beta * std::pow(2., (c.beta - 1.) / 2.)), 1. / c.beta);
-    {
-        int bits = 1;
-        while ((1u << bits) < (unsigned) c.np) bits++;
-        c.kb = (bits + 1) / 2;
-    }
+    c.kb = shuffle_key_bits(c.np);
 
     const size_t rows = (size_t) P * c.np, ld = c.ld, sub = (size_t) P * c.nks;
     X_.alloc(rows * ld);
@@ -142,28 +138,10 @@ void JayaEngine::init(int n, const double *lower, const double *upper, const dou
 }
 
 // host objective: the pool (init) or the trials of this generation, in slot order like the
-// reference's loop, so that the callable is called exactly `fev` times
+// reference's loop
 void JayaEngine::host_evaluate(bool init)
 {
-    const JayaConst &c = c_;
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<JayaScal> sc(c.npop);
-    scal_.download(sc.data(), c.npop);
-    std::vector<double> xh((size_t) c.np * c.ld), fh(c.np);
-    std::vector<int> occ(c.np);
-    for (int p = 0; p < c.npop; p++) {
-        if (c.honor_stop && sc[p].stop) continue;
-        (init ? X_ : T_).download(xh.data(), xh.size(), (size_t) p * c.np * c.ld);
-        occ_.download(occ.data(), c.np, (size_t) p * c.np);
-        for (int s = 0; s < c.np; s++) {
-            const int row = occ[s];
-            double f = 0.;
-            obj_.eval_host(xh.data() + (size_t) row * c.ld, 1, c.n, c.ld, &f);
-            nan_to_inf(&f, 1);
-            fh[row] = f;
-        }
-        (init ? f_ : ftrial_).upload(fh.data(), c.np, (size_t) p * c.np);
-    }
+    host_evaluate_rows(init ? X_ : T_, init ? f_ : ftrial_, c_.np, c_.n, c_.ld, c_.honor_stop, &occ_);
 }
 
 void JayaEngine::generation(bool honor_stop)
@@ -200,11 +178,7 @@ void JayaEngine::solution(int population, double *x_out, int *n_evals, int *conv
     enter_population("solution()", population);
     JayaScal s;
     scal_.download(&s, 1, population);
-    std::vector<double> x(c_.ld);
-    bestx_.download(x.data(), c_.ld, (size_t) population * c_.ld);
-    std::copy(x.begin(), x.begin() + c_.n, x_out);
-    *n_evals = s.fev;
-    *converged = s.conv;
+    report_solution(s, bestx_, (size_t) population * c_.ld, c_.n, c_.ld, x_out, n_evals, converged);
 }
 
 // the buffers of "record_draws": the draws and the trial rows of a generation
@@ -222,68 +196,42 @@ int JayaEngine::get(const std::string &k, int p, double *out, int cap)
     JayaScal s;
     scal_.download(&s, 1, p);
     const size_t pb = (size_t) p * c.np;
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
-    auto ints = [&](const DevBuf<int> &b, size_t off, int cnt) {
-        if (out && cap >= cnt) {
-            std::vector<int> v(cnt);
-            b.download(v.data(), cnt, off);
-            for (int i = 0; i < cnt; i++) out[i] = v[i];
-        }
-        return cnt;
-    };
-    auto rows = [&](const DevBuf<double> &b) {        // [np][ld] -> [np][n], by row
-        const int cnt = c.np * c.n;
-        if (out && cap >= cnt) {
-            std::vector<double> M((size_t) c.np * c.ld);
-            b.download(M.data(), M.size(), pb * c.ld);
-            for (int i = 0; i < c.np; i++)
-                std::copy(M.begin() + (size_t) i * c.ld, M.begin() + (size_t) i * c.ld + c.n,
-                        out + (size_t) i * c.n);
-        }
-        return cnt;
-    };
-    auto vec = [&](const DevBuf<double> &b, size_t off, int cnt) {
-        if (out && cap >= cnt) b.download(out, cnt, off);
-        return cnt;
-    };
+    const StateOut o { out, cap };
     if (k == "profile") return profile_report(out, cap);
     // per-member arrays are reported by ROW; "occ" maps the reference's slots to rows
-    if (k == "X") return rows(X_);
-    if (k == "f") return vec(f_, pb, c.np);
-    if (k == "occ") return ints(occ_, pb, c.np);
-    if (k == "len") return ints(len_, (size_t) p * c.nks, c.nks);
-    if (k == "pstrat") return vec(pstrat_, (size_t) p * c.nks, c.nks);
-    if (k == "perfindex") return vec(perfindex_, (size_t) p * c.nks, c.nks);
-    if (k == "bestx") return vec(bestx_, (size_t) p * c.ld, c.n);
+    if (k == "X") return o.rows(X_, pb, c.np, c.n, c.ld);
+    if (k == "f") return o.vec(f_, pb, c.np);
+    if (k == "occ") return o.ints(occ_, pb, c.np);
+    if (k == "len") return o.ints(len_, (size_t) p * c.nks, c.nks);
+    if (k == "pstrat") return o.vec(pstrat_, (size_t) p * c.nks, c.nks);
+    if (k == "perfindex") return o.vec(perfindex_, (size_t) p * c.nks, c.nks);
+    if (k == "bestx") return o.vec(bestx_, (size_t) p * c.ld, c.n);
     if (k == "trial" || k == "draws" || k == "ftrial") {
-        if (!c.record) throw Error(BBO_ERR_STATE, "'" + k + "' needs record_draws");
-        if (k == "trial") return rows(T_);
-        if (k == "ftrial") return vec(ftrial_, pb, c.np);
+        require_record(c.record, k);
+        if (k == "trial") return o.rows(T_, pb, c.np, c.n, c.ld);
+        if (k == "ftrial") return o.vec(ftrial_, pb, c.np);
         const int cnt = c.np * c.n * c.ndraw + 1;
-        if (out && cap >= cnt) {
+        if (o.fits(cnt)) {
             draws_.download(out, cnt - 1, pb * c.n * c.ndraw);
             out[cnt - 1] = s.uroul;        // the roulette's uniform (0 without `adapt`)
         }
         return cnt;
     }
-    if (k == "record_draws") return one(c.record);
-    if (k == "k") return one(s.k);
-    if (k == "nks") return one(c.nks);
-    if (k == "xchaos") return one(s.xchaos);
-    if (k == "best") return one(s.best);
-    if (k == "pbest") return one(s.pbest);
-    if (k == "fgbest") return one(s.fgbest);
-    if (k == "sigmau") return one(c.sigmau);
-    if (k == "fev") return one(s.fev);
-    if (k == "gen") return one(s.gen);
-    if (k == "stop") return one(s.stop);
-    if (k == "conv") return one(s.conv);
-    if (k == "m2") return one(s.m2);
-    if (k == "np") return one(c.np);
-    if (k == "n") return one(c.n);
+    if (k == "record_draws") return o.one(c.record);
+    if (k == "k") return o.one(s.k);
+    if (k == "nks") return o.one(c.nks);
+    if (k == "xchaos") return o.one(s.xchaos);
+    if (k == "best") return o.one(s.best);
+    if (k == "pbest") return o.one(s.pbest);
+    if (k == "fgbest") return o.one(s.fgbest);
+    if (k == "sigmau") return o.one(c.sigmau);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "gen") return o.one(s.gen);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "conv") return o.one(s.conv);
+    if (k == "m2") return o.one(s.m2);
+    if (k == "np") return o.one(c.np);
+    if (k == "n") return o.one(c.n);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 
@@ -303,18 +251,7 @@ int JayaEngine::set(const std::string &k, int p, const double *in, int count)
     }
     if (k == "X") {             // by row; the radii follow, f does not
         BBO_REQUIRE(count == c.np * c.n, "X: np * n values");
-        std::vector<double> M((size_t) c.np * c.ld, 0.), rad(c.np);
-        for (int i = 0; i < c.np; i++) {
-            double ssq = 0.;
-            for (int j = 0; j < c.n; j++) {
-                const double v = in[(size_t) i * c.n + j];
-                M[(size_t) i * c.ld + j] = v;
-                ssq += v * v;
-            }
-            rad[i] = std::sqrt(ssq);
-        }
-        X_.upload(M.data(), M.size(), pb * c.ld);
-        radius_.upload(rad.data(), c.np, pb);
+        upload_rows(X_, pb, c.np, c.n, c.ld, in, &radius_);
         return count;
     }
     if (k == "f") {

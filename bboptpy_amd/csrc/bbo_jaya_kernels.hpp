@@ -24,17 +24,6 @@ enum { JAYA_ORIGINAL = 0, JAYA_LEVY = 1, JAYA_TENT = 2, JAYA_LOGISTIC = 3 };
 // what a draw of the control stream is for (counter word 0)
 enum { JAYA_CTRL_XCHAOS = 0, JAYA_CTRL_LEN = 1, JAYA_CTRL_ROULETTE = 2, JAYA_CTRL_REDRAW = 3 };
 
-__device__ inline bool jaya_frozen(const JayaConst &c, const JayaScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
-__device__ inline void jaya_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // the redraw guards of the chaotic maps (`while (_xchaos == 0.7) _xchaos = Random::get(0., 1.)`)
 __device__ inline double jaya_redraw(const JayaConst &c, JayaScal *sc, int p)
 {
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(256) void jaya_init_eval(JayaDev d, JayaConst c)
         row[j] = v;
         ssq += v * v;
     }
-    jaya_wave_sync();
+    wave_sync();
     ssq = group_sum<64>(ssq);
     double f = JAYA_INF;
     if (c.obj >= 0) {
@@ -127,32 +116,6 @@ __global__ __launch_bounds__(256) void jaya_init_eval(JayaDev d, JayaConst c)
     }
 }
 
-// (f, slot) of the first strict minimum / maximum in slot order over a wavefront
-__device__ inline void jaya_wave_argmin(double &v, int &s)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int os = __shfl_xor(s, off, 64);
-        if (ov < v || (ov == v && os < s)) {
-            v = ov;
-            s = os;
-        }
-    }
-}
-__device__ inline void jaya_wave_argmax(double &v, int &s)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int os = __shfl_xor(s, off, 64);
-        if (ov > v || (ov == v && os < s)) {
-            v = ov;
-            s = os;
-        }
-    }
-}
-
 // divideSubpopulation (jaya.cpp:225-239), the best and the worst member of every sub-population
 // (:148-157) and the generation's share of the chaotic chain.  One workgroup per population.
 // grid (P), 256 threads
@@ -160,7 +123,7 @@ __global__ __launch_bounds__(256) void jaya_partition(JayaDev d, JayaConst c)
 {
     const int p = blockIdx.x;
     JayaScal *sc = d.scal + p;
-    if (jaya_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int np = c.np, n = c.n, ld = c.ld, nks = c.nks, k = sc->k, gen = sc->gen;
     const size_t pb = (size_t) p * np;
@@ -215,8 +178,8 @@ __global__ __launch_bounds__(256) void jaya_partition(JayaDev d, JayaConst c)
                 smax = s;
             }
         }
-        jaya_wave_argmin(fmin, smin);
-        jaya_wave_argmax(fmax, smax);
+        wave_argmin(fmin, smin);
+        wave_argmax(fmax, smax);
         if (lane == 0) {
             bwrow[2 * q] = occ[min(smin, np - 1)];
             bwrow[2 * q + 1] = occ[min(smax, np - 1)];
@@ -242,7 +205,7 @@ __global__ __launch_bounds__(256) void jaya_evolve(JayaDev d, JayaConst c)
 #pragma clang fp contract(off)
     const int p = blockIdx.y;
     const JayaScal *sc = d.scal + p;
-    if (jaya_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = blockIdx.x * 4 + wave, n = c.n, ld = c.ld, nks = c.nks;
@@ -303,7 +266,7 @@ __global__ __launch_bounds__(256) void jaya_evolve(JayaDev d, JayaConst c)
         ssq += t * t;
     }
     if (c.obj < 0) return;      // a host objective: jaya_select finishes the member
-    jaya_wave_sync();
+    wave_sync();
     ssq = group_sum<64>(ssq);
     double ft = eval_row_group<64>(c.obj, n, trial, d.aux, lane);
     if (ft != ft) ft = JAYA_INF;
@@ -323,7 +286,7 @@ __global__ __launch_bounds__(256) void jaya_evolve(JayaDev d, JayaConst c)
 __global__ __launch_bounds__(256) void jaya_select(JayaDev d, JayaConst c)
 {
     const int p = blockIdx.y;
-    if (jaya_frozen(c, d.scal + p)) return;
+    if (pop_frozen(c, d.scal + p)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave, n = c.n, ld = c.ld;
     if (row >= c.np) return;
@@ -356,7 +319,7 @@ __global__ __launch_bounds__(256) void jaya_finish(JayaDev d, JayaConst c, int i
 {
     const int p = blockIdx.x;
     JayaScal *sc = d.scal + p;
-    if (jaya_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double smin[4], ssum[4];
     __shared__ int srow[4];
     __shared__ int take;
@@ -372,7 +335,7 @@ __global__ __launch_bounds__(256) void jaya_finish(JayaDev d, JayaConst c, int i
         }
         rsum += d.radius[pb + i];
     }
-    jaya_wave_argmin(fmin, rmin);
+    wave_argmin(fmin, rmin);
     rsum = group_sum<64>(rsum);
     if (lane == 0) {
         smin[wave] = fmin;

@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "bbo_wave.hpp"
+
 namespace bbo {
 
 enum Objective : int {
@@ -67,22 +69,6 @@ __device__ inline double cos_2pi(double x)
     // k = 2 -> pi/2 + y -> -sin y ; q = 2 (k = 3): cos(pi - y) = -cos y
     const double c1 = k == 1 ? sy : -sy;
     return q == 0 ? cy : (q == 1 ? c1 : -cy);
-}
-
-template<int G>
-__device__ inline double group_sum(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
-
-template<int G>
-__device__ inline double group_prod(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v *= __shfl_xor(v, off, G);
-    return v;
 }
 
 // x: the candidate (LDS or global), n coordinates; aux: per-coordinate constants

@@ -238,15 +238,9 @@ void PsoEngine::solution(int population, double *x_out, int *n_evals, int *conve
     enter_population("solution()", population);
     PsoScal s;
     scal_.download(&s, 1, population);
-    std::vector<double> x(c_.ld);
-    xbest_.download(x.data(), c_.ld, (size_t) population * c_.ld);
-    std::copy(x.begin(), x.begin() + c_.n, x_out);
-    *n_evals = s.fev;
-    if (s.it == 0) {
+    report_solution(s, xbest_, (size_t) population * c_.ld, c_.n, c_.ld, x_out, n_evals, converged);
+    if (s.it == 0)
         *converged = radius_spread_converged(radius_, (size_t) population * c_.np, c_.np, c_.tol);
-    } else {
-        *converged = s.conv;
-    }
 }
 
 int PsoEngine::get(const std::string &k, int p, double *out, int cap)
@@ -255,51 +249,31 @@ int PsoEngine::get(const std::string &k, int p, double *out, int cap)
     const PsoConst &c = c_;
     PsoScal s;
     scal_.download(&s, 1, p);
-    auto one = [&](double v) {
-        if (out && cap >= 1) out[0] = v;
-        return 1;
-    };
-    auto rowsof = [&](const DevBuf<double> &b) {
-        const int cnt = c.np * c.n;
-        if (out && cap >= cnt) {
-            std::vector<double> tmp((size_t) c.np * c.ld);
-            b.download(tmp.data(), tmp.size(), (size_t) p * c.np * c.ld);
-            for (int i = 0; i < c.np; i++)
-                std::copy(tmp.begin() + (size_t) i * c.ld, tmp.begin() + (size_t) i * c.ld + c.n,
-                        out + (size_t) i * c.n);
-        }
-        return cnt;
-    };
-    auto vecof = [&](const DevBuf<double> &b) {
-        if (out && cap >= c.np) b.download(out, c.np, (size_t) p * c.np);
-        return c.np;
-    };
+    const StateOut o { out, cap };
+    const size_t pb = (size_t) p * c.np;
     if (k == "profile") return profile_report(out, cap);
-    if (k == "x") return rowsof(X_);
-    if (k == "v") return rowsof(V_);
-    if (k == "xb") return rowsof(XB_);
-    if (k == "f") return vecof(f_);
-    if (k == "fb") return vecof(fb_);
-    if (k == "ws") return vecof(ws_);
-    if (k == "xbest") {
-        if (out && cap >= c.n) xbest_.download(out, c.n, (size_t) p * c.ld);
-        return c.n;
-    }
-    if (k == "fbest") return one(s.fbest);
-    if (k == "w") return one(s.w);
-    if (k == "c1") return one(s.c1);
-    if (k == "c2") return one(s.c2);
-    if (k == "state") return one(s.state);
-    if (k == "it") return one(s.it);
-    if (k == "maxit") return one(s.maxit);
-    if (k == "fev") return one(s.fev);
-    if (k == "np") return one(c.np);
-    if (k == "chunk") return one(chunk_);      // particles between two refreshes of the swarm's best
-    if (k == "evof") return one(s.evof);
-    if (k == "stop") return one(s.stop);
-    if (k == "conv") return one(s.conv);
-    if (k == "m2") return one(s.m2);
-    if (k == "n") return one(c.n);
+    if (k == "x") return o.rows(X_, pb, c.np, c.n, c.ld);
+    if (k == "v") return o.rows(V_, pb, c.np, c.n, c.ld);
+    if (k == "xb") return o.rows(XB_, pb, c.np, c.n, c.ld);
+    if (k == "f") return o.vec(f_, pb, c.np);
+    if (k == "fb") return o.vec(fb_, pb, c.np);
+    if (k == "ws") return o.vec(ws_, pb, c.np);
+    if (k == "xbest") return o.vec(xbest_, (size_t) p * c.ld, c.n);
+    if (k == "fbest") return o.one(s.fbest);
+    if (k == "w") return o.one(s.w);
+    if (k == "c1") return o.one(s.c1);
+    if (k == "c2") return o.one(s.c2);
+    if (k == "state") return o.one(s.state);
+    if (k == "it") return o.one(s.it);
+    if (k == "maxit") return o.one(s.maxit);
+    if (k == "fev") return o.one(s.fev);
+    if (k == "np") return o.one(c.np);
+    if (k == "chunk") return o.one(chunk_);      // particles between two refreshes of the swarm's best
+    if (k == "evof") return o.one(s.evof);
+    if (k == "stop") return o.one(s.stop);
+    if (k == "conv") return o.one(s.conv);
+    if (k == "m2") return o.one(s.m2);
+    if (k == "n") return o.one(c.n);
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 
@@ -312,17 +286,11 @@ int PsoEngine::set(const std::string &k, int p, const double *in, int count)
         return 1;
     }
     if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);
-    auto rows_in = [&](DevBuf<double> &b) {
+    if (k == "x" || k == "v" || k == "xb") {
         BBO_REQUIRE(count == c.np * c.n, "set: wrong element count");
-        std::vector<double> tmp((size_t) c.np * c.ld, 0.);
-        for (int i = 0; i < c.np; i++)
-            std::copy(in + (size_t) i * c.n, in + (size_t) (i + 1) * c.n, tmp.begin() + (size_t) i * c.ld);
-        b.upload(tmp.data(), tmp.size(), (size_t) p * c.np * c.ld);
+        upload_rows(k == "x" ? X_ : k == "v" ? V_ : XB_, (size_t) p * c.np, c.np, c.n, c.ld, in);
         return count;
-    };
-    if (k == "x") return rows_in(X_);
-    if (k == "v") return rows_in(V_);
-    if (k == "xb") return rows_in(XB_);
+    }
     if (k == "f" || k == "fb") {
         BBO_REQUIRE(count == c.np, "set: wrong element count");
         (k == "f" ? f_ : fb_).upload(in, c.np, (size_t) p * c.np);

@@ -19,65 +19,6 @@ namespace bbo {
 typedef double pso_d4 __attribute__((ext_vector_type(4)));
 #define PSO_INF (__builtin_huge_val())
 
-__device__ inline bool pso_frozen(const PsoConst &c, const PsoScal *sc)
-{
-    return c.honor_stop && sc->stop != 0;
-}
-
-template<int G>
-__device__ inline double pso_group_sum(double v)
-{
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
-
-// block-wide (256 threads) reductions through a small LDS scratch
-__device__ inline double pso_block_sum(double v, double *scratch)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) scratch[tid >> 6] = v;
-    __syncthreads();
-    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
-}
-
-// arg-min (SIGN = +1) or arg-max (SIGN = -1) with first-index tie-break, 256 threads
-template<int SIGN>
-__device__ inline void pso_block_arg(double &v, int &idx, double *sval, int *sidx)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int oi = __shfl_xor(idx, off, 64);
-        const bool take = SIGN > 0 ? (ov < v || (ov == v && oi < idx))
-                                   : (ov > v || (ov == v && oi < idx));
-        if (take) {
-            v = ov;
-            idx = oi;
-        }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) {
-        sval[tid >> 6] = v;
-        sidx[tid >> 6] = idx;
-    }
-    __syncthreads();
-    v = sval[0];
-    idx = sidx[0];
-    for (int w = 1; w < 4; w++) {
-        const bool take = SIGN > 0 ? (sval[w] < v || (sval[w] == v && sidx[w] < idx))
-                                   : (sval[w] > v || (sval[w] == v && sidx[w] < idx));
-        if (take) {
-            v = sval[w];
-            idx = sidx[w];
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------
 // grid (ceil(np/16), P), 256 threads, LDS 16 * ld doubles
 // ---------------------------------------------------------------------------
@@ -106,7 +47,7 @@ __global__ __launch_bounds__(256) void pso_init(PsoDev d, PsoConst c)
         }
     }
     __syncthreads();
-    ssq = pso_group_sum<16>(ssq);
+    ssq = group_sum<16>(ssq);
     if (c.obj >= 0) {
         double f = eval_row_group<16>(c.obj, c.n, row, d.aux, g);
         if (g == 0 && i < c.np) {
@@ -133,7 +74,7 @@ __global__ __launch_bounds__(256) void pso_gbest_init(PsoDev d, PsoConst c)
             v = f[i];
             idx = i;
         }
-    pso_block_arg<1>(v, idx, sval, sidx);
+    block_arg<1>(v, idx, sval, sidx);
     if (idx == 0x7fffffff) idx = 0;
     for (int j = tid; j < c.ld; j += 256)
         d.xbest[(size_t) p * c.ld + j] = d.X[((size_t) p * c.np + idx) * c.ld + j];
@@ -158,7 +99,7 @@ __global__ __launch_bounds__(256) void pso_center(PsoDev d, PsoConst c, int part
 {
     const int p = blockIdx.y, part = blockIdx.x;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int rows_per = (c.np + parts - 1) / parts;
     const int r0 = part * rows_per, r1 = min(c.np, r0 + rows_per);
     for (int j = threadIdx.x; j < c.ld; j += 256) {
@@ -180,7 +121,7 @@ __global__ __launch_bounds__(256) void pso_mean(PsoDev d, PsoConst c, int parts)
 {
     const int p = blockIdx.x;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     for (int j = threadIdx.x; j < c.ld; j += 256) {
         double s = 0.;
         int q = 0;
@@ -200,7 +141,7 @@ __global__ __launch_bounds__(256) void pso_nrm(PsoDev d, PsoConst c)
 {
     const int p = blockIdx.y;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = blockIdx.x * 16 + r;
     double s = 0.;
@@ -215,7 +156,7 @@ __global__ __launch_bounds__(256) void pso_nrm(PsoDev d, PsoConst c)
             s += v * v;
         }
     }
-    s = pso_group_sum<16>(s);
+    s = group_sum<16>(s);
     if (g == 0 && i < c.np) d.nrm[(size_t) p * c.np + i] = s;
 }
 
@@ -254,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void pso_ese_sym(PsoDev d, PsoConst c)
 {
     const int p = blockIdx.y, I = blockIdx.x;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *cs = lds + 4 * ESE2_TILE;        // [2][128] column sums / [2][128] row sums
     double *nI = cs + 256;                   // [128] squared norms of block I
@@ -396,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void pso_ese_sym(PsoDev d, PsoConst c)
             for (int rt = 0; rt < 4; rt++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    const double s = pso_group_sum<16>(rowacc[rt][r]);
+                    const double s = group_sum<16>(rowacc[rt][r]);
                     if (fr == 0) rs[wc * 128 + 64 * wr + 16 * rt + fk + 4 * r] += s;
                 }
 #pragma unroll
@@ -434,7 +375,7 @@ __global__ __launch_bounds__(256) void pso_ese_finish(PsoDev d, PsoConst c)
 {
     const int p = blockIdx.y;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int i = blockIdx.x * 256 + threadIdx.x, np = c.np;
     if (i >= np) return;
     const int NB = (np + 127) >> 7, Jb = i >> 7, half = NB >> 1;
@@ -509,7 +450,7 @@ __global__ __launch_bounds__(256) void pso_control_a(PsoDev d, PsoConst c)
 {
     const int p = blockIdx.x;
     PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double sval[4];
     __shared__ int sidx[4];
     const int tid = threadIdx.x, np = c.np;
@@ -521,9 +462,9 @@ __global__ __launch_bounds__(256) void pso_control_a(PsoDev d, PsoConst c)
         if (ws[i] > hi) { hi = ws[i]; ihi = i; }
         if (f[i] < fv) { fv = f[i]; ib = i; }
     }
-    pso_block_arg<1>(lo, ilo, sval, sidx);
-    pso_block_arg<-1>(hi, ihi, sval, sidx);
-    pso_block_arg<1>(fv, ib, sval, sidx);
+    block_arg<1>(lo, ilo, sval, sidx);
+    block_arg<-1>(hi, ihi, sval, sidx);
+    block_arg<1>(fv, ib, sval, sidx);
     if (ib == 0x7fffffff) ib = 0;
     for (int j = tid; j < c.ld; j += 256)
         d.pvec[(size_t) p * c.ld + j] = d.xbest[(size_t) p * c.ld + j];
@@ -582,7 +523,7 @@ __global__ __launch_bounds__(256) void pso_control_b(PsoDev d, PsoConst c)
 {
     const int p = blockIdx.x;
     PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     if (!sc->need_elite) return;
     __shared__ double sval[4];
     __shared__ int sidx[4];
@@ -619,7 +560,7 @@ __global__ __launch_bounds__(256) void pso_control_b(PsoDev d, PsoConst c)
             hv = f[i];
             ih = i;
         }
-    pso_block_arg<-1>(hv, ih, sval, sidx);
+    block_arg<-1>(hv, ih, sval, sidx);
     if (ih == 0x7fffffff) ih = 0;
     const size_t row = ((size_t) p * np + ih) * ld;
     const bool better = nu < d.fb[(size_t) p * np + ih];
@@ -629,7 +570,7 @@ __global__ __launch_bounds__(256) void pso_control_b(PsoDev d, PsoConst c)
         if (better) d.XB[row + j] = pv[j];
         ssq += pv[j] * pv[j];
     }
-    ssq = pso_block_sum(ssq, sval);
+    ssq = block_sum<4>(ssq, sval);
     if (tid == 0) {
         f[ih] = nu;
         if (better) d.fb[(size_t) p * np + ih] = nu;
@@ -650,7 +591,7 @@ __global__ __launch_bounds__(256) void pso_update(PsoDev d, PsoConst c, int i0, 
 {
     const int p = blockIdx.y;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     extern __shared__ double lds[];
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = i0 + blockIdx.x * (blockDim.x >> 4) + r, ld = c.ld, n = c.n;
@@ -695,7 +636,7 @@ __global__ __launch_bounds__(256) void pso_update(PsoDev d, PsoConst c, int i0, 
         }
     }
     __syncthreads();
-    ssq = pso_group_sum<16>(ssq);
+    ssq = group_sum<16>(ssq);
     if (live && g == 0) d.radius[(size_t) p * c.np + i] = sqrt(ssq);
     if (c.obj < 0) return;   // host objective: pso_pbest runs after the host evaluation
     double f = eval_row_group<16>(c.obj, n, row, d.aux, g);
@@ -718,7 +659,7 @@ __global__ __launch_bounds__(256) void pso_pbest(PsoDev d, PsoConst c, int i0, i
 {
     const int p = blockIdx.y;
     const PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     const int tid = threadIdx.x, r = tid >> 4, g = tid & 15;
     const int i = i0 + blockIdx.x * 16 + r;
     if (i >= i1) return;
@@ -740,7 +681,7 @@ __global__ __launch_bounds__(256) void pso_gbest(PsoDev d, PsoConst c, int i0, i
 {
     const int p = blockIdx.x;
     PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double sval[4];
     __shared__ int sidx[4];
     const int tid = threadIdx.x, np = c.np, ld = c.ld;
@@ -752,7 +693,7 @@ __global__ __launch_bounds__(256) void pso_gbest(PsoDev d, PsoConst c, int i0, i
             fv = f[i];
             ib = i;
         }
-    pso_block_arg<1>(fv, ib, sval, sidx);
+    block_arg<1>(fv, ib, sval, sidx);
     const bool improved = ib != 0x7fffffff && fv < sc->fbest;
     if (improved)
         for (int j = tid; j < ld; j += 256)
@@ -765,7 +706,7 @@ __global__ __launch_bounds__(256) void pso_finish(PsoDev d, PsoConst c)
 {
     const int p = blockIdx.x;
     PsoScal *sc = d.scal + p;
-    if (pso_frozen(c, sc)) return;
+    if (pop_frozen(c, sc)) return;
     __shared__ double sval[4];
     __shared__ int sidx[4];
     const int tid = threadIdx.x, np = c.np, ld = c.ld;
@@ -777,20 +718,20 @@ __global__ __launch_bounds__(256) void pso_finish(PsoDev d, PsoConst c)
             fv = f[i];
             ib = i;
         }
-    pso_block_arg<1>(fv, ib, sval, sidx);
+    block_arg<1>(fv, ib, sval, sidx);
     const bool improved = ib != 0x7fffffff && fv < sc->fbest;
     if (improved)
         for (int j = tid; j < ld; j += 256)
             d.xbest[(size_t) p * ld + j] = d.X[((size_t) p * np + ib) * ld + j];
     double s = 0.;
     for (int i = tid; i < np; i += 256) s += rad[i];
-    const double mean = pso_block_sum(s, sval) / np;
+    const double mean = block_sum<4>(s, sval) / np;
     double m2 = 0.;
     for (int i = tid; i < np; i += 256) {
         const double dd = rad[i] - mean;
         m2 += dd * dd;
     }
-    m2 = pso_block_sum(m2, sval);
+    m2 = block_sum<4>(m2, sval);
     if (tid == 0) {
         if (improved) sc->fbest = fv;
         sc->it += 1;

@@ -121,37 +121,33 @@ public:
     int get(const std::string &k, int population, double *out, int cap) override
     {
         (void) population;
-        auto one = [&](double v) {
-            if (out && cap >= 1) out[0] = v;
-            return 1;
-        };
+        const StateOut o { out, cap };
         if (k == "xbest" || k == "x0") {
             const auto &v = k == "xbest" ? xbest_ : x0_;
-            if (out && cap >= (int) v.size()) std::copy(v.begin(), v.end(), out);
-            return (int) v.size();
+            return o.copy(v.data(), (int) v.size());
         }
-        if (k == "fev") return one(fev_);
-        if (k == "it") return one(it_);
-        if (k == "lambdadef") return one(lambdadef_);
-        if (k == "lambda") return one(lambda_);
-        if (k == "sigma") return one(sigma_);
-        if (k == "largelambda") return one(largelambda_);
-        if (k == "smalllambda") return one(smalllambda_);
-        if (k == "largebudget") return one(largebudget_);
-        if (k == "smallbudget") return one(smallbudget_);
-        if (k == "largerestarts") return one(largerestarts_);
-        if (k == "smallrestarts") return one(smallrestarts_);
-        if (k == "bestregime") return one(bestregime_);
-        if (k == "fx") return one(fx_);
-        if (k == "fxbest" || k == "fbest") return one(fxbest_);
-        if (k == "largesigma") return one(largesigma_);
-        if (k == "smallsigma") return one(smallsigma_);
-        if (k == "last_regime") return one(last_regime_);
-        if (k == "last_lambda") return one(last_lambda_);
-        if (k == "last_sigma") return one(last_sigma_);
-        if (k == "last_inner_fev") return one(last_inner_fev_);
-        if (k == "last_inner_converged") return one(last_inner_conv_);
-        if (k == "last_maxfev") return one(last_maxfev_);
+        if (k == "fev") return o.one(fev_);
+        if (k == "it") return o.one(it_);
+        if (k == "lambdadef") return o.one(lambdadef_);
+        if (k == "lambda") return o.one(lambda_);
+        if (k == "sigma") return o.one(sigma_);
+        if (k == "largelambda") return o.one(largelambda_);
+        if (k == "smalllambda") return o.one(smalllambda_);
+        if (k == "largebudget") return o.one(largebudget_);
+        if (k == "smallbudget") return o.one(smallbudget_);
+        if (k == "largerestarts") return o.one(largerestarts_);
+        if (k == "smallrestarts") return o.one(smallrestarts_);
+        if (k == "bestregime") return o.one(bestregime_);
+        if (k == "fx") return o.one(fx_);
+        if (k == "fxbest" || k == "fbest") return o.one(fxbest_);
+        if (k == "largesigma") return o.one(largesigma_);
+        if (k == "smallsigma") return o.one(smallsigma_);
+        if (k == "last_regime") return o.one(last_regime_);
+        if (k == "last_lambda") return o.one(last_lambda_);
+        if (k == "last_sigma") return o.one(last_sigma_);
+        if (k == "last_inner_fev") return o.one(last_inner_fev_);
+        if (k == "last_inner_converged") return o.one(last_inner_conv_);
+        if (k == "last_maxfev") return o.one(last_maxfev_);
         throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
     }
 

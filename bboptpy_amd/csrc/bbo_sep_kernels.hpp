@@ -115,7 +115,7 @@ __global__ __launch_bounds__(T) void sep_sample_eval(CmaDev d, CmaConst c)
                 Xp[j] = v;
             }
         }
-        cma_wave_sync();
+        wave_sync();
         if (c.obj >= 0 && row < c.lambda_pad) {
             double f = eval_row_group<G, true>(c.obj, c.n, xr, d.aux, g);
             if (g == 0) {
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(T) void sep_sample_eval(CmaDev d, CmaConst c)
                 d.f[(size_t) p * c.lambda_pad + row] = f;
             }
         }
-        cma_wave_sync();                     // the rows are reused by the next chunk
+        wave_sync();                     // the rows are reused by the next chunk
     }
 }
 
@@ -161,7 +161,7 @@ __device__ __forceinline__ void sep_term(int j, double v, const double *aux, dou
 }
 
 // sum of v over the wavefront, the same total in every lane (DPP row rotations + one readlane per
-// 16-lane row: a fixed order)
+// 16-lane row: a fixed order, and not the butterfly's of group_sum<64>)
 __device__ inline double sep_wave_sum(double v)
 {
     v = row16_sum(v);
@@ -290,7 +290,7 @@ __device__ __forceinline__ void sep_sample_sum_body(const CmaDev &d, const CmaCo
             }
             if (cnt == 0) break;
             cnt = min(cnt, SEP_PLIST);
-            cma_wave_sync();
+            wave_sync();
             for (int i0 = 0; i0 < cnt; i0 += 64) {
                 double ta = 0., tb = 0.;
                 int ek = -1, ej = -1;
@@ -316,7 +316,7 @@ __device__ __forceinline__ void sep_sample_sum_body(const CmaDev &d, const CmaCo
                     }
                 }
             }
-            cma_wave_sync();
+            wave_sync();
         }
 #pragma unroll
         for (int k = 0; k < SEP_K; k++) {
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(256) void sep_paths(CmaDev d, CmaConst c)
         ps[j] = v;
         ssq += v * v;
     }
-    ssq = wave_sum(ssq);
+    ssq = group_sum<64>(ssq);
     if ((tid & 63) == 0) red[tid >> 6] = ssq;
     __syncthreads();
     const double pslen = sqrt(red[0] + red[1] + red[2] + red[3]);

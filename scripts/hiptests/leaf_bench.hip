@@ -18,9 +18,9 @@ __global__ void k(int s, const double* d_in, const double* e_in, long long* out)
     double2 *rot = reinterpret_cast<double2*>(ws + 42);
     int *desc = reinterpret_cast<int*>(ws + 170);
     if (lane < 20) { ws[lane] = 0.; ws[20 + lane] = 0.; }
-    dc_wave_sync();
+    wave_sync();
     if (lane < s) { dl[lane] = dv[lane]; el[lane] = lane + 1 < s ? ev[lane] : 0.; }
-    dc_wave_sync();
+    wave_sync();
     EigMat blk { &Q(0, 0), Q.ld };
     QlState st { 0, 0, 1, 0, 0., 0. };
     long long tp = 0, ta = 0, calls = 0, sweeps = 0, rots = 0;
@@ -28,10 +28,10 @@ __global__ void k(int s, const double* d_in, const double* e_in, long long* out)
     for (int guard = 0; guard < 30 * s && !st.done; guard++) {
         long long a = __builtin_amdgcn_s_memtime();
         const int ns = ql_produce(st, s, dl, el, rot, desc, 64, lane);
-        dc_wave_sync();
+        wave_sync();
         long long b = __builtin_amdgcn_s_memtime();
         if (lane < s) ql_apply_row(blk, lane, rot, desc, ns);
-        dc_wave_sync();
+        wave_sync();
         long long c = __builtin_amdgcn_s_memtime();
         tp += b - a; ta += c - b; calls++; sweeps += ns;
         for (int q = 0; q < ns; q++) rots += desc[3*q+1] - desc[3*q];

@@ -18,12 +18,12 @@ __global__ void k(int s, const double* d_in, const double* e_in, double* d_out, 
         double2 *rot = reinterpret_cast<double2*>(ws + 42);
         int *desc = reinterpret_cast<int*>(ws + 170);
         if (lane < 20) { ws[lane] = 0.; ws[20 + lane] = 0.; }
-        dc_wave_sync();
+        wave_sync();
         if (lane < s) { dl[lane] = dv[lane]; el[lane] = lane + 1 < s ? ev[lane] : 0.; }
-        dc_wave_sync();
+        wave_sync();
         QlState st { 0, 0, 1, 0, 0., 0. };
         int ns = ql_produce(st, s, dl, el, rot, desc, 64, lane);
-        dc_wave_sync();
+        wave_sync();
         if (lane == 0) {
             printf("ns %d l %d m %d done %d f %g tst1 %g\n", ns, st.l, st.m, st.done, st.f, st.tst1);
             for (int i = 0; i < s; i++) printf("  d[%d]=%g e[%d]=%g\n", i, dl[i], i, el[i]);

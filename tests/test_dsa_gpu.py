@@ -402,3 +402,14 @@ def test_configure_statuses_and_refusals(hip):
     one = hip.DSA(20, 0., 0., 1, seed=2)
     sol = one.optimize(hip.objectives.sphere, lo, up, np.zeros(n))
     assert sol.n_evals == 2 and sol.converged and np.isfinite(sol.x).all()
+
+
+def test_a_row_matrix_round_trips_at_odd_n_in_the_second_population(hip):
+    """n = 3 (ld = 4), six rows, population 1: set_state -> get_state bit-equal, no padding column"""
+    n, np_, P = 3, 6, 2
+    g = hip.DSA(10 ** 6, 0., 0., np_, seed=4, populations=P)
+    g.initialize(hip.objectives.sphere, -2. * np.ones(n), 2. * np.ones(n), np.zeros((P, n)))
+    X = np.random.default_rng(9).uniform(-1., 1., (np_, n))
+    g.set_state("X", X, population=1)
+    got = g.get_state("X", 1)
+    assert got.size == np_ * n and got.tobytes() == X.tobytes()

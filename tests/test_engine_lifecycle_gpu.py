@@ -29,6 +29,8 @@ CASES = {
     "CSO": (lambda hip, mfev, **k: hip.CSO(mfev, 1e-12, NP, pcompete=2, **k), "f", ("f",)),
     "CCPSO": (lambda hip, mfev, **k: hip.CCPSO(mfev, 1e-12, NP, [2], **k), "fx", ("fx", "fy")),
     "APSO": (lambda hip, mfev, **k: hip.APSO(mfev, 1e-12, NP, **k), "fb", ("f", "fb")),
+    "JAYA": (lambda hip, mfev, **k: hip.JAYA(mfev, 1e-12, NP, 2, **k), "f", ("f",)),
+    "DSA": (lambda hip, mfev, **k: hip.DSA(mfev, 1e-12, 1e-12, NP, **k), "f", ("f",)),
 }
 NAMES = list(CASES)
 

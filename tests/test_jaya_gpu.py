@@ -275,3 +275,14 @@ def test_outcome_bands_match_the_reference(hip, obj):
     assert all(int(g.get_state("fev", p)[0]) == 4000 for p in range(P))
     print("device %s: quartiles of log10 f" % obj, np.percentile(np.log10(got), [25, 50, 75]))
     band(got, _h(b[obj]), obj + " device")
+
+
+def test_a_row_matrix_round_trips_at_odd_n_in_the_second_population(hip):
+    """n = 3 (ld = 4), six rows, population 1: set_state -> get_state bit-equal, no padding column"""
+    n, np_, P = 3, 6, 2
+    g = hip.JAYA(10 ** 6, 0., np_, 2, seed=4, populations=P)
+    g.initialize(hip.objectives.sphere, -2. * np.ones(n), 2. * np.ones(n), np.zeros((P, n)))
+    X = np.random.default_rng(9).uniform(-1., 1., (np_, n))
+    g.set_state("X", X, population=1)
+    got = g.get_state("X", 1)
+    assert got.size == np_ * n and got.tobytes() == X.tobytes()

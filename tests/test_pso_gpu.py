@@ -181,3 +181,14 @@ def test_whole_run_same_seed_matches_oracle(hip, oracle_lib, obj, seed):
     xo, fevo, convo = o.optimize(obj, lo, up, np.zeros(n))
     assert sol.n_evals == fevo and sol.converged == convo
     np.testing.assert_allclose(sol.x, xo, rtol=0, atol=1e-8)
+
+
+def test_a_row_matrix_round_trips_at_odd_n_in_the_second_population(hip):
+    """n = 3 (ld = 4), six rows, population 1: set_state -> get_state bit-equal, no padding column"""
+    n, np_, P = 3, 6, 2
+    g = hip.APSO(10 ** 6, 1e-12, np_, seed=4, populations=P)
+    g.initialize(hip.objectives.sphere, -2. * np.ones(n), 2. * np.ones(n), np.zeros((P, n)))
+    X = np.random.default_rng(9).uniform(-1., 1., (np_, n))
+    g.set_state("x", X, population=1)
+    got = g.get_state("x", 1)
+    assert got.size == np_ * n and got.tobytes() == X.tobytes()
