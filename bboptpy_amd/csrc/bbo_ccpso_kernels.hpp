@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void ccp_regroup(CcpDev d, CcpConst c)
         const int is0 = sc->is;
         int is = is0;
         if (!sc->improved) {
-            const u32x4 w = philox4x32_10(c.seed, 0, 0, (uint32_t) gen, sw);
+            const u32x4 w = philox4x32_10_uniform(c.seed, 0, 0, (uint32_t) gen, sw);
             is = uint_below(w.x, c.npps);
         }
         s_changed = is != is0;

@@ -33,7 +33,7 @@ enum { DSA_MAP_RANDOM1 = 0, DSA_MAP_DIFFERENTIAL = 1, DSA_MAP_RANDOM2 = 2 };
 // population, p) alone: dsa_rank and dsa_plan both call it and agree.
 __device__ inline int dsa_method(const DsaConst &c, const DsaScal *sc, int p, double &u, double &ucoin)
 {
-    const u32x4 w = philox4x32_10(c.seed, DSA_CTRL_METHOD, 0, (uint32_t) sc->gen,
+    const u32x4 w = philox4x32_10_uniform(c.seed, DSA_CTRL_METHOD, 0, (uint32_t) sc->gen,
             stream_word(STREAM_DSA_CTRL, (uint32_t) p));
     u = u01(w.x, w.y);
     ucoin = u01(w.z, w.w);
@@ -117,8 +117,8 @@ __global__ __launch_bounds__(256) void dsa_plan(DsaDev d, DsaConst c)
     const size_t pb = (size_t) p * np;
     if (tid == 0) {
         const uint32_t ctrl = stream_word(STREAM_DSA_CTRL, (uint32_t) p);
-        const u32x4 w0 = philox4x32_10(c.seed, DSA_CTRL_P, 0, gen, ctrl);
-        const u32x4 w2 = philox4x32_10(c.seed, DSA_CTRL_MAP, 0, gen, ctrl);
+        const u32x4 w0 = philox4x32_10_uniform(c.seed, DSA_CTRL_P, 0, gen, ctrl);
+        const u32x4 w2 = philox4x32_10_uniform(c.seed, DSA_CTRL_MAP, 0, gen, ctrl);
         const double up1 = u01(w0.x, w0.y), up2 = u01(w0.z, w0.w);
         const double ustrat = u01(w2.x, w2.y), ur = u01_open0(w2.z, w2.w);
         double um, ucoin;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void dsa_plan(DsaDev d, DsaConst c)
         }
     } else if (method == 2) {
         // E1-DSA, :270-275: rank min(ub, np - 1), once for all members
-        const u32x4 w = philox4x32_10(c.seed, 0, 1, gen, stream_word(STREAM_DSA_DIR, (uint32_t) p));
+        const u32x4 w = philox4x32_10_uniform(c.seed, 0, 1, gen, stream_word(STREAM_DSA_DIR, (uint32_t) p));
         const double u = u01(w.x, w.y);
         const int r = order[min((int) ceil(u * np), np - 1)];
         for (int i = tid; i < np; i += 256) {

@@ -22,13 +22,7 @@ struct EigMat {
 // 16-lane row) instead of LDS permutes; every lane gets the same total, and the fixed
 // order makes it identical in every wavefront that sums the same values
 template<int CTRL>
-__device__ inline double eig_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
+__device__ inline double eig_dpp(double v) { return dpp_mov<CTRL>(v); }
 
 // partner exchange inside groups of four lanes (DPP quad_perm: a plain vector move, where
 // __shfl_xor goes through the LDS crossbar -- ds_bpermute, an address computation and a wait on

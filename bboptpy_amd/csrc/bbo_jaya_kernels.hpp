@@ -27,7 +27,7 @@ enum { JAYA_CTRL_XCHAOS = 0, JAYA_CTRL_LEN = 1, JAYA_CTRL_ROULETTE = 2, JAYA_CTR
 // the redraw guards of the chaotic maps (`while (_xchaos == 0.7) _xchaos = Random::get(0., 1.)`)
 __device__ inline double jaya_redraw(const JayaConst &c, JayaScal *sc, int p)
 {
-    const u32x4 w = philox4x32_10(c.seed, JAYA_CTRL_REDRAW, (uint32_t) sc->nredraw, 0,
+    const u32x4 w = philox4x32_10_uniform(c.seed, JAYA_CTRL_REDRAW, (uint32_t) sc->nredraw, 0,
             stream_word(STREAM_JAYA_CTRL, (uint32_t) p));
     sc->nredraw++;
     return u01(w.x, w.y);
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64) void jaya_seed(JayaDev d, JayaConst c)
         d.perfindex[(size_t) p * c.nks + q] = 0.;
     }
     if (tid != 0) return;
-    const u32x4 w = philox4x32_10(c.seed, JAYA_CTRL_XCHAOS, 0, 0, stream_word(STREAM_JAYA_CTRL, (uint32_t) p));
+    const u32x4 w = philox4x32_10_uniform(c.seed, JAYA_CTRL_XCHAOS, 0, 0, stream_word(STREAM_JAYA_CTRL, (uint32_t) p));
     double xc = u01(w.x, w.y);
     if (c.mutation == JAYA_TENT)
         for (int i = 0; i < c.np; i++)
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void jaya_partition(JayaDev d, JayaConst c)
         const int base = np / k;
         for (int q = 0; q < k; q++) len[q] = base;
         for (int i = 0; i < np - base * k; i++) {
-            const u32x4 w = philox4x32_10(c.seed, JAYA_CTRL_LEN, (uint32_t) i, (uint32_t) gen, ctrl);
+            const u32x4 w = philox4x32_10_uniform(c.seed, JAYA_CTRL_LEN, (uint32_t) i, (uint32_t) gen, ctrl);
             len[uint_below(w.x, k)]++;
         }
         int o = 0;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256) void jaya_finish(JayaDev d, JayaConst c, int i
         ps[k - 1] = exp(c.temper * imp);
         double total = 0.;
         for (int q = 0; q < nks; q++) total += ps[q];
-        const u32x4 w = philox4x32_10(c.seed, JAYA_CTRL_ROULETTE, 0, (uint32_t) gen,
+        const u32x4 w = philox4x32_10_uniform(c.seed, JAYA_CTRL_ROULETTE, 0, (uint32_t) gen,
                 stream_word(STREAM_JAYA_CTRL, (uint32_t) p));
         const double u = u01(w.x, w.y);
         double U = u * total;

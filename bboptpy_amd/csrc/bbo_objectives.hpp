@@ -173,13 +173,7 @@ __device__ inline double eval_row_group(int obj, int n, const double *xrow, cons
 // objectives go through eval_row_group from LDS instead.
 // ---------------------------------------------------------------------------
 template<int CTRL>
-__device__ inline double row16_dpp(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
+__device__ inline double row16_dpp(double v) { return dpp_mov<CTRL>(v); }
 
 __device__ inline double row16_sum(double v)
 {
@@ -235,10 +229,11 @@ __device__ inline void eval_frag_rows(int obj, int n, const double (&x)[NT][4], 
         case OBJ_ROSENBROCK:
 #pragma unroll
             for (int t = 0; t < NT; t++) {
+                // the right-hand neighbour in ONE move: lane 15 takes lane 0's value, and the column
+                // to its right is lane 0's of the NEXT tile, so lane 0 -- nobody reads its own-tile
+                // value -- offers that one (beyond the last tile: masked below)
                 const double xj = x[t][r];
-                const double same = row16_next(xj);
-                const double wrap = row16_next(x[t + 1 < NT ? t + 1 : t][r]);
-                const double xn = c0 < 15 ? same : wrap;
+                const double xn = row16_next(c0 == 0 ? x[t + 1 < NT ? t + 1 : t][r] : xj);
                 const double tt = xn - xj * xj;
                 const double u = 1. - xj;
                 a += (16 * t + c0 + 1 < n) ? 100. * (tt * tt) + u * u : 0.;

@@ -481,8 +481,8 @@ __global__ __launch_bounds__(256) void pso_control_a(PsoDev d, PsoConst c)
         } else {
             // updatec1c2, apso.cpp:248-298
             const uint32_t sw = stream_word(STREAM_PSO_CTRL, (uint32_t) p);
-            u32x4 w0 = philox4x32_10(c.seed, 0, 0, (uint32_t) sc->it, sw);
-            u32x4 w1 = philox4x32_10(c.seed, 1, 0, (uint32_t) sc->it, sw);
+            u32x4 w0 = philox4x32_10_uniform(c.seed, 0, 0, (uint32_t) sc->it, sw);
+            u32x4 w1 = philox4x32_10_uniform(c.seed, 1, 0, (uint32_t) sc->it, sw);
             const double delta1 = u01(w0.x, w0.y) * (0.1 - 0.05) + 0.05;
             const double delta2 = u01(w1.x, w1.y) * (0.1 - 0.05) + 0.05;
             double c1 = sc->c1, c2 = sc->c2;
@@ -504,7 +504,7 @@ __global__ __launch_bounds__(256) void pso_control_a(PsoDev d, PsoConst c)
             sc->c2 = c2;
             if (ns == 3) {
                 // updateElitist, apso.cpp:203-209: perturb one coordinate of gbest
-                const u32x4 w2 = philox4x32_10(c.seed, 2, 0, (uint32_t) sc->it, sw);
+                const u32x4 w2 = philox4x32_10_uniform(c.seed, 2, 0, (uint32_t) sc->it, sw);
                 const int dd = uint_below(w2.x, c.n);
                 double z0, z1;
                 normal_pair(c.seed, 3, 0, (uint32_t) sc->it, sw, z0, z1);

@@ -65,10 +65,7 @@ __device__ inline bool pair_less(double fa, int ia, double fb, int ib)
 // 16-lane row and go through DPP moves (VALU, no LDS crossbar: quad_perm for 1 and 2,
 // row_half_mirror + quad reversal for 4, row_ror:8 for 8); 16 and 32 use the LDS permute.
 template<int CTRL>
-__device__ inline int sort_dpp(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
+__device__ inline int sort_dpp(int v) { return dpp_mov<CTRL>(v); }
 
 template<int LX>
 __device__ inline int sort_xor_lane(int v)

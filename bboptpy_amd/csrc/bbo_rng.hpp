@@ -40,7 +40,23 @@ struct u32x4 {
     uint32_t x, y, z, w;
 };
 
-__host__ __device__ inline u32x4 philox4x32_10(uint64_t seed, uint32_t c0, uint32_t c1,
+// a ^ b ^ c.  gfx950 has the three-input bit operation (truth table 0x96 = parity); left to
+// itself the compiler forms it for a fraction of the rounds' XOR pairs only, and on the vector
+// pipe the CMA samplers share with their fp64 MFMAs every instruction is paid for.
+// LANES = false: the portable expression.  The three-input operation exists on the vector unit
+// only; a call whose counters are the same in every lane (a control draw) is computed on the
+// scalar unit as long as nothing in it is a vector instruction.
+template<bool LANES>
+__host__ __device__ inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+    if (LANES) return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#endif
+    return a ^ b ^ c;
+}
+
+template<bool LANES>
+__host__ __device__ inline u32x4 philox_rounds(uint64_t seed, uint32_t c0, uint32_t c1,
         uint32_t c2, uint32_t c3)
 {
     uint32_t k0 = (uint32_t) seed, k1 = (uint32_t) (seed >> 32);
@@ -48,15 +64,29 @@ __host__ __device__ inline u32x4 philox4x32_10(uint64_t seed, uint32_t c0, uint3
     for (int r = 0; r < 10; r++) {
         const uint64_t p0 = (uint64_t) 0xD2511F53u * c0;
         const uint64_t p1 = (uint64_t) 0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t) (p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n0 = xor3<LANES>((uint32_t) (p1 >> 32), c1, k0);
         const uint32_t n1 = (uint32_t) p1;
-        const uint32_t n2 = (uint32_t) (p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n2 = xor3<LANES>((uint32_t) (p0 >> 32), c3, k1);
         const uint32_t n3 = (uint32_t) p0;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
     return u32x4 { c0, c1, c2, c3 };
+}
+
+// the draws of the lanes (counters that differ from lane to lane)
+__host__ __device__ inline u32x4 philox4x32_10(uint64_t seed, uint32_t c0, uint32_t c1,
+        uint32_t c2, uint32_t c3)
+{
+    return philox_rounds<true>(seed, c0, c1, c2, c3);
+}
+
+// the same words for a control draw: every counter word is the same in all lanes
+__host__ __device__ inline u32x4 philox4x32_10_uniform(uint64_t seed, uint32_t c0, uint32_t c1,
+        uint32_t c2, uint32_t c3)
+{
+    return philox_rounds<false>(seed, c0, c1, c2, c3);
 }
 
 __host__ __device__ inline uint32_t stream_word(uint32_t stream, uint32_t sub)

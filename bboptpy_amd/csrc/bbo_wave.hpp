@@ -25,6 +25,27 @@ __device__ inline bool pop_frozen(const C &c, const S *sc)
     return c.honor_stop && sc->stop != 0;
 }
 
+// DPP move of a 32-bit word / an fp64 value with control word CTRL, all rows and banks enabled.
+// mov_dpp with bound_ctrl set instead of update_dpp(old = 0, ..., bound_ctrl = false): a lane whose
+// source does not exist (the lanes row_shr shifts in) or is switched off reads 0 in the first form
+// and keeps old = 0 in the second -- the same value -- and with row_mask = bank_mask = 0xf no lane
+// is left out of the write, so `old` shows nowhere else.  But `old = 0` is an operand the compiler
+// has to put into the destination first: a v_mov_b32 v, 0 in front of every v_mov_b32_dpp, twice
+// per fp64 value, on the pipe the fp64 MFMAs share.  (A move under a partial row or bank mask does
+// keep `old` in the lanes it leaves out and cannot take this form; there is none in the library.)
+template<int CTRL>
+__device__ inline int dpp_mov(int v)
+{
+    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
+}
+
+template<int CTRL>
+__device__ inline double dpp_mov(double v)
+{
+    const int lo = dpp_mov<CTRL>(__double2loint(v)), hi = dpp_mov<CTRL>(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
 // xor butterfly over G lanes (a power of two, <= 64, contiguous in one wavefront): every lane of
 // the group returns the total
 template<int G>
