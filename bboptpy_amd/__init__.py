@@ -9,8 +9,8 @@ from . import objectives
 from .objectives import vectorized, DeviceObjective
 from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, CMAES,
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
-                           SANSDE, APSO, CSO, CCPSO, JAYA, DSA)
+                           SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "objectives",
            "vectorized", "DeviceObjective"]

@@ -13,13 +13,16 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
-    ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA = range(14)
+    ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
+    ALGO_HEES = range(15)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
 ERR_ARG = -1
 # bbo_cma_phase
 PHASE_SAMPLE_EVALUATE, PHASE_RANK, PHASE_UPDATE, PHASE_EIGEN, PHASE_HISTORY_STOP = range(5)
+# bbo_hees_phase
+HEES_PHASE_SAMPLE, HEES_PHASE_RANK, HEES_PHASE_UPDATE, HEES_PHASE_FINISH = range(4)
 
 BUILTIN_IDS = {"sphere": 0, "rosenbrock": 1, "rastrigin": 2, "ellipsoid": 3, "ackley": 4,
                "griewank": 5, "cigar": 6, "discus": 7, "diffpow": 8, "schwefel12": 9}
@@ -58,6 +61,11 @@ class JayaParams(C.Structure):
 class DsaParams(C.Structure):
     """bbo_dsa_params: DSA's constructor arguments that bbo_params has no field for"""
     _fields_ = [("adapt", C.c_int), ("nbatch", C.c_int)]
+
+
+class HeesParams(C.Structure):
+    """bbo_hees_params: HEES's constructor arguments that bbo_params has no field for"""
+    _fields_ = [("mres", C.c_int), ("print", C.c_int)]
 
 
 class Objective(C.Structure):
@@ -120,6 +128,11 @@ def lib():
     L.bbo_dsa_params_default.argtypes = [C.POINTER(DsaParams)]
     L.bbo_dsa_params_default.restype = None
     L.bbo_dsa_configure.argtypes = [C.c_void_p, C.POINTER(DsaParams)]
+    L.bbo_hees_params_default.argtypes = [C.POINTER(HeesParams)]
+    L.bbo_hees_params_default.restype = None
+    L.bbo_hees_configure.argtypes = [C.c_void_p, C.POINTER(HeesParams)]
+    L.bbo_hees_phase.argtypes = [C.c_void_p, C.c_int]
+    L.bbo_hees_inject_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -130,7 +143,8 @@ def lib():
                  "bbo_cma_set_seed", "bbo_cma_evaluate", "bbo_ccpso_set_shard", "bbo_ccpso_set_local", "bbo_ccpso_phase",
                  "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
                  "bbo_program_create", "bbo_program_destroy", "bbo_jaya_configure",
-                 "bbo_dsa_configure"):
+                 "bbo_dsa_configure", "bbo_hees_configure", "bbo_hees_phase",
+                 "bbo_hees_inject_normals"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -145,6 +159,7 @@ EXPORTED_SYMBOLS = (
     "bbo_program_create", "bbo_program_destroy",
     "bbo_jaya_params_default", "bbo_jaya_configure",
     "bbo_dsa_params_default", "bbo_dsa_configure",
+    "bbo_hees_params_default", "bbo_hees_configure", "bbo_hees_phase", "bbo_hees_inject_normals",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

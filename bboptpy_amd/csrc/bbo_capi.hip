@@ -5,6 +5,7 @@
 #include "bbo_ccpso.hpp"
 #include "bbo_jaya.hpp"
 #include "bbo_dsa.hpp"
+#include "bbo_hees.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -18,6 +19,7 @@ Optimizer* make_cso_engine(const bbo_params &p);      // bbo_cso.hip
 Optimizer* make_ccpso_engine(const bbo_params &p);    // bbo_ccpso.hip
 Optimizer* make_jaya_engine(const bbo_params &p);     // bbo_jaya.hip
 Optimizer* make_dsa_engine(const bbo_params &p);      // bbo_dsa.hip
+Optimizer* make_hees_engine(const bbo_params &p);     // bbo_hees.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -213,6 +215,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_DSA:
             h->opt.reset(bbo::make_dsa_engine(*params));
+            break;
+        case BBO_ALGO_HEES:
+            h->opt.reset(bbo::make_hees_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -518,6 +523,41 @@ int bbo_dsa_configure(bbo_handle h, const bbo_dsa_params *p)
         if (!e) throw bbo::Error(BBO_ERR_ARG, "not a DSA handle");
         e->configure(*p);
     });
+}
+
+void bbo_hees_params_default(bbo_hees_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp:206-211
+    p->mres = 1;
+    p->print = 0;
+}
+
+namespace {
+bbo::HeesEngine* as_hees(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::HeesEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a HEES handle");
+    return e;
+}
+}
+
+int bbo_hees_configure(bbo_handle h, const bbo_hees_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_hees_configure: NULL parameters");
+        as_hees(h)->configure(*p);
+    });
+}
+
+int bbo_hees_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_hees(h)->phase(phase); });
+}
+
+int bbo_hees_inject_normals(bbo_handle h, const double *z, int count)
+{
+    return guarded(h, [&] { as_hees(h)->inject_normals(z, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

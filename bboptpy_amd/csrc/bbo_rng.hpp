@@ -33,7 +33,8 @@ enum Stream : uint32_t {
     STREAM_DSA_PERM = 14,
     STREAM_DSA_DIR = 15,
     STREAM_DSA_MAP = 16,
-    STREAM_DSA_R = 17
+    STREAM_DSA_R = 17,
+    STREAM_HEES_NORMAL = 18
 };
 
 struct u32x4 {

@@ -724,6 +724,52 @@ class DSA(MultivariateSearch):
         return h
 
 
+class HEES(MultivariateSearch):
+    """HEES(mfev, tol, mres=1, print=False, np=0, sigma0=2.) -- :206-211 (Hessian Estimation
+    Evolution Strategy, Glasmachers & Krause 2020; hees.cpp).  `np` is mu, the number of mirrored
+    pairs: 2 np + 1 evaluations per generation; np = 0 means int(2 + 1.5 ln n).  optimize() with
+    mres > 1 restarts with doubled np from uniform points of the box (a finite box, populations=1);
+    initialize / iterate / run ignore mres, as in the reference.  The bounds never clamp."""
+    _algo = _ffi.ALGO_HEES
+
+    def __init__(self, mfev, tol, mres=1, print=False, np=0, sigma0=2., **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.np, p.sigma0 = int(mfev), float(tol), int(np), float(sigma0)
+        h = self._hees = _ffi.HeesParams()
+        h.mres, h.print = int(mres), int(bool(print))
+        if h.mres > 1 and p.populations != 1:
+            raise ValueError("HEES: restarts (mres > 1) work on populations=1 only")
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_hees_configure(h, C.byref(self._hees))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def optimize(self, f, lower, upper, guess):
+        if self._hees.print:
+            sys.stdout.flush()      # the table is written by the library
+        return super().optimize(f, lower, upper, guess)
+
+    def phase(self, which):
+        """one part of a generation: 0 sample + evaluate, 1 rank, 2 update, 3 finish"""
+        self._check(_ffi.lib().bbo_hees_phase(self._handle, int(which)))
+
+    def inject_normals(self, z):
+        """the normals of the following generations: per population the reference's (B n) x n
+        table, B = ceil(mu / n), of which the first mu rows are used; None: the device draws"""
+        if z is None:
+            self._check(_ffi.lib().bbo_hees_inject_normals(self._handle, None, 0))
+            return
+        z = _np.ascontiguousarray(_np.asarray(z, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_hees_inject_normals(
+            self._handle, z.ctypes.data_as(C.c_void_p), z.size))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

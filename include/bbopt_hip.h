@@ -55,7 +55,8 @@ typedef enum {
     BBO_ALGO_CCPSO = 10,       /* CCPSOSearch  src/multivariate/pso/ccpso.h:46        */
     BBO_ALGO_CHOLESKY_CMAES = 11, /* CholeskyCmaes src/multivariate/cma/cholesky_cmaes.h:37 */
     BBO_ALGO_JAYA = 12,        /* JayaSearch   src/multivariate/jaya/jaya.h:50        */
-    BBO_ALGO_DSA = 13          /* DSSearch     src/multivariate/pso/ds.h:33           */
+    BBO_ALGO_DSA = 13,         /* DSSearch     src/multivariate/pso/ds.h:33           */
+    BBO_ALGO_HEES = 14         /* Hees         src/multivariate/hees/hees.h:53        */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -360,6 +361,29 @@ int bbo_jaya_configure(bbo_handle h, const bbo_jaya_params *p);
 typedef struct { int adapt, nbatch; } bbo_dsa_params;
 void bbo_dsa_params_default(bbo_dsa_params *p);     /* 1, 100 */
 int bbo_dsa_configure(bbo_handle h, const bbo_dsa_params *p);
+
+/* ---- HEES (BBO_ALGO_HEES): HEES(mfev,tol,mres=1,print=False,np=0,sigma0=2.)  py/multivariate_py.cpp:206-211,
+ * the Hessian Estimation Evolution Strategy (Glasmachers & Krause 2020; hees.cpp).  `mfev`, `tol`, `np`
+ * (0 or less: mu = int(2 + 1.5 ln n)) and `sigma0` travel in bbo_params; `mres` and `print` travel
+ * here.  bbo_hees_configure is legal between bbo_create and bbo_init; without it the defaults hold.
+ * BBO_ERR_ARG: not a HEES handle; BBO_ERR_STATE after bbo_init.  Limits: n in [1, 512], mu <= 4096
+ * (bbo_init returns BBO_ERR_ARG beyond them).  The box is never used to clamp.  bbo_optimize with
+ * mres > 1 makes up to mres runs from the remaining budget, mu doubling from run to run, the start
+ * points uniform in the box from the second run on (a finite box and populations = 1 are required;
+ * run r uses the seed of the handle + r - 1); with `print` it writes the reference's table (iter | f* |
+ * fev, one row per run) to stdout and reports converged = 0.  bbo_init / bbo_iterate / bbo_run
+ * ignore mres, as the reference's init / iterate do.  Objective programs are refused by bbo_init;
+ * HEES is no base of a restart driver.
+ * bbo_hees_phase: one part of a generation (0 sample + evaluate, 1 rank, 2 the updates of A, m,
+ * p_s and sigma, 3 f(m), the counters and the stop test); the four in order are bbo_iterate.
+ * bbo_hees_inject_normals: the normals of the following generations instead of the device's draws,
+ * `populations` tables of (B n) x n doubles, B = ceil(mu / n), as the reference draws them: the
+ * first mu rows of each are used.  NULL returns to the device generator; bbo_init does the same. */
+typedef struct { int mres, print; } bbo_hees_params;
+void bbo_hees_params_default(bbo_hees_params *p);   /* 1, 0 */
+int bbo_hees_configure(bbo_handle h, const bbo_hees_params *p);
+int bbo_hees_phase(bbo_handle h, int phase);
+int bbo_hees_inject_normals(bbo_handle h, const double *z, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
