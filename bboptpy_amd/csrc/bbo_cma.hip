@@ -752,6 +752,17 @@ void CmaEngine::launch_eigen()
             && !(d_.dbg & (2 | 16777216)) && mw_reserve((long) c.npop * 16);
     // n <= 16: a wavefront per matrix (dbg bit 4 keeps the big kernel)
     const bool small = c.n <= 16 && c.n >= 2 && c.ld == 16 && !(d_.dbg & 16);
+    // a batch of n = ld = 128 under lazy_isc, production settings: the fixed-shape build of cma_eigen
+    // (same bits; any diagnostic bit the decomposition reads, a clock request, or bit 2097152 keeps
+    // the generic kernel)
+    const int eig_path_bits = 1 | 2 | 4 | 8 | 1024 | 2048 | 8192 | 16384 | 32768 | 524288 | 2097152 | 4194304 | 8388608;
+    const bool fixed_shape = c.n == 128 && c.ld == 128 && pl_lds.use_lds && pl_lds.dc && pl_lds.reg_path
+            && pl_lds.threads == 512 && pl_lds.lda == EIG_FX_PLAN.lda && pl_lds.rc == EIG_FX_PLAN.rc
+            && pl_lds.lds_bytes == EIG_FX_PLAN.lds_bytes && !d_.stamps && !(d_.dbg & eig_path_bits);
+    const bool fixed128 = fixed_shape && c.npop > split_maxp_ && !split128 && c.lazy_isc;
+    // (the split form's reduction, cma_eigen_r1, has the same build)
+    const bool fixed_r1 = fixed_shape && split128 && pl.hybrid;
+    eig_fixed_last_ = (fixed128 || fixed_r1) && !small;
     if (small)    // (does cma_post's work too: one launch less where launches are what costs)
         hipLaunchKernelGGL(cma_eigen_small, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_, 0,
                 1);
@@ -761,7 +772,11 @@ void CmaEngine::launch_eigen()
     else if (pl.threads == 256)
         hipLaunchKernelGGL(cma_eigen_256, dim3(c.npop), dim3(256), pl.lds_bytes, stream_, d_, c_,
                 pl, 0);
-    else if (pl.use_lds)
+    else if (fixed128) {
+        allow_lds((const void*) cma_eigen_fx128, 160 * 1024 - 768);
+        const EigFxArgs fa { d_.C, d_.B, d_.D, d_.BDp, d_.eig_work, d_.scal, c.eigenfreq, c.honor_stop };
+        hipLaunchKernelGGL(cma_eigen_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
+    } else if (pl.use_lds)
         hipLaunchKernelGGL(cma_eigen, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_,
                 pl, 0);
     else if (pl.hybrid && !(d_.dbg & (2 | 1024 | 4194304))) {
@@ -780,7 +795,11 @@ void CmaEngine::launch_eigen()
         // engines (they wait for each other: MwBudget above, bbo_eig_mw.hpp; diagnostic bit 16777216
         // keeps the reduction on one workgroup)
         const bool use_mw = !split128 && !mw_disabled_ && !(d_.dbg & 16777216) && mw_reserve((long) c.npop * MW_G);
-        if (split128) {
+        if (split128 && fixed_r1) {
+            allow_lds((const void*) cma_eigen_r1_fx128, 160 * 1024 - 768);
+            const EigFxArgs fa { d_.C, d_.B, d_.D, d_.BDp, d_.eig_work, d_.scal, c.eigenfreq, c.honor_stop };
+            hipLaunchKernelGGL(cma_eigen_r1_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
+        } else if (split128) {
             allow_lds((const void*) cma_eigen_r1, 160 * 1024 - 768);
             hipLaunchKernelGGL(cma_eigen_r1, dim3(c.npop), dim3(512), pl_lds.lds_bytes, stream_, d_, c_,
                     pl_lds, 0);
@@ -1235,6 +1254,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     if (c.variant == 3 && k == "ranked") return o.one(c.ranked);
     if (k == "eig_mw_off") return o.one(mw_disabled_ ? 1 : 0);
     if (k == "eig_split_maxp") return o.one(split_maxp_);
+    if (k == "eig_fixed128") return o.one(eig_fixed_last_ ? 1 : 0);       // the last decomposition took a fixed-shape kernel
     if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups
         MwBudget &b = MwBudget::get();

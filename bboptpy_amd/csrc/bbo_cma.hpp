@@ -155,6 +155,7 @@ private:
     long sample128_min_rows_ = 256 * 128;   // candidates in flight from which cma_sample_eval128 is used
     bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
+    bool eig_fixed_last_ = false;      // the last launch_eigen took the fixed-shape kernel (get "eig_fixed128")
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;
 

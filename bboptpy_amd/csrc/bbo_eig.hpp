@@ -51,7 +51,7 @@ __host__ __device__ inline size_t eig_slab(int ld) { return (size_t) (ld + 32) *
 // doubles of the `part` area behind the nine LDS vectors: [4][vl] column partial sums of the generic
 // path; the hybrid (128 < n <= 256, D&C) keeps eight 128-column slabs of its transposed product and
 // the previous step's u / w (2 x 128) there
-__host__ __device__ inline int eig_part_doubles(int vl, bool reg_path, bool hybrid)
+__host__ __device__ constexpr int eig_part_doubles(int vl, bool reg_path, bool hybrid)
 {
     if (reg_path) return 0;
     const int generic = 4 * vl;
@@ -61,7 +61,8 @@ __host__ __device__ inline int eig_part_doubles(int vl, bool reg_path, bool hybr
     return vl >= 256 ? (generic > 1024 ? generic : 1024) : 1280;
 }
 
-inline EigPlan eig_plan(int n, int ld)
+// (constexpr: the fixed-shape kernel cma_eigen_fx128 takes its plan as a compile-time value)
+constexpr EigPlan eig_plan(int n, int ld)
 {
     EigPlan pl {};
     pl.threads = n <= 32 ? 128 : n <= 64 ? 256 : EIG_THREADS;
@@ -1101,7 +1102,9 @@ __device__ inline void eig_tred_sym256(const double *C, int ld, int n, const Eig
 // eig_work[3] = [d | e | h | .] and cma_eig_halves / STAGE 2 take over; 2 = the top merge of the two
 // halves cma_eig_halves has solved (their eigenvalues at eig_work[3] + 3 n, their eigenvector blocks
 // on the diagonal of the work matrix), the reflectors' T factors and the closing repair / root.
-template<int TT, bool LDSM, int HYB = 1, int STAGE = 0>
+// FX (cma_eigen_fx128): n = ld = 128, no diagnostics -- the caller passes d, c and pl as constants and
+// the divide and conquer takes its block structure as compile-time facts (eig_dc_phase)
+template<int TT, bool LDSM, int HYB = 1, int STAGE = 0, bool FX = false>
 __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &c, const EigPlan &pl,
         int force)
 {
@@ -1254,7 +1257,7 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
         long long *st_ = (d.stamps && p == 0 && !(STAGE == 2 && (d.dbg & 2048))) ? d.stamps : nullptr;
         if (LDSM || HYB || TT != EIG_THREADS) {
             // n <= 256: the reflectors are stashed (hv = 1 / their scalars)
-            eig_dc_phase<TT, false, !LDSM>(Qm, n, dv, ev, Gp, Bp_, ld, scr, st_, d.dbg, LDSM ? 0 : 1, hvec,
+            eig_dc_phase<TT, false, !LDSM, FX>(Qm, n, dv, ev, Gp, Bp_, ld, scr, st_, d.dbg, LDSM ? 0 : 1, hvec,
                     !LDSM && !(d.dbg & 2) && !(d.dbg & 1024),   // (hybrid: V already in its place)
                     nullptr, STAGE == 2 ? 2 : 0, STAGE == 2 && tri[4 * n] != 0.,
                     STAGE == 2 ? force : 0, tri + 4 * n + 8);      // (STAGE 2: `force` = the part)
@@ -1393,6 +1396,49 @@ __global__ __launch_bounds__(512) void cma_eigen_g(CmaDev d, CmaConst c, EigPlan
 __global__ __launch_bounds__(512) void cma_eigen_b(CmaDev d, CmaConst c, EigPlan pl, int force)
 {
     cma_eigen_impl<512, false, 0>(d, c, pl, force);
+}
+// The batch decomposition of n = ld = 128 under lazy_isc, production settings only (round 7): what
+// cma_eigen computes, bit for bit, with everything the generic kernel decides at run time -- the
+// dimension and its strides, the plan, the diagnostic switches, the clocks, the 16 leaves of 8 and
+// the merge widths 16, 32, 64, 128 -- a compile-time fact, and the handful of pointers and scalars
+// it reads as its only arguments (CmaDev, CmaConst and EigPlan by value were 258 spilled SGPRs).
+struct EigFxArgs {
+    double *C, *B, *D, *BDp, *eig_work;
+    CmaScal *scal;
+    double eigenfreq;
+    int honor_stop;
+};
+constexpr EigPlan EIG_FX_PLAN = eig_plan(128, 128);
+__global__ __launch_bounds__(512) void cma_eigen_fx128(EigFxArgs a)
+{
+    static_assert(EIG_FX_PLAN.use_lds == 1 && EIG_FX_PLAN.dc == 1 && EIG_FX_PLAN.reg_path == 1
+            && EIG_FX_PLAN.threads == 512 && EIG_FX_PLAN.vl == 130, "cma_eigen_fx128: the plan of n = 128");
+    CmaDev d {};
+    d.C = a.C;
+    d.B = a.B;
+    d.D = a.D;
+    d.BDp = a.BDp;
+    d.eig_work = a.eig_work;
+    d.scal = a.scal;
+    CmaConst c {};
+    c.n = c.ld = 128;
+    c.lazy_isc = 1;
+    c.honor_stop = a.honor_stop;
+    c.eigenfreq = a.eigenfreq;
+    cma_eigen_impl<512, true, 1, 0, true>(d, c, EIG_FX_PLAN, 0);
+}
+// (the same build of cma_eigen_r1, the reduction of the split form for at most eig_split_maxp matrices)
+__global__ __launch_bounds__(512) void cma_eigen_r1_fx128(EigFxArgs a)
+{
+    CmaDev d {};
+    d.C = a.C;
+    d.eig_work = a.eig_work;
+    d.scal = a.scal;
+    CmaConst c {};
+    c.n = c.ld = 128;
+    c.honor_stop = a.honor_stop;
+    c.eigenfreq = a.eigenfreq;
+    cma_eigen_impl<512, true, 1, 5, true>(d, c, EIG_FX_PLAN, 0);
 }
 // 128 < n <= 256 split over workgroups (round 4): the reduction (one workgroup, as before), then the
 // two HALVES of the torn tridiagonal matrix as problems of their own, each by a workgroup with its

@@ -23,6 +23,8 @@
 // dc_prototype.py is the numpy model this file was developed against.
 #pragma once
 
+#include <type_traits>
+
 #include "bbo_cma.hpp"
 #include "bbo_eig_ql.hpp"
 
@@ -548,19 +550,33 @@ __device__ __forceinline__ void dc_secular(const DcWork &W, int k, double rho, i
 // Fg (global) is scratch for the eigenvector factor of this merge (m x m).
 // BIG: instantiations for 256 < n <= 512 (two passes over a level's merges, merges the
 // register-resident product cannot hold); the n <= 256 ones compile exactly as before
-template<int LPR, bool do_gemm, bool BIG = false, bool WIDE = true>
-__device__ inline void dc_merge_level(const DcMat &Q, const DcTeam &tm, int a, int mid, int b,
-        double rho_in, double *dv, double *Fg, const DcWork &W0, long long *stamps,
-        int mlevel = 0, double *Tg = nullptr,     // widest merge of this level; m x m global scratch
-        int part = 0)       // 1: stop before the secular equation, 2: start behind it (cma_eig_secular)
+// MFX > 0 (the fixed-shape kernel, eig_dc_phase<.., FX>): every team of the level is active and
+// merges MFX columns, two blocks of MFX / 2, with MFX / 16 wavefronts; no clocks, no parts -- the
+// same statements with these as constants
+template<int LPR, bool do_gemm, bool BIG = false, bool WIDE = true, int MFX = 0>
+__device__ inline void dc_merge_level(const DcMat &Q, const DcTeam &tm_in, int a, int mid_in, int b,
+        double rho_in, double *dv, double *Fg, const DcWork &W0, long long *stamps_in,
+        int mlevel_in = 0, double *Tg = nullptr,  // widest merge of this level; m x m global scratch
+        int part_in = 0)    // 1: stop before the secular equation, 2: start behind it (cma_eig_secular)
 {
+    DcTeam tm = tm_in;
+    if (MFX) {
+        tm.active = 1;
+        tm.nwaves = MFX / 16;
+        tm.tthreads = 4 * MFX;
+        tm.wave_scope = MFX == 16;
+        tm.sorted_in = MFX > 16;
+    }
+    long long *const stamps = MFX ? nullptr : stamps_in;
+    const int mlevel = MFX ? MFX : mlevel_in, part = MFX ? 0 : part_in;
+    const int mid = MFX ? a + MFX / 2 : mid_in;
 #define MG_STAMP(slot) do { if (stamps && threadIdx.x == 0 && a == 0) stamps[slot] = wall_clock64(); } while (0)
     MG_STAMP(24);
     const int lane = threadIdx.x & 63;
     const int ttid = tm.ttid, TT = tm.tthreads;
     const bool on = tm.active != 0;
     const bool wv = tm.wave_scope != 0;
-    const int m = on ? b - a : 0;
+    const int m = MFX ? MFX : on ? b - a : 0;
     // trips of the binary-search rankings: log2(longest list) + 1, the same for every team
     const int search_trips = 32 - __builtin_clz(max(mlevel > 0 ? mlevel : (BIG ? 512 : 256), 1));
     const double sgn = rho_in >= 0. ? 1. : -1.;
@@ -1355,9 +1371,13 @@ __device__ inline void dc_apply_reflectors(const DcMat &Q, int n, const double *
 // (forceinline: called once with Q in LDS and once with Q in global memory from cma_eigen -- as a
 // shared out-of-line function it would see generic pointers and address everything with FLAT
 // instructions)
-template<int TT = 512, bool BIG = false, bool WIDE = true>
-__device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, double *ev, double *G,
-        double *Bout, int ldb, double *scratch, long long *stamps, int dbg, int ext_top = 0,
+// FX (cma_eigen_fx128: n = 128 in LDS, stashed reflectors, mode 0, no diagnostics): 16 leaves of 8
+// rows, a pair to a wavefront, and four levels of merges of 16, 32, 64 and 128 columns by teams of
+// 1, 2, 4 and 8 wavefronts -- what the statements below arrive at for n = 128 through shared memory,
+// written down as constants (the wavefront's index is a scalar there)
+template<int TT = 512, bool BIG = false, bool WIDE = true, bool FX = false>
+__device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n_in, double *dv, double *ev, double *G,
+        double *Bout, int ldb, double *scratch, long long *stamps_in, int dbg_in, int ext_top = 0,
         const double *hv = nullptr, bool qh_ready = false, double *Tscratch = nullptr, int mode = 0,
         bool t_prebuilt = false,     // (mode 2: the reflector panels' T factors are in place already)
         int top_part = 0, double *Wimg = nullptr)   // (mode 2: 1 = up to the secular equation, the work
@@ -1369,8 +1389,12 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, 
     // 2 = the TOP merge only: the two halves [0, n / 2) and [n / 2, n) arrive solved (dv = their
     //     eigenvalues in ascending order each, Q = their eigenvector blocks, global memory)
 #define DC_STAMP(slot) do { if (stamps && threadIdx.x == 0) stamps[slot] = wall_clock64(); } while (0)
+    static_assert(!FX || (TT == 512 && !BIG && !WIDE), "FX: the 512-thread kernel with the matrix in LDS");
+    const int n = FX ? 128 : n_in, dbg = FX ? 0 : dbg_in;
+    long long *const stamps = FX ? nullptr : stamps_in;
     DC_STAMP(16);
-    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, T = FX ? TT : blockDim.x, lane = tid & 63;
+    const int wave = FX ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     const int NW = T >> 6;
     double *Qh = G;                       // Q_house, n x n row-major
     double *F = G + (size_t) n * n;       // merge factors (one m x m slab per merge)
@@ -1416,6 +1440,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, 
         int ex = 0;
         if (am > 0.) frexp(am, &ex);
         scale_s = am > 0. ? ldexp(1., 1 - ex) : 1.;
+        if (!FX) {
         // blocks of <= leaf_rows rows.  With the matrix in LDS
         // (16 < n <= 128) the leaves are 8 x 8: a QL leaf is a serial chain of ~2 (s^2 / 2)
         // rotations, the extra level of merges -- 16-pole merges, one wavefront each -- costs a
@@ -1427,12 +1452,16 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, 
         int nb = 1;
         while ((n + nb - 1) / nb > leaf_rows && nb < MAXB) nb <<= 1;
         nblk_s = mode == 2 ? 2 : nb;
+        }
     }
     __syncthreads();
-    if (tid <= nblk_s) bounds[tid] = (int) (((long long) tid * n) / nblk_s);
-    __syncthreads();
+    if (!FX) {
+        if (tid <= nblk_s) bounds[tid] = (int) (((long long) tid * n) / nblk_s);
+        __syncthreads();
+    }
     const double scale = scale_s;
-    const int nblk = nblk_s;
+    const int nblk = FX ? 16 : nblk_s;
+    auto bound = [&](int i) { return FX ? 8 * i : bounds[i]; };
     for (int i = tid; i < n; i += T) {
         dv[i] *= scale;
         ev[i] *= scale;
@@ -1450,7 +1479,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, 
     __syncthreads();
     // rank-one tears at the block boundaries (mode 2: the halves were torn before they were solved)
     if (tid >= 1 && tid < nblk && mode != 2) {
-        const int bd = bounds[tid];
+        const int bd = bound(tid);
         const double r = fabs(ev[bd - 1]);
         dv[bd - 1] -= r;
         dv[bd] -= r;
@@ -1466,8 +1495,8 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, 
     } else if (!(dbg & 8) && !(dbg & 524288)) {
         for (int pr = wave; 2 * pr < nblk; pr += NW) {
             const int b0 = 2 * pr, b1 = 2 * pr + 1;
-            const int a0 = bounds[b0], s0 = bounds[b0 + 1] - a0;
-            const int a1 = b1 < nblk ? bounds[b1] : 0, s1 = b1 < nblk ? bounds[b1 + 1] - a1 : 0;
+            const int a0 = bound(b0), s0 = bound(b0 + 1) - a0;
+            const int a1 = b1 < nblk ? bound(b1) : 0, s1 = b1 < nblk ? bound(b1 + 1) - a1 : 0;
             dc_leaf_ql_pair(Q, a0, s0, a1, s1, dv, ev, dv, lane);
         }
     } else
@@ -1486,7 +1515,31 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n, double *dv, 
     // of `bounds` -- read where they are needed.  (Kept in per-thread arrays indexed at run time,
     // the edges lived in scratch memory: 5 us of bookkeeping per level.)
     auto edge = [&](int i, int L) { return bounds[min(i << L, nblk)]; };
-    int nc = nblk;
+    if (FX) {
+        auto level = [&](auto m_tag) {
+            constexpr int M = decltype(m_tag)::value, WPT = M / 16;
+            DcTeam tm;
+            tm.id = wave / WPT;
+            tm.active = 1;
+            tm.wave0 = tm.id * WPT;
+            tm.nwaves = WPT;
+            tm.twave = wave & (WPT - 1);
+            tm.ttid = tid - 64 * tm.wave0;
+            tm.tthreads = 64 * WPT;
+            tm.wave_scope = WPT == 1;
+            tm.sorted_in = M > 16;
+            if (tid == 0) maxnr_s = 0;
+            __syncthreads();
+            const int a = M * tm.id, mid = a + M / 2;
+            dc_merge_level<4, true, false, WIDE, M>(Q, tm, a, mid, a + M, ev[mid - 1], dv, F + (size_t) a * n, W,
+                    nullptr, M, nullptr);
+        };
+        level(std::integral_constant<int, 16>());
+        level(std::integral_constant<int, 32>());
+        level(std::integral_constant<int, 64>());
+        level(std::integral_constant<int, 128>());
+    }
+    int nc = FX ? 1 : nblk;
     // (diagnostic bits 8192 / 16384: stop after the first / second level, so that the phase clocks
     // of dc_merge_level -- the first team's, every level overwrites them -- show THAT level)
     int levels_done = 0;
