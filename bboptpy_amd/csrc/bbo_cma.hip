@@ -625,7 +625,7 @@ void CmaEngine::launch_rank()
     BBO_HIP(hipGetLastError());
 }
 
-void CmaEngine::launch_update()
+void CmaEngine::launch_update(bool with_cov)
 {
     const CmaConst &c = c_;
     if (c.variant == 3) {
@@ -713,7 +713,9 @@ void CmaEngine::launch_update()
         hipLaunchKernelGGL(cma_paths, dim3(c.npop), dim3(256), 0, stream_, d_, c_);
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
-    {
+    // (with_cov == false: the fixed-shape eigensolver that follows forms C on its load, and the slot
+    // is not opened -- a slot without calls is left out of the kernel table)
+    if (with_cov) {
         const int total = c.n * (c.n + 1) / 2;
         dim3 grid((total + 255) / 256, c.npop);
         timer_.begin(stream_, K_COV);
@@ -729,9 +731,31 @@ int CmaEngine::next_mw_xcd()
     return counter.fetch_add(1) & 7;
 }
 
-void CmaEngine::launch_eigen()
+// Which build launch_eigen takes for the reduction: 0 = a generic kernel, 1 = cma_eigen_fx128 (a batch
+// of n = ld = 128 under lazy_isc, production settings: same bits; any diagnostic bit the decomposition
+// reads, a clock request, or bit 2097152 keeps the generic kernel), 2 = cma_eigen_r1_fx128 (the split
+// form's reduction, which has the same build).  generation() asks too: in front of form 1 it leaves
+// cma_cov out, that kernel forms C itself.
+int CmaEngine::eig_fixed_form() const
 {
     const CmaConst &c = c_;
+    if (c.variant >= 2 || c.n != 128 || c.ld != 128) return 0;
+    const EigPlan pl_lds = eig_plan(c.n, c.ld);
+    const bool split128 = pl_lds.use_lds && pl_lds.threads == 512 && pl_lds.dc && c.npop <= split_maxp_
+            && !(d_.dbg & (2 | 4 | 8 | 1024 | 4194304));
+    const int eig_path_bits = 1 | 2 | 4 | 8 | 1024 | 2048 | 8192 | 16384 | 32768 | 524288 | 2097152 | 4194304 | 8388608;
+    const bool fixed_shape = pl_lds.use_lds && pl_lds.dc && pl_lds.reg_path
+            && pl_lds.threads == 512 && pl_lds.lda == EIG_FX_PLAN.lda && pl_lds.rc == EIG_FX_PLAN.rc
+            && pl_lds.lds_bytes == EIG_FX_PLAN.lds_bytes && !d_.stamps && !(d_.dbg & eig_path_bits);
+    if (fixed_shape && c.npop > split_maxp_ && !split128 && c.lazy_isc) return 1;
+    if (fixed_shape && split128 && eig_plan_split(c.n, c.ld).hybrid) return 2;
+    return 0;
+}
+
+void CmaEngine::launch_eigen(bool cov_fused)
+{
+    const CmaConst &c = c_;
+    cov_fused_last_ = false;
     if (c.variant >= 2) return;        // diagonal covariance: d = sqrt(c) is part of sep_paths; Cholesky: no decomposition
     // 64 < n <= 128 with few matrices in flight (one optimisation run at a time): the reduction on
     // one workgroup, the divide and conquer and the reflectors over many -- the structure of
@@ -752,17 +776,14 @@ void CmaEngine::launch_eigen()
             && !(d_.dbg & (2 | 16777216)) && mw_reserve((long) c.npop * 16);
     // n <= 16: a wavefront per matrix (dbg bit 4 keeps the big kernel)
     const bool small = c.n <= 16 && c.n >= 2 && c.ld == 16 && !(d_.dbg & 16);
-    // a batch of n = ld = 128 under lazy_isc, production settings: the fixed-shape build of cma_eigen
-    // (same bits; any diagnostic bit the decomposition reads, a clock request, or bit 2097152 keeps
-    // the generic kernel)
-    const int eig_path_bits = 1 | 2 | 4 | 8 | 1024 | 2048 | 8192 | 16384 | 32768 | 524288 | 2097152 | 4194304 | 8388608;
-    const bool fixed_shape = c.n == 128 && c.ld == 128 && pl_lds.use_lds && pl_lds.dc && pl_lds.reg_path
-            && pl_lds.threads == 512 && pl_lds.lda == EIG_FX_PLAN.lda && pl_lds.rc == EIG_FX_PLAN.rc
-            && pl_lds.lds_bytes == EIG_FX_PLAN.lds_bytes && !d_.stamps && !(d_.dbg & eig_path_bits);
-    const bool fixed128 = fixed_shape && c.npop > split_maxp_ && !split128 && c.lazy_isc;
-    // (the split form's reduction, cma_eigen_r1, has the same build)
-    const bool fixed_r1 = fixed_shape && split128 && pl.hybrid;
-    eig_fixed_last_ = (fixed128 || fixed_r1) && !small;
+    // the fixed-shape builds of n = ld = 128 (eig_fixed_form)
+    const int fixed_form = eig_fixed_form();
+    const bool fixed128 = fixed_form == 1, fixed_r1 = fixed_form == 2;
+    eig_fixed_last_ = fixed_form != 0;
+    BBO_REQUIRE(!cov_fused || fixed128, "C is formed by cma_eigen_fx128 only");
+    cov_fused_last_ = cov_fused;
+    const EigFxArgs fa { d_.C, d_.B, d_.D, d_.BDp, d_.eig_work, d_.scal, c.eigenfreq, c.honor_stop,
+            c.splits, c.variant, d_.gram_part, d_.pc, c.cc, c.c1, c.cmu, c.cneg, c.alphaold };
     if (small)    // (does cma_post's work too: one launch less where launches are what costs)
         hipLaunchKernelGGL(cma_eigen_small, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_, 0,
                 1);
@@ -773,9 +794,13 @@ void CmaEngine::launch_eigen()
         hipLaunchKernelGGL(cma_eigen_256, dim3(c.npop), dim3(256), pl.lds_bytes, stream_, d_, c_,
                 pl, 0);
     else if (fixed128) {
+        // (cov_fused: no cma_cov launch has gone before, the kernel forms C from the Gram slabs itself)
         allow_lds((const void*) cma_eigen_fx128, 160 * 1024 - 768);
-        const EigFxArgs fa { d_.C, d_.B, d_.D, d_.BDp, d_.eig_work, d_.scal, c.eigenfreq, c.honor_stop };
-        hipLaunchKernelGGL(cma_eigen_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
+        allow_lds((const void*) cma_eigen_fx128u, 160 * 1024 - 768);
+        if (cov_fused)
+            hipLaunchKernelGGL(cma_eigen_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
+        else
+            hipLaunchKernelGGL(cma_eigen_fx128u, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
     } else if (pl.use_lds)
         hipLaunchKernelGGL(cma_eigen, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_,
                 pl, 0);
@@ -797,7 +822,6 @@ void CmaEngine::launch_eigen()
         const bool use_mw = !split128 && !mw_disabled_ && !(d_.dbg & 16777216) && mw_reserve((long) c.npop * MW_G);
         if (split128 && fixed_r1) {
             allow_lds((const void*) cma_eigen_r1_fx128, 160 * 1024 - 768);
-            const EigFxArgs fa { d_.C, d_.B, d_.D, d_.BDp, d_.eig_work, d_.scal, c.eigenfreq, c.honor_stop };
             hipLaunchKernelGGL(cma_eigen_r1_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
         } else if (split128) {
             allow_lds((const void*) cma_eigen_r1, 160 * 1024 - 768);
@@ -981,8 +1005,11 @@ void CmaEngine::generation(bool honor_stop)
     if (obj_.needs_host()) host_evaluate();
     else if (obj_.is_program()) program_evaluate();
     launch_rank();
-    launch_update();
-    launch_eigen();
+    // n = ld = 128 in front of cma_eigen_fx128: that kernel forms C on its load, no cma_cov launch
+    // (diagnostic bit 32 keeps the pair; phase() always launches it)
+    const bool fuse_cov = eig_fixed_form() == 1 && !(d_.dbg & 32);
+    launch_update(!fuse_cov);
+    launch_eigen(fuse_cov);
     launch_history_stop();
 }
 
@@ -1255,6 +1282,8 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "eig_mw_off") return o.one(mw_disabled_ ? 1 : 0);
     if (k == "eig_split_maxp") return o.one(split_maxp_);
     if (k == "eig_fixed128") return o.one(eig_fixed_last_ ? 1 : 0);       // the last decomposition took a fixed-shape kernel
+    if (k == "cov_fused") return o.one(cov_fused_last_ ? 1 : 0);          // the last generation formed C inside it
+    if (k == "splits") return o.one(c.splits);                            // Gram slabs per population
     if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups
         MwBudget &b = MwBudget::get();

@@ -134,8 +134,9 @@ private:
     void launch_sample_eval();
     void launch_post(int mode);
     void launch_rank();
-    void launch_update();
-    void launch_eigen();
+    void launch_update(bool with_cov = true);
+    void launch_eigen(bool cov_fused = false);
+    int eig_fixed_form() const;
     void launch_history_stop();
     void host_evaluate();
     void program_evaluate();
@@ -156,6 +157,7 @@ private:
     bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
     bool eig_fixed_last_ = false;      // the last launch_eigen took the fixed-shape kernel (get "eig_fixed128")
+    bool cov_fused_last_ = false;      // the last generation formed C inside the eigensolver (get "cov_fused")
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;
 

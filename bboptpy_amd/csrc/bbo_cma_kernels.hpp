@@ -1610,10 +1610,9 @@ __device__ __forceinline__ void cov_body(const CmaDev &d, const CmaConst &c, int
     double *C = d.C + (size_t) p * ld * ld;
     const double *pc = d.pc + (size_t) p * ld;
     const double cij = C[(size_t) i * ld + j];
-    const double c2 = (1. - sc->hsig) * c.cc * (2. - c.cc);
-    const double decay = c.variant == 1 ? (1. - c.c1 - c.cmu + c.cneg * c.alphaold)
-                                        : (1. - c.c1 - c.cmu);
-    double sum = decay * cij + c.c1 * (pc[i] * pc[j] + c2 * cij);
+    // (the element's formula: shared with the prologue of the fixed-shape eigensolvers, bbo_eig.hpp)
+    const CovCoef k = cov_coef(c, sc->hsig);
+    double sum = cov_elem(k, cij, pc[i], pc[j]);
     const double *G = d.gram_part + (size_t) p * c.splits * ld * ld + (size_t) i * ld + j;
     double g = 0.;
     {

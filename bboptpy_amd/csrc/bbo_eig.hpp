@@ -124,6 +124,24 @@ inline EigPlan eig_plan_split(int n, int ld)
     return pl;
 }
 
+// One element of the covariance update before its Gram slabs are added (active_cmaes.cpp:137-160):
+// decay C_ij + c1 (pc_i pc_j + c2 C_ij).  cov_body (bbo_cma_kernels.hpp) and the prologue of the
+// fixed-shape eigensolvers below both call these two, so the forms cannot drift apart.
+struct CovCoef {
+    double c1, c2, decay;
+};
+__device__ __forceinline__ CovCoef cov_coef(const CmaConst &c, int hsig)
+{
+    const double c2 = (1. - hsig) * c.cc * (2. - c.cc);
+    const double decay = c.variant == 1 ? (1. - c.c1 - c.cmu + c.cneg * c.alphaold)
+                                        : (1. - c.c1 - c.cmu);
+    return CovCoef { c.c1, c2, decay };
+}
+__device__ __forceinline__ double cov_elem(const CovCoef &k, double cij, double pci, double pcj)
+{
+    return k.decay * cij + k.c1 * (pci * pcj + k.c2 * cij);
+}
+
 // Straight-line pieces of the register-resident tred2, specialised on how many 32-column
 // groups the active block still covers (a guard inside the unrolled loops would split them into
 // basic blocks and serialise the LDS reads they issue).
@@ -1091,6 +1109,98 @@ __device__ inline void eig_tred_sym256(const double *C, int ld, int n, const Eig
     __syncthreads();
 }
 
+// The prologue of the fixed-shape eigensolvers (n = ld = 128, round 8): the workgroup that is about
+// to decompose a population's C forms it first -- what cma_cov computes, element for element
+// (cov_coef / cov_elem, then the Gram slabs in ascending order from 0., then sum += g) -- into the
+// LDS matrix that becomes the reflector stash, mirrored, and writes it to global memory in whole
+// rows; the reduction then loads its registers from the LDS copy.  Rows are walked directly: wavefront
+// w takes rows w, w + 8, ..; a row below 64 is one element per lane, a row from 64 on two, which makes
+// 24 elements per thread in two batches of 12 (each batch: its 12 loads of C and the first two slabs'
+// 24 in flight together; with more slabs, four at a time).
+template<int TT>
+__device__ inline void eig_cov_prologue128(const CmaDev &d, const CmaConst &c, const CmaScal *sc, int p,
+        double *As, int tid)
+{
+    constexpr int N = 128, LB = eig_plan(128, 128).lda, EPT = 12;
+    double *C = d.C + (size_t) p * N * N;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const double *pc = d.pc + (size_t) p * N;
+    const int splits = c.splits;
+    const double *G = d.gram_part + (size_t) p * splits * N * N;
+    const CovCoef k = cov_coef(c, sc->hsig);
+    const double pcl0 = pc[lane], pcl1 = pc[lane + 64];
+    static_assert(24 % EPT == 0, "eig_cov_prologue128: 24 elements per thread");
+#pragma unroll
+    for (int e0 = 0; e0 < 24; e0 += EPT) {
+        int off[EPT];
+        bool ok[EPT];
+        double cij[EPT], pci[EPT], g[EPT];
+#pragma unroll
+        for (int u = 0; u < EPT; u++) {
+            const int e = e0 + u;
+            const int i = e < 8 ? wave + 8 * e : 64 + wave + 8 * ((e - 8) >> 1);
+            const int j = e < 8 ? lane : lane + 64 * ((e - 8) & 1);
+            ok[u] = j <= i;
+            off[u] = i * N + j;
+            cij[u] = ok[u] ? C[off[u]] : 0.;
+            pci[u] = pc[i];
+            g[u] = 0.;
+        }
+        int s = 0;
+        for (; s + 4 <= splits; s += 4) {     // (ascending, as cov_body adds them)
+            double x[4][EPT];
+#pragma unroll
+            for (int u = 0; u < EPT; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) x[v][u] = ok[u] ? G[(size_t) (s + v) * N * N + off[u]] : 0.;
+#pragma unroll
+            for (int u = 0; u < EPT; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) g[u] += x[v][u];
+        }
+        if (s + 2 <= splits) {
+            double x0[EPT], x1[EPT];
+#pragma unroll
+            for (int u = 0; u < EPT; u++) {
+                x0[u] = ok[u] ? G[(size_t) s * N * N + off[u]] : 0.;
+                x1[u] = ok[u] ? G[(size_t) (s + 1) * N * N + off[u]] : 0.;
+            }
+#pragma unroll
+            for (int u = 0; u < EPT; u++) {
+                g[u] += x0[u];
+                g[u] += x1[u];
+            }
+            s += 2;
+        }
+        if (s < splits) {
+            double x0[EPT];
+#pragma unroll
+            for (int u = 0; u < EPT; u++) x0[u] = ok[u] ? G[(size_t) s * N * N + off[u]] : 0.;
+#pragma unroll
+            for (int u = 0; u < EPT; u++) g[u] += x0[u];
+        }
+#pragma unroll
+        for (int u = 0; u < EPT; u++) {
+            const int e = e0 + u;
+            const int i = e < 8 ? wave + 8 * e : 64 + wave + 8 * ((e - 8) >> 1);
+            const int h = e < 8 ? 0 : ((e - 8) & 1);
+            const int j = lane + 64 * h;
+            double sum = cov_elem(k, cij[u], pci[u], h ? pcl1 : pcl0);
+            sum += g[u];
+            if (ok[u]) {
+                As[i * LB + j] = sum;
+                As[j * LB + i] = sum;
+            }
+        }
+    }
+    __syncthreads();
+    // the new C, both halves, from LDS: a row per 64 threads at a time, 16 bytes per lane
+    for (int q = tid; q < N * (N / 2); q += TT) {
+        const int r = q >> 6, c2 = (q & 63) * 2;
+        *reinterpret_cast<double2*>(&C[r * N + c2]) = make_double2(As[r * LB + c2], As[r * LB + c2 + 1]);
+    }
+}
+
 // LDSM: the work matrix A (reflector stash, then the eigenvector blocks of the divide and conquer)
 // lives in LDS (pl.use_lds) -- a COMPILE-TIME fact here.  As the run-time choice
 // `pl.use_lds ? LDS : global` the pointer is generic and every access to A -- each rotation of a QL
@@ -1104,13 +1214,17 @@ __device__ inline void eig_tred_sym256(const double *C, int ld, int n, const Eig
 // on the diagonal of the work matrix), the reflectors' T factors and the closing repair / root.
 // FX (cma_eigen_fx128): n = ld = 128, no diagnostics -- the caller passes d, c and pl as constants and
 // the divide and conquer takes its block structure as compile-time facts (eig_dc_phase)
-template<int TT, bool LDSM, int HYB = 1, int STAGE = 0, bool FX = false>
+// PRO (cma_eigen_fx128 only): eig_cov_prologue128 in front of the reduction -- the kernel forms C, no
+// cma_cov launch has gone before it
+template<int TT, bool LDSM, int HYB = 1, int STAGE = 0, bool FX = false, bool PRO = false>
 __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &c, const EigPlan &pl,
         int force)
 {
     const int p = blockIdx.x;
     CmaScal *sc = d.scal + p;
     if (c.honor_stop && sc->stop != 0) return;
+    // (a fused prologue runs whether or not the decomposition is due, as cma_cov did)
+    bool due = true;
     if (STAGE == 2 || STAGE == 4) {
         if (sc->eig_stage != 1) return;
     } else if (STAGE == 3) {
@@ -1122,7 +1236,8 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
             sc->eigen_done = 0;
             sc->eig_stage = 0;
         }
-        return;
+        if (!PRO) return;
+        due = false;
     }
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, T = TT, lane = tid & 63, wave = tid >> 6;
@@ -1198,7 +1313,13 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
         }
         __syncthreads();
     } else {
-    if (LDSM) {      // (use_lds implies the register-resident reduction: n <= 128)
+    if (PRO) {
+        // (the matrix comes from the LDS block that becomes the stash, as in STAGE 3)
+        eig_cov_prologue128<TT>(d, c, sc, p, A.a, tid);
+        if (!due) return;
+        eig_tred_accum_reg128<TT>(A.a, A.ld, n, A, dv, ev, uv, wv, gv, hvec, td, tid, nullptr, A.a, A.ld, true,
+                !(pl.dc && !(d.dbg & 2)));
+    } else if (LDSM) {      // (use_lds implies the register-resident reduction: n <= 128)
         // (with the D&C stage the reflectors stay stashed in A: eig_dc_phase applies them to the
         // tridiagonal eigenvectors in blocked form on the matrix cores)
         eig_tred_accum_reg128<TT>(C, ld, n, A, dv, ev, uv, wv, gv, hvec, td, tid,
@@ -1402,14 +1523,31 @@ __global__ __launch_bounds__(512) void cma_eigen_b(CmaDev d, CmaConst c, EigPlan
 // dimension and its strides, the plan, the diagnostic switches, the clocks, the 16 leaves of 8 and
 // the merge widths 16, 32, 64, 128 -- a compile-time fact, and the handful of pointers and scalars
 // it reads as its only arguments (CmaDev, CmaConst and EigPlan by value were 258 spilled SGPRs).
+// (round 8: the covariance update's inputs too -- cma_eigen_fx128 forms C itself, eig_cov_prologue128)
 struct EigFxArgs {
     double *C, *B, *D, *BDp, *eig_work;
     CmaScal *scal;
     double eigenfreq;
     int honor_stop;
+    int splits, variant;
+    const double *gram_part, *pc;
+    double cc, c1, cmu, cneg, alphaold;
 };
+__device__ __forceinline__ void eig_fx_cov_args(const EigFxArgs &a, CmaDev &d, CmaConst &c)
+{
+    d.gram_part = const_cast<double*>(a.gram_part);
+    d.pc = const_cast<double*>(a.pc);
+    c.splits = a.splits;
+    c.variant = a.variant;
+    c.cc = a.cc;
+    c.c1 = a.c1;
+    c.cmu = a.cmu;
+    c.cneg = a.cneg;
+    c.alphaold = a.alphaold;
+}
 constexpr EigPlan EIG_FX_PLAN = eig_plan(128, 128);
-__global__ __launch_bounds__(512) void cma_eigen_fx128(EigFxArgs a)
+template<bool PRO>
+__device__ __forceinline__ void cma_eigen_fx128_body(const EigFxArgs &a)
 {
     static_assert(EIG_FX_PLAN.use_lds == 1 && EIG_FX_PLAN.dc == 1 && EIG_FX_PLAN.reg_path == 1
             && EIG_FX_PLAN.threads == 512 && EIG_FX_PLAN.vl == 130, "cma_eigen_fx128: the plan of n = 128");
@@ -1425,9 +1563,22 @@ __global__ __launch_bounds__(512) void cma_eigen_fx128(EigFxArgs a)
     c.lazy_isc = 1;
     c.honor_stop = a.honor_stop;
     c.eigenfreq = a.eigenfreq;
-    cma_eigen_impl<512, true, 1, 0, true>(d, c, EIG_FX_PLAN, 0);
+    if (PRO) eig_fx_cov_args(a, d, c);
+    cma_eigen_impl<512, true, 1, 0, true, PRO>(d, c, EIG_FX_PLAN, 0);
 }
-// (the same build of cma_eigen_r1, the reduction of the split form for at most eig_split_maxp matrices)
+// (in a generation: C formed on the load, no cma_cov launch in front)
+__global__ __launch_bounds__(512) void cma_eigen_fx128(EigFxArgs a)
+{
+    cma_eigen_fx128_body<true>(a);
+}
+// (behind cma_cov: phase(), diagnostic bit 32)
+__global__ __launch_bounds__(512) void cma_eigen_fx128u(EigFxArgs a)
+{
+    cma_eigen_fx128_body<false>(a);
+}
+// (the same build of cma_eigen_r1, the reduction of the split form for at most eig_split_maxp matrices;
+// always behind cma_cov: one workgroup summing a single population's 32 slabs is slower than the 33
+// workgroups of cma_cov)
 __global__ __launch_bounds__(512) void cma_eigen_r1_fx128(EigFxArgs a)
 {
     CmaDev d {};
