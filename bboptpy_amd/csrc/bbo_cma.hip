@@ -478,9 +478,8 @@ void CmaEngine::launch_sample_eval()
             // wavefronts) per CU up to ld = 1024
             const size_t lds = (size_t) 8 * c.ld * sizeof(double);
             const dim3 grid(std::min((c.lambda_pad + 7) / 8, per_pop), c.npop);
-            if (c.n == c.ld && !c.bound && c.lambda == c.lambda_pad && !d_.zinject
-                    && !d_.zrecord && !(d_.dbg & 256)) {   // nothing to guard (the benchmark's SEP)
-                if (sep_sum_objective(c.obj) && !(d_.dbg & 1048576)) {
+            if (nothing_to_guard()) {   // (the benchmark's SEP)
+                if (sep_sum_objective(c.obj) && !(d_.dbg & DBG_SEP_ROWS_LDS)) {
                     // sums of per-coordinate terms: no row in LDS (sep_sample_sum); 256-thread
                     // workgroups, as many rows in flight as the registers allow
                     const dim3 sgrid(std::min(c.lambda_pad / (4 * SEP_K), per_pop), c.npop);
@@ -532,8 +531,7 @@ void CmaEngine::launch_sample_eval()
         allow_lds((const void*) cma_sample_eval128, 128 * 1024);
         dim3 grid((c.lambda_pad + rw - 1) / rw, c.npop);
         // the lean build of the tile loop where nothing needs guarding (M, C3)
-        const int full = (c.n == 128 && !c.bound && c.lambda == c.lambda_pad && !d_.zinject
-                && !d_.zrecord && !(d_.dbg & 256)) ? 1 : 0;
+        const int full = nothing_to_guard() ? 1 : 0;
         if (c.variant == 3 && chol_tri_) {      // (lower-triangular operand: 36 of 64 block pairs)
             allow_lds((const void*) cma_sample_eval128_tri, 128 * 1024);
             hipLaunchKernelGGL(cma_sample_eval128_tri, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
@@ -572,7 +570,7 @@ void CmaEngine::launch_sample_eval()
         const size_t lds = (size_t) 16 * (c.ld + 2) * sizeof(double);
         allow_lds((const void*) cma_sample_eval<8>, 80 * 1024);   // ld = 512: 65 792 bytes
         // a handful of row tiles on the whole chip (C5: two): one column tile per wavefront
-        if ((long) grid.x * grid.y <= 32 && c.ld <= 256 && !(d_.dbg & 268435456))
+        if ((long) grid.x * grid.y <= 32 && c.ld <= 256 && !(d_.dbg & DBG_SAMPLE_4WAVES))
             hipLaunchKernelGGL((cma_sample_eval<1, 16>), grid, dim3(1024), lds, stream_, d_, c_);
         else
             switch (pick_maxt(c.ld)) {
@@ -611,10 +609,10 @@ void CmaEngine::launch_rank()
         rank_wrote_norms_ = c.variant == 1 && c.use_zn && !basis_maybe_stale_;
     } else {
         // few candidates in flight: 8 per workgroup, 32 slices each (a quarter of the 64-bit compares
-        // per thread; diagnostic bit 128 keeps the 32-candidate form -- the same counts)
-        if ((long) c.npop * ((c.lambda + 31) / 32) <= 256 && c.lambda >= 2048 && !(d_.dbg & (128 | 4096)))
+        // per thread; DBG_RANK_COUNT32 keeps the 32-candidate form -- the same counts)
+        if ((long) c.npop * ((c.lambda + 31) / 32) <= 256 && c.lambda >= 2048 && !(d_.dbg & (DBG_RANK_COUNT32 | DBG_RANK_COUNT_NO64)))
             hipLaunchKernelGGL(cma_rank64, dim3((c.lambda + 3) / 4, c.npop), dim3(256), 0, stream_, d_, c_);
-        else if ((long) c.npop * ((c.lambda + 31) / 32) <= 512 && c.lambda >= 512 && !(d_.dbg & 128))
+        else if ((long) c.npop * ((c.lambda + 31) / 32) <= 512 && c.lambda >= 512 && !(d_.dbg & DBG_RANK_COUNT32))
             hipLaunchKernelGGL(cma_rank32, dim3((c.lambda + 7) / 8, c.npop), dim3(256), 0, stream_, d_, c_);
         else
             hipLaunchKernelGGL(cma_rank, dim3((c.lambda + 31) / 32, c.npop), dim3(256), 0, stream_, d_, c_);
@@ -686,7 +684,7 @@ void CmaEngine::launch_update(bool with_cov)
         const size_t lds = (size_t) (2 * G128_CH * G128_LDY + 4 * G128_CH) * sizeof(double);
         allow_lds((const void*) cma_gram128, 80 * 1024);
         timer_.begin(stream_, K_GRAM);
-        if (d_.dbg & 512)   // (diagnostic: the LDS-staged form, same bits)
+        if (d_.dbg & DBG_GRAM128_LDS)   // (diagnostic: the LDS-staged form, same bits)
             hipLaunchKernelGGL(cma_gram128, dim3(c.splits, c.npop), dim3(256), lds, stream_, d_, c_);
         else
             hipLaunchKernelGGL(cma_gram128s, dim3(c.splits, c.npop), dim3(256), 0, stream_, d_, c_);
@@ -704,7 +702,7 @@ void CmaEngine::launch_update(bool with_cov)
         BBO_HIP(hipGetLastError());
     }
     timer_.begin(stream_, K_PATHS);
-    if (c.lazy_isc && c.n >= 64 && !(d_.dbg & 131072))
+    if (c.lazy_isc && c.n >= 64 && !(d_.dbg & DBG_PATHS_LAZY256))
         // (1024 threads: a quarter of the dependent round trips of the two passes over B)
         hipLaunchKernelGGL(cma_paths_lazy1k, dim3(c.npop), dim3(1024), 0, stream_, d_, c_);
     else if (c.lazy_isc)
@@ -731,201 +729,195 @@ int CmaEngine::next_mw_xcd()
     return counter.fetch_add(1) & 7;
 }
 
-// Which build launch_eigen takes for the reduction: 0 = a generic kernel, 1 = cma_eigen_fx128 (a batch
-// of n = ld = 128 under lazy_isc, production settings: same bits; any diagnostic bit the decomposition
-// reads, a clock request, or bit 2097152 keeps the generic kernel), 2 = cma_eigen_r1_fx128 (the split
-// form's reduction, which has the same build).  generation() asks too: in front of form 1 it leaves
-// cma_cov out, that kernel forms C itself.
-int CmaEngine::eig_fixed_form() const
+// What one decomposition launches, from the engine's constants and switches alone: nothing is launched,
+// allocated or reserved here.  launch_eigen walks the result; generation() asks first, because in front
+// of a route that forms C it leaves cma_cov out -- one function, so the two cannot disagree.
+EigRoute CmaEngine::eig_route(bool spread_ok, bool fuse_ok) const
 {
     const CmaConst &c = c_;
-    if (c.variant >= 2 || c.n != 128 || c.ld != 128) return 0;
+    const int dbg = d_.dbg;
+    EigRoute r {};
+    if (c.variant >= 2) return r;      // diagonal covariance: d = sqrt(c) is part of sep_paths; Cholesky: no decomposition
+    auto add = [&r](EigKernel k, int arg = 0) { r.step[r.count++] = EigRoute::Step { k, arg }; };
+    // 64 < n <= 128 with few matrices in flight (one optimisation run at a time): split over kernels the
+    // way 128 < n <= 256 is (DBG_EIG_ONE_WG: everything on the reducing workgroup, as for a batch)
     const EigPlan pl_lds = eig_plan(c.n, c.ld);
-    const bool split128 = pl_lds.use_lds && pl_lds.threads == 512 && pl_lds.dc && c.npop <= split_maxp_
-            && !(d_.dbg & (2 | 4 | 8 | 1024 | 4194304));
-    const int eig_path_bits = 1 | 2 | 4 | 8 | 1024 | 2048 | 8192 | 16384 | 32768 | 524288 | 2097152 | 4194304 | 8388608;
-    const bool fixed_shape = pl_lds.use_lds && pl_lds.dc && pl_lds.reg_path
-            && pl_lds.threads == 512 && pl_lds.lda == EIG_FX_PLAN.lda && pl_lds.rc == EIG_FX_PLAN.rc
-            && pl_lds.lds_bytes == EIG_FX_PLAN.lds_bytes && !d_.stamps && !(d_.dbg & eig_path_bits);
-    if (fixed_shape && c.npop > split_maxp_ && !split128 && c.lazy_isc) return 1;
-    if (fixed_shape && split128 && eig_plan_split(c.n, c.ld).hybrid) return 2;
-    return 0;
+    r.split = pl_lds.use_lds && pl_lds.threads == 512 && pl_lds.dc && c.npop <= split_maxp_
+            && !(dbg & (DBG_QL | DBG_DC_NO_MERGES | DBG_DC_NO_LEAVES | DBG_TRED_L2 | DBG_EIG_ONE_WG));
+    const EigPlan pl = r.split ? eig_plan_split(c.n, c.ld) : pl_lds;
+    spread_ok = spread_ok && !mw_disabled_;
+    // the fixed-shape builds of n = ld = 128 (plan: EIG_FX_PLAN = eig_plan(128, 128)) read no switch and
+    // write no clock: production settings only
+    const bool fixed_shape = c.n == 128 && c.ld == 128 && !d_.stamps
+            && !(dbg & (DBG_EIG_IN_KERNEL | DBG_EIG_GENERIC128));
+    bool big_spread = false, wy4_packs = false, fcols_closed = false;
+    if (c.n <= 16 && c.n >= 2 && c.ld == 16 && !(dbg & DBG_NO_EIGEN_SMALL))
+        add(EK_EIGEN_SMALL);
+    else if (pl.threads < 512)    // four lanes per row: smaller matrices, smaller workgroups, several per CU
+        add(pl.threads == 128 ? EK_EIGEN_128 : EK_EIGEN_256);
+    else if (fixed_shape && c.npop > split_maxp_ && c.lazy_isc) {
+        // a batch: in a generation (DBG_COV_UNFUSED aside) the kernel forms C from the Gram slabs itself
+        r.fixed = true;
+        r.forms_c = fuse_ok && !(dbg & DBG_COV_UNFUSED);
+        add(r.forms_c ? EK_EIGEN_FX128 : EK_EIGEN_FX128U);
+    } else if (pl.use_lds)
+        add(EK_EIGEN);
+    else if (pl.hybrid && !(dbg & (DBG_QL | DBG_TRED_L2 | DBG_EIG_ONE_WG))) {
+        // 128 < n <= 256 and the split form: reduction, the two halves side by side, top merge.  The
+        // reduction of n > 128 is spread while all its workgroups can be resident at once next to those
+        // of the process's other engines (they wait for each other: MwBudget above, bbo_eig_mw.hpp)
+        if (r.split) {
+            r.fixed = fixed_shape;
+            add(r.fixed ? EK_EIGEN_R1_FX128 : EK_EIGEN_R1);
+        } else if (spread_ok && !(dbg & DBG_TRED_ONE_WG)) {
+            r.mw_workgroups = (long) c.npop * MW_G;
+            const int istop = (dbg & DBG_TRED_ALL_SPREAD) ? 1 : 128;
+            add(EK_TRED_MW, istop);
+            if (istop > 1) add(EK_TRED_TAIL);
+        } else
+            add(EK_EIGEN_G1);
+        add(EK_EIG_HALVES);
+        // the top merge: with few matrices in flight the secular equation on workgroups of its own
+        if ((long) c.npop * 8 <= 256 && !(dbg & DBG_TOP_ONE_KERNEL)) {
+            add(EK_EIGEN_G2, 1);
+            add(EK_EIG_SECULAR);
+            // ... and behind it the Loewner vector and the columns of F, the closing repair / root with
+            // them (even n: the T factors were built beside the halves)
+            fcols_closed = !(c.n & 1) && c.lazy_isc && (long) c.npop * ((c.n + 15) / 16) <= 256
+                    && !(dbg & (DBG_TOP_PART2 | DBG_WY_PER_WAVE));
+            if (fcols_closed) {
+                add(EK_EIG_LOWNER);
+                add(EK_EIG_FCOLS);
+            } else
+                add(EK_EIGEN_G2, 2);
+        } else
+            add(EK_EIGEN_G2, 0);
+    } else if (pl.hybrid)
+        add(EK_EIGEN_G);          // (everything in one workgroup)
+    else if (c.n > 256 && pl.dc && spread_ok && !(dbg & (DBG_QL | DBG_TRED_ONE_WG))) {
+        // 256 < n <= 512, few matrices (while 16 workgroups per matrix fit the chip at once): the
+        // structure of 128 < n <= 256 in front of the same divide and conquer; two spread kernels, down
+        // to pivot row 256 and to 128 (DBG_TRED_ALL_SPREAD: the first one down to row 128)
+        big_spread = true;
+        r.mw_workgroups = (long) c.npop * 16;
+        const bool chain = !(dbg & DBG_TRED_ALL_SPREAD);
+        add(EK_TRED_MW512, chain ? 256 : 128);
+        if (chain) add(EK_TRED_MW_CHAIN);
+        add(EK_TRED_TAIL, chain ? 1 : 0);
+        add(EK_EIGEN_B4);
+    } else
+        add(EK_EIGEN_B);
+    r.timed = r.count;
+    if (pl.dc && !pl.reg_path && (pl.hybrid || !(dbg & DBG_QL))) {
+        // n > 128: the top merge's two products as whole-GPU kernels (few populations: 64 x 16 blocks)
+        const long blocks = (c.n + 63) / 64;
+        add(blocks * blocks * c.npop < 128 ? EK_EIG_GEMM1 : EK_EIG_GEMM, 0);
+        if (big_spread)
+            add(EK_EIG_WY4_512);
+        else if ((dbg & DBG_QL) || !pl.hybrid)     // (n > 256, QL: Q_house was accumulated by the reduction)
+            add(EK_EIG_GEMM, 1);
+        else if ((long) c.npop * ((c.n + 15) / 16) <= 256 && !(dbg & DBG_WY_PER_WAVE)) {
+            // (under lazy_isc the packed operand B D leaves with B: no cma_post launch)
+            wy4_packs = c.lazy_isc != 0;
+            add(EK_EIG_WY4, wy4_packs ? (fcols_closed ? 2 : 1) : 0);
+        } else
+            add(EK_EIG_WY);
+    }
+    // (lazy_isc: the eigensolver has written the packed B D itself and C^-1/2 is not formed)
+    const bool packed_by_eigen = c.lazy_isc && pl.dc && pl.reg_path && !(dbg & DBG_QL);
+    r.post = r.step[0].k != EK_EIGEN_SMALL && !packed_by_eigen && !wy4_packs;
+    if (r.post) add(c.ld <= 128 ? EK_POST_MFMA : EK_POST);
+    return r;
 }
 
-void CmaEngine::launch_eigen(bool cov_fused)
+void CmaEngine::launch_eigen(EigRoute r)
 {
     const CmaConst &c = c_;
-    cov_fused_last_ = false;
-    if (c.variant >= 2) return;        // diagonal covariance: d = sqrt(c) is part of sep_paths; Cholesky: no decomposition
-    // 64 < n <= 128 with few matrices in flight (one optimisation run at a time): the reduction on
-    // one workgroup, the divide and conquer and the reflectors over many -- the structure of
-    // 128 < n <= 256 (diagnostic bit 4194304: everything on the reducing workgroup, as for a batch)
-    const EigPlan pl_lds = eig_plan(c.n, c.ld);
-    const bool split128 = pl_lds.use_lds && pl_lds.threads == 512 && pl_lds.dc && c.npop <= split_maxp_
-            && !(d_.dbg & (2 | 4 | 8 | 1024 | 4194304));
-    const EigPlan pl = split128 ? eig_plan_split(c.n, c.ld) : pl_lds;
-    bool wy4_packs = false, fcols_closed = false;
-    allow_lds((const void*) cma_eigen, 160 * 1024 - 768);
-    allow_lds((const void*) cma_eigen_g, 160 * 1024 - 768);
-    allow_lds((const void*) cma_eigen_b, 160 * 1024 - 768);
-    allow_lds((const void*) cma_eigen_256, 160 * 1024 - 768);
-    allow_lds((const void*) cma_eigen_128, 160 * 1024 - 768);
-    timer_.begin(stream_, K_EIGEN);
-    // (256 < n <= 512 by the spread reduction: while its 16 workgroups per matrix fit the chip at once)
-    const bool big_spread = c.n > 256 && pl.dc && !pl.hybrid && !mw_disabled_
-            && !(d_.dbg & (2 | 16777216)) && mw_reserve((long) c.npop * 16);
-    // n <= 16: a wavefront per matrix (dbg bit 4 keeps the big kernel)
-    const bool small = c.n <= 16 && c.n >= 2 && c.ld == 16 && !(d_.dbg & 16);
-    // the fixed-shape builds of n = ld = 128 (eig_fixed_form)
-    const int fixed_form = eig_fixed_form();
-    const bool fixed128 = fixed_form == 1, fixed_r1 = fixed_form == 2;
-    eig_fixed_last_ = fixed_form != 0;
-    BBO_REQUIRE(!cov_fused || fixed128, "C is formed by cma_eigen_fx128 only");
-    cov_fused_last_ = cov_fused;
+    // (no reservation: the one-workgroup reduction; no spread route forms C, so fuse_ok as asked)
+    if (r.mw_workgroups && !mw_reserve(r.mw_workgroups)) r = eig_route(false, r.forms_c);
+    last_route_ = r;
+    if (c.variant >= 2) return;
+    const EigPlan pl_lds = eig_plan(c.n, c.ld), pl = r.split ? eig_plan_split(c.n, c.ld) : pl_lds;
     const EigFxArgs fa { d_.C, d_.B, d_.D, d_.BDp, d_.eig_work, d_.scal, c.eigenfreq, c.honor_stop,
             c.splits, c.variant, d_.gram_part, d_.pc, c.cc, c.c1, c.cmu, c.cneg, c.alphaold };
-    if (small)    // (does cma_post's work too: one launch less where launches are what costs)
-        hipLaunchKernelGGL(cma_eigen_small, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_, 0,
-                1);
-    else if (pl.threads == 128)   // four lanes per row: smaller matrices, smaller workgroups,
-        hipLaunchKernelGGL(cma_eigen_128, dim3(c.npop), dim3(128), pl.lds_bytes, stream_, d_, c_,
-                pl, 0);             // several of them per CU
-    else if (pl.threads == 256)
-        hipLaunchKernelGGL(cma_eigen_256, dim3(c.npop), dim3(256), pl.lds_bytes, stream_, d_, c_,
-                pl, 0);
-    else if (fixed128) {
-        // (cov_fused: no cma_cov launch has gone before, the kernel forms C from the Gram slabs itself)
-        allow_lds((const void*) cma_eigen_fx128, 160 * 1024 - 768);
-        allow_lds((const void*) cma_eigen_fx128u, 160 * 1024 - 768);
-        if (cov_fused)
-            hipLaunchKernelGGL(cma_eigen_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
-        else
-            hipLaunchKernelGGL(cma_eigen_fx128u, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
-    } else if (pl.use_lds)
-        hipLaunchKernelGGL(cma_eigen, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_,
-                pl, 0);
-    else if (pl.hybrid && !(d_.dbg & (2 | 1024 | 4194304))) {
-        // 128 < n <= 256: reduction, the two halves side by side (eigenvector blocks in LDS), top
-        // merge -- three launches (diagnostic bit 4194304: everything in one workgroup, round 3)
-        const EigPlan plh = eig_plan(128, 128);
-        allow_lds((const void*) cma_eigen_g1, 160 * 1024 - 768);
-        allow_lds((const void*) cma_eigen_g2, 160 * 1024 - 768);
-        allow_lds((const void*) cma_eig_halves, 160 * 1024 - 768);
-        // the reduction: its first n - 128 steps spread over MW_G workgroups per matrix (2.8 us per
-        // step, an exchange between compute units each, where the one-workgroup step with the whole
-        // active matrix on chip costs ~5), the leading 128 x 128 block then on one workgroup
-        // (1.15 us per step): 0.35 against 0.36 ms per decomposition at n = 132, 0.63 / 0.73 at 200,
-        // 0.83 / 1.04 at 256 -- while all of a launch's workgroups (256 threads, 277 registers per
-        // lane: ONE per compute unit) can be resident at once next to those of the process's other
-        // engines (they wait for each other: MwBudget above, bbo_eig_mw.hpp; diagnostic bit 16777216
-        // keeps the reduction on one workgroup)
-        const bool use_mw = !split128 && !mw_disabled_ && !(d_.dbg & 16777216) && mw_reserve((long) c.npop * MW_G);
-        if (split128 && fixed_r1) {
-            allow_lds((const void*) cma_eigen_r1_fx128, 160 * 1024 - 768);
-            hipLaunchKernelGGL(cma_eigen_r1_fx128, dim3(c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, fa);
-        } else if (split128) {
-            allow_lds((const void*) cma_eigen_r1, 160 * 1024 - 768);
-            hipLaunchKernelGGL(cma_eigen_r1, dim3(c.npop), dim3(512), pl_lds.lds_bytes, stream_, d_, c_,
-                    pl_lds, 0);
-        } else if (use_mw) {
+    auto per_matrix = [&](auto kernel, int threads, const EigPlan &p, auto... args) {   // one workgroup each
+        allow_lds((const void*) kernel, 160 * 1024 - 768);
+        hipLaunchKernelGGL(kernel, dim3(c.npop), dim3(threads), p.lds_bytes, stream_, args...);
+    };
+    auto per_columns = [&](auto kernel, int w, int threads, auto... args) {   // ceil(n / w) workgroups per matrix
+        hipLaunchKernelGGL(kernel, dim3((c.n + w - 1) / w, c.npop), dim3(threads), 0, stream_, d_, c_, args...);
+    };
+    timer_.begin(stream_, K_EIGEN);
+    for (int i = 0; i < r.count; i++) {
+        if (i == r.timed) {          // (the top merge's products are not part of the slot)
+            timer_.end(stream_);
+            BBO_HIP(hipGetLastError());
+        }
+        const int arg = r.step[i].arg;
+        switch (r.step[i].k) {
+        case EK_EIGEN_SMALL:
+            hipLaunchKernelGGL(cma_eigen_small, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_, 0, 1);
+            break;
+        case EK_EIGEN_128: per_matrix(cma_eigen_128, 128, pl, d_, c_, pl, 0); break;
+        case EK_EIGEN_256: per_matrix(cma_eigen_256, 256, pl, d_, c_, pl, 0); break;
+        case EK_EIGEN: per_matrix(cma_eigen, 512, pl, d_, c_, pl, 0); break;
+        case EK_EIGEN_FX128: per_matrix(cma_eigen_fx128, 512, EIG_FX_PLAN, fa); break;
+        case EK_EIGEN_FX128U: per_matrix(cma_eigen_fx128u, 512, EIG_FX_PLAN, fa); break;
+        case EK_EIGEN_R1: per_matrix(cma_eigen_r1, 512, pl_lds, d_, c_, pl_lds, 0); break;
+        case EK_EIGEN_R1_FX128: per_matrix(cma_eigen_r1_fx128, 512, EIG_FX_PLAN, fa); break;
+        case EK_EIGEN_G1: per_matrix(cma_eigen_g1, 512, pl, d_, c_, pl, 0); break;
+        case EK_TRED_MW:
             mw_launched_ = true;
             if (mw_buf_.count != (size_t) c.npop * MW_BUF_DOUBLES) mw_buf_.alloc((size_t) c.npop * MW_BUF_DOUBLES);
-            // (its steps down to the leading 128 x 128 block; that block on one workgroup: diagnostic
-            // bit 536870912 keeps all steps spread)
-            const int istop = (d_.dbg & 536870912) ? 1 : 128;
             hipLaunchKernelGGL(cma_tred_mw, dim3(8 * MW_G, c.npop), dim3(MW_T), 0, stream_, d_, c_, 0,
-                    mw_buf_.p, ++mw_launch_, istop, mw_xcd_);
-            if (istop > 1) {
-                allow_lds((const void*) cma_tred_tail, 160 * 1024 - 768);
-                hipLaunchKernelGGL(cma_tred_tail, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
-            }
-        } else
-            hipLaunchKernelGGL(cma_eigen_g1, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
-        hipLaunchKernelGGL(cma_eig_halves, dim3(3, c.npop), dim3(512), plh.lds_bytes, stream_, d_, c_,
-                plh, pl.lda);
-        // the top merge: with few matrices in flight its secular equation goes to ceil(n / 32)
-        // workgroups of its own between the two parts (diagnostic bit 67108864: one kernel)
-        if ((long) c.npop * 8 <= 256 && !(d_.dbg & 67108864)) {
-            hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 1);
-            hipLaunchKernelGGL(cma_eig_secular, dim3((c.n + 31) / 32, c.npop), dim3(512), 0, stream_, d_, c_);
-            // behind the secular equation: the Loewner vector and the columns of F on n / 32 workgroups
-            // each, the closing repair / root with them (even n: the T factors were built beside the
-            // halves; diagnostic bit 33554432: cma_eigen_g2 part 2, one workgroup, as in round 4)
-            fcols_closed = !(c.n & 1) && c.lazy_isc && (long) c.npop * ((c.n + 15) / 16) <= 256
-                    && !(d_.dbg & (33554432 | 134217728));
-            if (fcols_closed) {
-                hipLaunchKernelGGL(cma_eig_lowner, dim3((c.n + 31) / 32, c.npop), dim3(512), 0, stream_, d_, c_);
-                hipLaunchKernelGGL(cma_eig_fcols, dim3((c.n + 31) / 32, c.npop), dim3(512), 0, stream_, d_, c_);
-            } else
-                hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 2);
-        } else
-            hipLaunchKernelGGL(cma_eigen_g2, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
-    } else if (pl.hybrid)
-        hipLaunchKernelGGL(cma_eigen_g, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_,
-                pl, 0);
-    else if (big_spread) {
-        // 256 < n <= 512, few matrices: the structure of 128 < n <= 256 -- the reduction's first
-        // n - 128 steps spread over 16 workgroups (cma_tred_mw512), the leading block on one
-        // (cma_tred_tail), the reflectors stashed -- in front of the same divide and conquer
-        // (two spread kernels: rows of 512 on 16 workgroups down to pivot row 256, 5.5 us per step,
-        // then rows of 256 on 8, 2.9 us per step -- each with exchange buffers of its own: a value
-        // one of them publishes must never sit where the other looks for a flag; diagnostic bit
-        // 536870912 keeps the first one down to row 128)
-        const bool chain = !(d_.dbg & 536870912);
-        mw_launched_ = true;
-        const size_t need = (size_t) c.npop * (mw_buf_doubles(512) + mw_buf_doubles(256));
-        if (mw_buf_.count != need) mw_buf_.alloc(need);
-        hipLaunchKernelGGL(cma_tred_mw512, dim3(8 * 16, c.npop), dim3(MW_T), 0, stream_, d_, c_, 0,
-                mw_buf_.p, ++mw_launch_, chain ? 256 : 128, mw_xcd_);
-        if (chain)
+                    mw_buf_.p, ++mw_launch_, arg, mw_xcd_);
+            break;
+        case EK_TRED_TAIL: {   // (n > 256: vectors + a 128 x 130 matrix, the LDS of the plan of 256)
+            const EigPlan plt = c.n > 256 ? eig_plan(256, 256) : pl;
+            per_matrix(cma_tred_tail, 512, plt, d_, c_, plt, arg);
+            break;
+        }
+        case EK_EIG_HALVES:
+            allow_lds((const void*) cma_eig_halves, 160 * 1024 - 768);
+            hipLaunchKernelGGL(cma_eig_halves, dim3(3, c.npop), dim3(512), EIG_FX_PLAN.lds_bytes, stream_, d_, c_,
+                    EIG_FX_PLAN, pl.lda);
+            break;
+        case EK_EIGEN_G2: per_matrix(cma_eigen_g2, 512, pl, d_, c_, pl, arg); break;
+        case EK_EIG_SECULAR: per_columns(cma_eig_secular, 32, 512); break;
+        case EK_EIG_LOWNER: per_columns(cma_eig_lowner, 32, 512); break;
+        case EK_EIG_FCOLS: per_columns(cma_eig_fcols, 32, 512); break;
+        case EK_EIGEN_G: per_matrix(cma_eigen_g, 512, pl, d_, c_, pl, 0); break;
+        case EK_TRED_MW512:
+            mw_launched_ = true;
+            if (mw_buf_.count != (size_t) c.npop * (mw_buf_doubles(512) + mw_buf_doubles(256)))
+                mw_buf_.alloc((size_t) c.npop * (mw_buf_doubles(512) + mw_buf_doubles(256)));
+            hipLaunchKernelGGL(cma_tred_mw512, dim3(8 * 16, c.npop), dim3(MW_T), 0, stream_, d_, c_, 0,
+                    mw_buf_.p, ++mw_launch_, arg, mw_xcd_);
+            break;
+        case EK_TRED_MW_CHAIN:
             hipLaunchKernelGGL(cma_tred_mw_chain, dim3(8 * MW_G, c.npop), dim3(MW_T), 0, stream_, d_, c_,
                     mw_buf_.p + (size_t) c.npop * mw_buf_doubles(512), ++mw_launch_, 128, mw_xcd_);
-        const EigPlan plt = eig_plan(256, 256);        // (the tail's LDS: vectors + a 128 x 130 matrix)
-        allow_lds((const void*) cma_tred_tail, 160 * 1024 - 768);
-        hipLaunchKernelGGL(cma_tred_tail, dim3(c.npop), dim3(512), plt.lds_bytes, stream_, d_, c_, plt,
-                chain ? 1 : 0);
-        allow_lds((const void*) cma_eigen_b4, 160 * 1024 - 768);
-        hipLaunchKernelGGL(cma_eigen_b4, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_, pl, 0);
-    } else
-        hipLaunchKernelGGL(cma_eigen_b, dim3(c.npop), dim3(512), pl.lds_bytes, stream_, d_, c_,
-                pl, 0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    if (pl.dc && !pl.reg_path && (pl.hybrid || !(d_.dbg & 2))) {
-        // n > 128: the top merge's two products as whole-GPU kernels
-        dim3 grid((c.n + 63) / 64, (c.n + 63) / 64, c.npop);
-        // few populations: 64 x 16 blocks, four times the workgroups (same sums, same order)
-        const bool narrow = (long) grid.x * grid.y * grid.z < 128;
-        dim3 grid1((c.n + 15) / 16, (c.n + 63) / 64, c.npop);
-        if (narrow)
-            hipLaunchKernelGGL(cma_eig_gemm1, grid1, dim3(256), 0, stream_, d_, c_, pl.lda, 0);
-        else
-            hipLaunchKernelGGL(cma_eig_gemm, grid, dim3(256), 0, stream_, d_, c_, pl.lda, 0);
-        // second product: the stashed reflectors applied in blocked form (the QL fallback of
-        // the diagnostic switch has accumulated Q_house instead)
-        if (big_spread)
-            hipLaunchKernelGGL(cma_eig_wy4_512, dim3((c.n + 15) / 16, c.npop), dim3(256), 0, stream_, d_, c_);
-        else if ((d_.dbg & 2) || !pl.hybrid)     // (n > 256: Q_house was accumulated by the reduction)
-            hipLaunchKernelGGL(cma_eig_gemm, grid, dim3(256), 0, stream_, d_, c_, pl.lda, 1);
-        else
-        {
-            // few matrices: a 16-column tile per WORKGROUP, its rows dealt to the four wavefronts
-            // (diagnostic bit 134217728 keeps a tile per wavefront)
-            if ((long) c.npop * ((c.n + 15) / 16) <= 256 && !(d_.dbg & 134217728)) {
-                // (under lazy_isc the packed operand B D leaves with B: no cma_post launch)
-                wy4_packs = c.lazy_isc != 0;
-                hipLaunchKernelGGL(cma_eig_wy4, dim3((c.n + 15) / 16, c.npop), dim3(256), 0, stream_, d_, c_,
-                        wy4_packs ? (fcols_closed ? 2 : 1) : 0);
-            } else
-                hipLaunchKernelGGL(cma_eig_wy, dim3((c.n + 63) / 64, c.npop), dim3(256), 0, stream_, d_,
-                        c_);
+            break;
+        case EK_EIGEN_B4: per_matrix(cma_eigen_b4, 512, pl, d_, c_, pl, 0); break;
+        case EK_EIGEN_B: per_matrix(cma_eigen_b, 512, pl, d_, c_, pl, 0); break;
+        case EK_EIG_GEMM1:
+            hipLaunchKernelGGL(cma_eig_gemm1, dim3((c.n + 15) / 16, (c.n + 63) / 64, c.npop), dim3(256), 0,
+                    stream_, d_, c_, pl.lda, arg);
+            break;
+        case EK_EIG_GEMM:
+            hipLaunchKernelGGL(cma_eig_gemm, dim3((c.n + 63) / 64, (c.n + 63) / 64, c.npop), dim3(256), 0,
+                    stream_, d_, c_, pl.lda, arg);
+            break;
+        case EK_EIG_WY4: per_columns(cma_eig_wy4, 16, 256, arg); break;
+        case EK_EIG_WY4_512: per_columns(cma_eig_wy4_512, 16, 256); break;
+        case EK_EIG_WY: per_columns(cma_eig_wy, 64, 256); break;
+        case EK_POST: case EK_POST_MFMA: break;      // (r.post: launch_post below, in a slot of its own)
         }
-        BBO_HIP(hipGetLastError());
     }
+    if (r.timed == r.count) timer_.end(stream_);
+    BBO_HIP(hipGetLastError());
     timer_.begin(stream_, K_POST);
-    // (lazy_isc: the eigensolver has written the packed B D itself and C^-1/2 is not formed)
-    const bool packed_by_eigen = c.lazy_isc && pl.dc && pl.reg_path && !(d_.dbg & 2);
-    if (!small && !packed_by_eigen && !wy4_packs) launch_post(0);
+    if (r.post) launch_post(0);
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
 }
@@ -968,13 +960,13 @@ void CmaEngine::program_evaluate()
 }
 
 // n <= 16, lambda <= 64, on-device objective: whole generations in one launch
-// (cma_small_generations).  The per-kernel timers and the diagnostic bit 64 keep the nine-kernel
+// (cma_small_generations).  The per-kernel timers and DBG_NO_SMALL_FUSED keep the nine-kernel
 // path, which computes the same bits.
 bool CmaEngine::small_fused_ok() const
 {
     const CmaConst &c = c_;
     return c.variant < 2 && c.ld == 16 && c.n >= 2 && c.lambda_pad <= 64 && obj_.fused()
-            && c.npop <= SMALL_FUSED_MAXP && !timer_.on() && !(d_.dbg & (16 | 64));
+            && c.npop <= SMALL_FUSED_MAXP && !timer_.on() && !(d_.dbg & (DBG_NO_EIGEN_SMALL | DBG_NO_SMALL_FUSED));
 }
 
 void CmaEngine::launch_small(int gens, bool honor_stop)
@@ -1006,10 +998,10 @@ void CmaEngine::generation(bool honor_stop)
     else if (obj_.is_program()) program_evaluate();
     launch_rank();
     // n = ld = 128 in front of cma_eigen_fx128: that kernel forms C on its load, no cma_cov launch
-    // (diagnostic bit 32 keeps the pair; phase() always launches it)
-    const bool fuse_cov = eig_fixed_form() == 1 && !(d_.dbg & 32);
-    launch_update(!fuse_cov);
-    launch_eigen(fuse_cov);
+    // (DBG_COV_UNFUSED keeps the pair; phase() always launches it)
+    const EigRoute route = eig_route(true, true);
+    launch_update(!route.forms_c);
+    launch_eigen(route);
     launch_history_stop();
 }
 
@@ -1027,14 +1019,14 @@ void CmaEngine::phase(int which)
         break;
     case BBO_PHASE_RANK: launch_rank(); break;
     case BBO_PHASE_UPDATE: launch_update(); break;
-    case BBO_PHASE_EIGEN: launch_eigen(); break;
+    case BBO_PHASE_EIGEN: launch_eigen(eig_route()); break;
     case BBO_PHASE_HISTORY_STOP: launch_history_stop(); break;
     default: throw Error(BBO_ERR_ARG, "unknown CMA phase");
     }
     BBO_HIP(hipStreamSynchronize(stream_));
     if (mw_check_failed() && which == BBO_PHASE_EIGEN) {
         // the spread reduction gave up: this generation's decomposition by the one-workgroup path
-        launch_eigen();
+        launch_eigen(eig_route());
         BBO_HIP(hipStreamSynchronize(stream_));
     }
     timer_.collect();
@@ -1062,7 +1054,7 @@ void CmaEngine::after_chunk(bool in_run)
     if (mw_check_failed()) {
         // the spread reduction gave up (bbo_eig_mw.hpp): the decomposition this generation was due
         // is not lost -- eigenlastev has not moved, the one-workgroup kernels take it now
-        launch_eigen();
+        launch_eigen(eig_route());
         BBO_HIP(hipStreamSynchronize(stream_));
     }
 }
@@ -1281,8 +1273,13 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     if (c.variant == 3 && k == "ranked") return o.one(c.ranked);
     if (k == "eig_mw_off") return o.one(mw_disabled_ ? 1 : 0);
     if (k == "eig_split_maxp") return o.one(split_maxp_);
-    if (k == "eig_fixed128") return o.one(eig_fixed_last_ ? 1 : 0);       // the last decomposition took a fixed-shape kernel
-    if (k == "cov_fused") return o.one(cov_fused_last_ ? 1 : 0);          // the last generation formed C inside it
+    if (k == "eig_fixed128") return o.one(last_route_.fixed ? 1 : 0);     // the last decomposition took a fixed-shape kernel
+    if (k == "cov_fused") return o.one(last_route_.forms_c ? 1 : 0);      // the last generation formed C inside it
+    if (k == "eig_route") {                                               // its kernels in launch order: EigKernel ids
+        double ids[sizeof(last_route_.step) / sizeof(last_route_.step[0])];
+        for (int i = 0; i < last_route_.count; i++) ids[i] = last_route_.step[i].k;
+        return o.copy(ids, last_route_.count);
+    }
     if (k == "splits") return o.one(c.splits);                            // Gram slabs per population
     if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups

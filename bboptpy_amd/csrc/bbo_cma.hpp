@@ -56,6 +56,54 @@ struct CmaConst {
     int ranked;
 };
 
+// Diagnostic switches: the bits of CmaDev::dbg (bbo_set "dbg", 0 in production).  Each selects an older
+// or alternative form of a kernel for A/B tests and timing.  This list is the documentation; the VALUES
+// are frozen (tests and scripts pass them as numbers).
+enum CmaDbg : int {
+    DBG_QL_NO_APPLY      = 1,          // QL stage: the rotations are not applied to the vectors (timing: B is wrong)
+    DBG_QL               = 2,          // tridiagonal stage by the reference's implicit QL, not divide and conquer
+    DBG_DC_NO_MERGES     = 4,          // divide and conquer: leaves only, no merge level (timing: B is wrong)
+    DBG_DC_NO_LEAVES     = 8,          // divide and conquer: the QL leaves are skipped (timing: B is wrong)
+    DBG_NO_EIGEN_SMALL   = 16,         // n <= 16: cma_eigen_128 + cma_post, not cma_eigen_small; no fused generations
+    DBG_COV_UNFUSED      = 32,         // n = 128 batch: cma_cov, then cma_eigen_fx128u, where cma_eigen_fx128 forms C
+    DBG_NO_SMALL_FUSED   = 64,         // n <= 16: the nine-kernel generation, not cma_small_generations
+    DBG_RANK_COUNT32     = 128,        // counting rank: cma_rank (32 candidates a workgroup), not cma_rank32 / 64
+    DBG_SAMPLE_GUARDED   = 256,        // the guarded builds of the samplers where the lean ones would run
+    DBG_GRAM128_LDS      = 512,        // the LDS-staged cma_gram128, not cma_gram128s
+    DBG_TRED_L2          = 1024,       // 128 < n <= 256: one kernel (cma_eigen_g), its first n - 128 Householder
+                                       // steps streaming from L2; 64 < n <= 128: no split decomposition
+    DBG_STAMPS_HALVES    = 2048,       // split decomposition: the phase clocks show cma_eig_halves' first half,
+                                       // not the top merge
+    DBG_RANK_COUNT_NO64  = 4096,       // counting rank: cma_rank32 where cma_rank64 would run
+    DBG_DC_ONE_LEVEL     = 8192,       // divide and conquer stops after its first merge level (phase clocks)
+    DBG_DC_TWO_LEVELS    = 16384,      // ... after its second
+    DBG_DC_LEAF16        = 32768,      // 16 < n <= 128: leaves of 16 rows, not 8
+    DBG_GRAM_NO_PACING   = 65536,      // cma_gram128s without its pacing barrier
+    DBG_PATHS_LAZY256    = 131072,     // cma_paths_lazy (256 threads) where cma_paths_lazy1k would run
+    DBG_RANK_BITONIC     = 262144,     // cma_rank_sort: the bitonic sort where the merge sort would run
+    DBG_DC_LEAF_SINGLE   = 524288,     // one QL leaf per wavefront at a time, not two
+    DBG_SEP_ROWS_LDS     = 1048576,    // sep_sample_eval (row in LDS) where sep_sample_sum would run
+    DBG_EIG_GENERIC128   = 2097152,    // n = ld = 128: cma_eigen / cma_eigen_r1 where the fixed-shape builds would run
+    DBG_EIG_ONE_WG       = 4194304,    // 64 < n <= 256: the whole decomposition on one workgroup (cma_eigen /
+                                       // cma_eigen_g), no split over kernels
+    DBG_DC_WG_BARRIERS   = 8388608,    // workgroup barriers in the one-wavefront merges
+    DBG_TRED_ONE_WG      = 16777216,   // n > 128: the Householder reduction on one workgroup (cma_eigen_g1 /
+                                       // cma_eigen_b), not spread
+    DBG_TOP_PART2        = 33554432,   // top merge: Loewner vector and F by cma_eigen_g2 part 2, not cma_eig_lowner /
+                                       // cma_eig_fcols
+    DBG_TOP_ONE_KERNEL   = 67108864,   // 128 < n <= 256 (and the split form): the top merge as one cma_eigen_g2
+    DBG_WY_PER_WAVE      = 134217728,  // cma_eig_wy (a tile per wavefront) where cma_eig_wy4 would run
+    DBG_SAMPLE_4WAVES    = 268435456,  // n > 128: the four-wavefront cma_sample_eval where <1, 16> would run
+    DBG_TRED_ALL_SPREAD  = 536870912,  // spread reduction: no cma_tred_tail (128 < n <= 256), no cma_tred_mw_chain
+                                       // (n > 256)
+    // every bit cma_eigen / cma_eigen_r1 read inside the kernel (bbo_eig.hpp, bbo_eig_dc.hpp), and
+    // DBG_EIG_ONE_WG, which asks for them.  The fixed-shape builds of n = ld = 128 read none, so any of these
+    // -- and DBG_EIG_GENERIC128 -- keeps the generic kernel: a bit added to those two files belongs in this mask.
+    DBG_EIG_IN_KERNEL    = DBG_QL_NO_APPLY | DBG_QL | DBG_DC_NO_MERGES | DBG_DC_NO_LEAVES | DBG_TRED_L2
+                           | DBG_STAMPS_HALVES | DBG_DC_ONE_LEVEL | DBG_DC_TWO_LEVELS | DBG_DC_LEAF16
+                           | DBG_DC_LEAF_SINGLE | DBG_EIG_ONE_WG | DBG_DC_WG_BARRIERS,
+};
+
 struct CmaDev {
     double *X;          // [P][lambda_pad][ld]   candidates (arx)
     double *f;          // [P][lambda_pad]       fitness, +inf on padding rows
@@ -83,9 +131,37 @@ struct CmaDev {
     double *zrecord;                  // [P][lambda][n] or null
     CmaScal *scal;                    // [P]
     long long *stamps;                // [16] eigensolver phase clocks (diagnostic) or null
-    int dbg;                          // diagnostic switches (0 in production)
+    int dbg;                          // diagnostic switches: CmaDbg bits (0 in production)
     int mw_fault;                     // fault injection of bbo_eig_mw.hpp (-1: none; environment only)
     int *mw_fail_host;                // pinned host word: a spread reduction of this engine timed out
+};
+
+// The kernels of one decomposition.  get "eig_route" returns the ids of the last launch_eigen in launch
+// order, so this order is that key's contract: append, never renumber.
+enum EigKernel : int {
+    EK_EIGEN_SMALL = 0, EK_EIGEN_128, EK_EIGEN_256, EK_EIGEN, EK_EIGEN_FX128, EK_EIGEN_FX128U,   // 0 .. 5
+    EK_EIGEN_R1, EK_EIGEN_R1_FX128, EK_EIGEN_G1, EK_TRED_MW, EK_TRED_TAIL, EK_EIG_HALVES,        // 6 .. 11
+    EK_EIGEN_G2, EK_EIG_SECULAR, EK_EIG_LOWNER, EK_EIG_FCOLS, EK_EIGEN_G,                        // 12 .. 16
+    EK_TRED_MW512, EK_TRED_MW_CHAIN, EK_EIGEN_B4, EK_EIGEN_B,                                    // 17 .. 20
+    EK_EIG_GEMM1, EK_EIG_GEMM, EK_EIG_WY4, EK_EIG_WY4_512, EK_EIG_WY,                            // 21 .. 25
+    EK_POST, EK_POST_MFMA                                                                        // 26, 27
+};
+
+// What one launch_eigen does: plain data, computed by CmaEngine::eig_route and by nothing else.
+struct EigRoute {
+    struct Step {
+        EigKernel k;
+        int arg;       // cma_tred_mw / _mw512: istop; cma_tred_tail: 1 behind the chain kernel; cma_eigen_g2: part;
+                       // cma_eig_gemm: which product; cma_eig_wy4: pack mode
+    };
+    Step step[12];
+    int count;         // steps in all, the trailing EK_POST / EK_POST_MFMA included
+    int timed;         // the first `timed` of them are the profile's cma_eigen slot, the rest the top merge's products
+    bool split;        // 64 < n <= 128, few matrices: the kernels behind the reduction take eig_plan_split
+    bool post;         // launch_post(0) follows
+    bool fixed;        // a fixed-shape build of n = ld = 128 (get "eig_fixed128")
+    bool forms_c;      // cma_eigen_fx128 forms C on its load: no cma_cov in front (get "cov_fused")
+    long mw_workgroups;   // > 0: spread kernels that need this many workgroups reserved (mw_reserve)
 };
 
 class CmaEngine: public Engine<CmaScal> {
@@ -135,8 +211,15 @@ private:
     void launch_post(int mode);
     void launch_rank();
     void launch_update(bool with_cov = true);
-    void launch_eigen(bool cov_fused = false);
-    int eig_fixed_form() const;
+    // spread_ok: the spread reduction may be used; fuse_ok: no cma_cov has gone before (a generation)
+    EigRoute eig_route(bool spread_ok = true, bool fuse_ok = false) const;
+    void launch_eigen(EigRoute r);
+    // the samplers' lean builds: no padding column or row, no box, no injected or recorded normals
+    bool nothing_to_guard() const
+    {
+        return c_.n == c_.ld && !c_.bound && c_.lambda == c_.lambda_pad && !d_.zinject && !d_.zrecord
+                && !(d_.dbg & DBG_SAMPLE_GUARDED);
+    }
     void launch_history_stop();
     void host_evaluate();
     void program_evaluate();
@@ -156,8 +239,7 @@ private:
     long sample128_min_rows_ = 256 * 128;   // candidates in flight from which cma_sample_eval128 is used
     bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
-    bool eig_fixed_last_ = false;      // the last launch_eigen took the fixed-shape kernel (get "eig_fixed128")
-    bool cov_fused_last_ = false;      // the last generation formed C inside the eigensolver (get "cov_fused")
+    EigRoute last_route_ {};           // what the last launch_eigen did (get "eig_route", "eig_fixed128", "cov_fused")
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;
 

@@ -652,7 +652,7 @@ __global__ __launch_bounds__(256) void cma_rank64(CmaDev d, CmaConst c)
 // bitonic network otherwise (12 max(m, 1024) bytes).  grid (P), 1024 threads (256 for m <= 256)
 __host__ __device__ inline bool rank_sort_merges(int m, int dbg)
 {
-    return (m == 2048 || m == 4096) && !(dbg & 262144);
+    return (m == 2048 || m == 4096) && !(dbg & DBG_RANK_BITONIC);
 }
 
 __global__ __launch_bounds__(1024) void cma_rank_sort(CmaDev d, CmaConst c, int m)
@@ -1265,7 +1265,7 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
     const int nrows = min(c.rps, c.lambda_pad - row0);
     const int nch = (nrows + G128_CH - 1) / G128_CH;
     const int fr = lane & 15, fk = lane >> 4;
-    const bool pace = !(d.dbg & 65536);
+    const bool pace = !(d.dbg & DBG_GRAM_NO_PACING);
 
     double xo[8];
 #pragma unroll

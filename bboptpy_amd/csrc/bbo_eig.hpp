@@ -1318,26 +1318,26 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
         eig_cov_prologue128<TT>(d, c, sc, p, A.a, tid);
         if (!due) return;
         eig_tred_accum_reg128<TT>(A.a, A.ld, n, A, dv, ev, uv, wv, gv, hvec, td, tid, nullptr, A.a, A.ld, true,
-                !(pl.dc && !(d.dbg & 2)));
+                !(pl.dc && !(d.dbg & DBG_QL)));
     } else if (LDSM) {      // (use_lds implies the register-resident reduction: n <= 128)
         // (with the D&C stage the reflectors stay stashed in A: eig_dc_phase applies them to the
         // tridiagonal eigenvectors in blocked form on the matrix cores)
         eig_tred_accum_reg128<TT>(C, ld, n, A, dv, ev, uv, wv, gv, hvec, td, tid,
                 (d.stamps && p == 0) ? d.stamps : nullptr, A.a, A.ld, true,
-                !(pl.dc && !(d.dbg & 2)));
+                !(pl.dc && !(d.dbg & DBG_QL)));
     } else if (TT == EIG_THREADS && !LDSM) {
         const bool hybrid = HYB != 0;        // 128 < n <= 256: LDS holds a 128 x 128 stash matrix
         EigMat Ast { reinterpret_cast<double*>(ibuf + 2 * EIG_MAXSEQ * 3 + 8), 128 };
         // (with the D&C stage the reflectors stay stashed: cma_eig_wy applies them in blocked form)
         // (diagnostic bit 1024: round 2's form of the first n - 128 steps, streaming from L2)
-        if (hybrid && !(d.dbg & 2) && !(d.dbg & 1024))
+        if (hybrid && !(d.dbg & DBG_QL) && !(d.dbg & DBG_TRED_L2))
             eig_tred_sym256(C, ld, n, A, dv, ev, uv, wv, gv, hvec, td, nv, tid,
                     (d.stamps && p == 0) ? d.stamps : nullptr, Ast, false,
                     d.eig_work + (size_t) (4 * p + 1) * eig_slab(ld));
         else
         eig_tred_accum_global(C, ld, n, A, dv, ev, uv, wv, gv, hvec, td, part, nv, tid,
                 (d.stamps && p == 0) ? d.stamps : nullptr, hybrid ? &Ast : nullptr,
-                !(hybrid && !(d.dbg & 2)));
+                !(hybrid && !(d.dbg & DBG_QL)));
     }   // generic path
     {   // tql2 prologue: shift the sub-diagonal down (cmaes.cpp:384-387); T >= n
         const double t = (tid + 1 < n) ? ev[tid + 1] : 0.;
@@ -1367,7 +1367,7 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
         return;
     }
 
-    const bool use_dc = pl.dc && !(d.dbg & 2);
+    const bool use_dc = pl.dc && !(d.dbg & DBG_QL);
     if (use_dc) {
         // divide and conquer on the tridiagonal matrix; writes B (ascending eigenvalues)
         double *scr = uv;
@@ -1375,11 +1375,11 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
         // per-population global scratch: [work matrix | Q_house | F | Q F], eig_slab(ld) each
         double *Gp = d.eig_work + (size_t) (4 * p + 1) * eig_slab(ld);
         double *Bp_ = d.B + (size_t) p * ld * ld;
-        long long *st_ = (d.stamps && p == 0 && !(STAGE == 2 && (d.dbg & 2048))) ? d.stamps : nullptr;
+        long long *st_ = (d.stamps && p == 0 && !(STAGE == 2 && (d.dbg & DBG_STAMPS_HALVES))) ? d.stamps : nullptr;
         if (LDSM || HYB || TT != EIG_THREADS) {
             // n <= 256: the reflectors are stashed (hv = 1 / their scalars)
             eig_dc_phase<TT, false, !LDSM, FX>(Qm, n, dv, ev, Gp, Bp_, ld, scr, st_, d.dbg, LDSM ? 0 : 1, hvec,
-                    !LDSM && !(d.dbg & 2) && !(d.dbg & 1024),   // (hybrid: V already in its place)
+                    !LDSM && !(d.dbg & DBG_QL) && !(d.dbg & DBG_TRED_L2),   // (hybrid: V already in its place)
                     nullptr, STAGE == 2 ? 2 : 0, STAGE == 2 && tri[4 * n] != 0.,
                     STAGE == 2 ? force : 0, tri + 4 * n + 8);      // (STAGE 2: `force` = the part)
             if (STAGE == 2 && force == 1) return;
@@ -1421,7 +1421,7 @@ __device__ __forceinline__ void cma_eigen_impl(const CmaDev &d, const CmaConst &
             } else if (epoch > 0) {
                 const int prv = cur ^ 1;
                 const int ns = nseq[prv];
-                if (!(d.dbg & 1))
+                if (!(d.dbg & DBG_QL_NO_APPLY))
                 for (int k = tid - 64; k < n; k += T - 64)
                     ql_apply_row(A, k, rot + (size_t) prv * pl.rc, desc + prv * EIG_MAXSEQ * 3,
                             ns);
@@ -1935,7 +1935,7 @@ __global__ __launch_bounds__(512) void cma_eig_halves(CmaDev d, CmaConst c, EigP
     // (diagnostic bit 2048: the phase clocks show the FIRST HALF's leaves and merges, the top merge
     // behind it keeps its hands off them)
     eig_dc_phase<512, false, false>(Qm, m, dv, ev, G, Bout, lda_work, uv,
-            (d.stamps && p == 0 && h == 0 && (d.dbg & 2048)) ? d.stamps : nullptr, d.dbg, 0, nullptr,
+            (d.stamps && p == 0 && h == 0 && (d.dbg & DBG_STAMPS_HALVES)) ? d.stamps : nullptr, d.dbg, 0, nullptr,
             true, nullptr, 1);
     // the rest of this half's rows of the work matrix: the other half's columns are zero
     const int c0 = h ? 0 : mid, cw = h ? mid : n - mid;

@@ -1445,7 +1445,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n_in, double *d
         // (16 < n <= 128) the leaves are 8 x 8: a QL leaf is a serial chain of ~2 (s^2 / 2)
         // rotations, the extra level of merges -- 16-pole merges, one wavefront each -- costs a
         // third of what the smaller leaves save (round 3, once the merges had become cheap)
-        const int leaf_rows = (!ext_top && n > 16 && n <= 128 && !(dbg & 32768)) ? 8 : DC_LEAF;
+        const int leaf_rows = (!ext_top && n > 16 && n <= 128 && !(dbg & DBG_DC_LEAF16)) ? 8 : DC_LEAF;
         // (a power-of-two number of blocks whose sizes differ by at most one, edges floor(i n / nb):
         // every level pairs all of its blocks.  Until round 3 thread 0 halved the blocks one level
         // at a time through a per-thread array -- scratch memory: most of the 15 us this set-up took)
@@ -1492,7 +1492,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n_in, double *d
     // the one-leaf-at-a-time form)
     if (mode == 2) {
         // (no leaves)
-    } else if (!(dbg & 8) && !(dbg & 524288)) {
+    } else if (!(dbg & DBG_DC_NO_LEAVES) && !(dbg & DBG_DC_LEAF_SINGLE)) {
         for (int pr = wave; 2 * pr < nblk; pr += NW) {
             const int b0 = 2 * pr, b1 = 2 * pr + 1;
             const int a0 = bound(b0), s0 = bound(b0 + 1) - a0;
@@ -1500,7 +1500,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n_in, double *d
             dc_leaf_ql_pair(Q, a0, s0, a1, s1, dv, ev, dv, lane);
         }
     } else
-    if (!(dbg & 8))
+    if (!(dbg & DBG_DC_NO_LEAVES))
     for (int blk = wave; blk < nblk; blk += NW) {
         const int a = bounds[blk], s = bounds[blk + 1] - a;
         dc_leaf_ql(Q, a, s, dv, ev, dv, scratch + (size_t) wave * 272, lane,
@@ -1543,7 +1543,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n_in, double *d
     // (diagnostic bits 8192 / 16384: stop after the first / second level, so that the phase clocks
     // of dc_merge_level -- the first team's, every level overwrites them -- show THAT level)
     int levels_done = 0;
-    while (nc > 1 && !(dbg & 4) && !((dbg & 8192) && levels_done >= 1) && !((dbg & 16384) && levels_done >= 2)) {
+    while (nc > 1 && !(dbg & DBG_DC_NO_MERGES) && !((dbg & DBG_DC_ONE_LEVEL) && levels_done >= 1) && !((dbg & DBG_DC_TWO_LEVELS) && levels_done >= 2)) {
         const int L = levels_done;
         levels_done++;
         const int nm = nc >> 1;                       // merges at this level
@@ -1572,7 +1572,7 @@ __device__ __forceinline__ void eig_dc_phase(const DcMat &Q, int n_in, double *d
         tm.twave = wave - tm.wave0;
         tm.ttid = tid - 64 * tm.wave0;
         tm.tthreads = 64 * wpt;
-        tm.wave_scope = wpt == 1 && !(dbg & 8388608);      // (diagnostic bit: workgroup barriers)
+        tm.wave_scope = wpt == 1 && !(dbg & DBG_DC_WG_BARRIERS);      // (diagnostic bit: workgroup barriers)
         if (tid == 0) maxnr_s = 0;
         __syncthreads();
         const int q = tm.active ? q0 : 0;
