@@ -592,33 +592,35 @@ void CmaEngine::launch_rank()
     const CmaConst &c = c_;
     rank_wrote_norms_ = false;
     timer_.begin(stream_, K_RANK);
-    // few populations: the counting kernel spreads one ranking over many CUs; many
-    // populations: one in-LDS sort per population is far less work in total
-    if (c.lambda <= 64 && c.lambda >= 2 && c.npop >= 4) {
+    // (which form, and why: rank_route, bbo_rank.hpp)
+    last_rank_ = rank_route(c.lambda, c.npop, d_.dbg);
+    switch (last_rank_) {
+    case RK_WAVE:
         hipLaunchKernelGGL(cma_rank_wave, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_);
-    } else if (c.lambda <= SORT_LDS_MAX && c.npop >= 4) {
-        int m = 2;
-        while (m < c.lambda) m <<= 1;
+        break;
+    case RK_COUNT64:
+        hipLaunchKernelGGL(cma_rank64, dim3((c.lambda + 3) / 4, c.npop), dim3(256), 0, stream_, d_, c_);
+        break;
+    case RK_COUNT32:
+        hipLaunchKernelGGL(cma_rank32, dim3((c.lambda + 7) / 8, c.npop), dim3(256), 0, stream_, d_, c_);
+        break;
+    case RK_COUNT8:
+        hipLaunchKernelGGL(cma_rank, dim3((c.lambda + 31) / 32, c.npop), dim3(256), 0, stream_, d_, c_);
+        break;
+    default: {   // the in-LDS sorts: cma_rank_sort picks the instantiation from m and dbg like rank_route
+        const int m = rank_sort_m(c.lambda);
         allow_lds((const void*) cma_rank_sort, 128 * 1024);
         const size_t lds = rank_sort_merges(m, d_.dbg) ? (size_t) m * 24 : (size_t) std::max(m, 1024) * 12;
         hipLaunchKernelGGL(cma_rank_sort, dim3(c.npop), dim3(sort_threads(m)), lds, stream_, d_,
                 c_, m);
-        // the whitened norms of the worst mu, where they are the sampler's sigma^2 ||z||^2 handed
-        // round through the ranking (cma_whiten128's shortcut): written by the sort itself, which
-        // has the ranking in LDS -- a launch less per generation (10 us of the M step)
-        rank_wrote_norms_ = c.variant == 1 && c.use_zn && !basis_maybe_stale_;
-    } else {
-        // few candidates in flight: 8 per workgroup, 32 slices each (a quarter of the 64-bit compares
-        // per thread; DBG_RANK_COUNT32 keeps the 32-candidate form -- the same counts)
-        if ((long) c.npop * ((c.lambda + 31) / 32) <= 256 && c.lambda >= 2048 && !(d_.dbg & (DBG_RANK_COUNT32 | DBG_RANK_COUNT_NO64)))
-            hipLaunchKernelGGL(cma_rank64, dim3((c.lambda + 3) / 4, c.npop), dim3(256), 0, stream_, d_, c_);
-        else if ((long) c.npop * ((c.lambda + 31) / 32) <= 512 && c.lambda >= 512 && !(d_.dbg & DBG_RANK_COUNT32))
-            hipLaunchKernelGGL(cma_rank32, dim3((c.lambda + 7) / 8, c.npop), dim3(256), 0, stream_, d_, c_);
-        else
-            hipLaunchKernelGGL(cma_rank, dim3((c.lambda + 31) / 32, c.npop), dim3(256), 0, stream_, d_, c_);
-        // (the whitened norms leave with the ranking here too: see cma_rank_body)
-        rank_wrote_norms_ = c.variant == 1 && c.use_zn && !basis_maybe_stale_;
+        break;
     }
+    }
+    // the whitened norms of the worst mu, where they are the sampler's sigma^2 ||z||^2 handed
+    // round through the ranking (cma_whiten128's shortcut): written by the sort itself, which
+    // has the ranking in LDS, and by cma_rank_body -- a launch less per generation (10 us of the
+    // M step).  Not by the one-wavefront form.
+    if (last_rank_ != RK_WAVE) rank_wrote_norms_ = c.variant == 1 && c.use_zn && !basis_maybe_stale_;
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
 }
@@ -1280,6 +1282,7 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         for (int i = 0; i < last_route_.count; i++) ids[i] = last_route_.step[i].k;
         return o.copy(ids, last_route_.count);
     }
+    if (k == "rank_route") return o.one(last_rank_);                      // the form of the last launch_rank: RankKernel
     if (k == "splits") return o.one(c.splits);                            // Gram slabs per population
     if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups
@@ -1290,6 +1293,11 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "best_len") return o.one(s.hist_len);
     if (k == "best_buffer") return o.one(s.hist_head);
     if (k == "ibest") return o.one(s.ibw[0]);
+    if (k == "ybw") return o.copy(s.ybw, 4);    // best, 2nd best, 2nd worst, worst of the last ranking ...
+    if (k == "ibw") {                           // ... and their candidates
+        const double ids[4] = { (double) s.ibw[0], (double) s.ibw[1], (double) s.ibw[2], (double) s.ibw[3] };
+        return o.copy(ids, 4);
+    }
     if (k == "n") return o.one(c.n);
     if (k == "lambda") return o.one(c.lambda);
     if (k == "mu") return o.one(c.mu);
@@ -1354,9 +1362,12 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
         upload_rows(X_, (size_t) p * c.lambda_pad, c.lambda, c.n, c.ld, in);
         return count;
     }
-    if (c.variant == 3 && k == "fitness") {      // (the same; the ranking is NOT redone: fit_idx keeps its order)
+    if (k == "fitness") {      // (crafted states; the ranking is NOT redone: fit_idx keeps its order.  NaN
+                               // goes in as +inf, like every evaluation path: no NaN reaches a ranking)
         BBO_REQUIRE(count == c.lambda, "set: wrong element count");
-        f_.upload(in, c.lambda, (size_t) p * c.lambda_pad);
+        std::vector<double> f(in, in + c.lambda);
+        nan_to_inf(f.data(), c.lambda);
+        f_.upload(f.data(), c.lambda, (size_t) p * c.lambda_pad);
         return count;
     }
     if (k == "xmean") return vec_in(xmean_);

@@ -240,6 +240,7 @@ private:
     bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
     EigRoute last_route_ {};           // what the last launch_eigen did (get "eig_route", "eig_fixed128", "cov_fused")
+    int last_rank_ = -1;               // the form the last launch_rank took: RankKernel (get "rank_route"), -1 before
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;
 

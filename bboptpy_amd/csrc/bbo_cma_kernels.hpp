@@ -649,11 +649,10 @@ __global__ __launch_bounds__(256) void cma_rank64(CmaDev d, CmaConst c)
 
 // the same ranking by one in-LDS sort per population (lambda <= SORT_LDS_MAX): merge sort by
 // merge path for 2048 / 4096 padded keys (`merge`: two buffers, 24 m bytes of dynamic LDS), the
-// bitonic network otherwise (12 max(m, 1024) bytes).  grid (P), 1024 threads (256 for m <= 256)
-__host__ __device__ inline bool rank_sort_merges(int m, int dbg)
-{
-    return (m == 2048 || m == 4096) && !(dbg & DBG_RANK_BITONIC);
-}
+// bitonic network otherwise (12 max(m, 1024) bytes): rank_sort_merges, bbo_rank.hpp.
+// grid (P), 1024 threads (256 for m <= 256)
+static_assert((int) DBG_RANK_COUNT32 == RANK_DBG_COUNT32 && (int) DBG_RANK_COUNT_NO64 == RANK_DBG_COUNT_NO64
+        && (int) DBG_RANK_BITONIC == RANK_DBG_BITONIC, "bbo_rank.hpp reads these bits of CmaDev::dbg");
 
 __global__ __launch_bounds__(1024) void cma_rank_sort(CmaDev d, CmaConst c, int m)
 {

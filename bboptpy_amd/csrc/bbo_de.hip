@@ -141,21 +141,29 @@ void DeEngine::init(int n, const double *lower, const double *upper, const doubl
 void DeEngine::launch_rank(int which_next, int np_bound)
 {
     const DeConst &c = c_;
-    if (np_bound <= 64 && np_bound >= 2 && c.npop >= 4) {
+    // (which form: rank_route, bbo_rank.hpp.  DE has the 8-slice counting kernel only, and its sort
+    // always merges at 2048 / 4096 keys)
+    last_rank_ = rank_route(np_bound, c.npop, RANK_DBG_COUNT32);
+    switch (last_rank_) {
+    case RK_WAVE:
         hipLaunchKernelGGL(de_rank_wave, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_,
                 which_next);
-    } else if (np_bound <= SORT_LDS_MAX && c.npop >= 4) {
-        int m = 2;
-        while (m < np_bound) m <<= 1;
+        break;
+    case RK_COUNT8: {
+        dim3 rgrid((np_bound + 31) / 32, c.npop);
+        hipLaunchKernelGGL(de_rank, rgrid, dim3(256), 0, stream_, d_, c_, which_next);
+        break;
+    }
+    default: {
+        const int m = rank_sort_m(np_bound);
         allow_lds((const void*) de_rank_sort, SORT_LDS_MAX * 12);
         // (2048 / 4096 keys: merge sort by merge path, two buffers; bbo_rank.hpp)
         hipLaunchKernelGGL(de_rank_sort, dim3(c.npop), dim3(sort_threads(m)),
-                (m == 2048 || m == 4096) ? (size_t) m * 24 : (size_t) std::max(m, 1024) * 12,
+                rank_sort_merges(m, 0) ? (size_t) m * 24 : (size_t) std::max(m, 1024) * 12,
                 stream_, d_,
                 c_, which_next, m);
-    } else {
-        dim3 rgrid((np_bound + 31) / 32, c.npop);
-        hipLaunchKernelGGL(de_rank, rgrid, dim3(256), 0, stream_, d_, c_, which_next);
+        break;
+    }
     }
     BBO_HIP(hipGetLastError());
 }
@@ -307,6 +315,7 @@ int DeEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "m2") return o.one(s.m2);
     if (k == "nsucc") return o.one(s.nsucc);
     if (k == "n") return o.one(c.n);
+    if (k == "rank_route") return o.one(last_rank_);     // the form of the last launch_rank: RankKernel
     throw Error(BBO_ERR_KEY, "unknown state key '" + k + "'");
 }
 

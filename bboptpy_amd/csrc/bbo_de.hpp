@@ -83,6 +83,7 @@ private:
 
     DeConst c_ {};
     DeDev d_ {};
+    int last_rank_ = -1;     // the form the last launch_rank took: RankKernel (get "rank_route"), -1 before
     int np_host_ = 0;        // upper bound of the device np (exact while no population stopped)
     long fev_host_ = 0;
     DevBuf<double> cra_, crb_;

@@ -178,6 +178,7 @@ int DsaEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "profile") return profile_report(out, cap);
     if (k == "X") return o.rows(s.cur ? X1_ : X0_, pb, c.np, c.n, c.ld);
     if (k == "f") return o.vec(f_, pb, c.np);
+    if (k == "fit_idx") return o.ints(order_, pb, c.np);     // rank -> row, as the last dsa_rank that sorted left it
     if (k == "p") return o.copy(s.p, 4);
     if (k == "w") return o.copy(s.w, 4);
     if (k == "bestx") return o.vec(bestx_, (size_t) p * c.ld, c.n);

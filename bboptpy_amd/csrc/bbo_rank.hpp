@@ -352,4 +352,57 @@ __device__ inline void bitonic_sort_lds(const double *f, int count, int m, doubl
     else bitonic_sort_regs<8>(f, count, keys, idx, order, rank);
 }
 
+// ---- which form ranks: one decision for every engine ----------------------------------------------
+// The diagnostic switches the decision reads: bits of CmaDev::dbg (bbo_cma.hpp lists them as
+// DBG_RANK_*; the values are frozen there).  DeEngine has the 8-slice counting kernel only and
+// says so with RANK_DBG_COUNT32.
+enum RankDbg : int { RANK_DBG_COUNT32 = 128, RANK_DBG_COUNT_NO64 = 4096, RANK_DBG_BITONIC = 262144 };
+
+// The forms.  get "rank_route" returns the one the last launch_rank took, so this order is that
+// key's contract: append, never renumber.
+enum RankKernel : int {
+    RK_WAVE = 0,                                                        // one wavefront per population
+    RK_SORT_BITONIC256,                                                 // bitonic_sort_regs<1, 256>
+    RK_SORT_BITONIC_E1, RK_SORT_BITONIC_E2, RK_SORT_BITONIC_E4, RK_SORT_BITONIC_E8,   // 2 .. 5
+    RK_SORT_MERGE2, RK_SORT_MERGE4,                                     // 6, 7: merge_sort_lds
+    RK_COUNT8, RK_COUNT32, RK_COUNT64                                   // 8 .. 10: rank_by_counting<SL>
+};
+
+// the padded size of the in-LDS sorts: the power of two >= count, at least 2
+__host__ __device__ inline int rank_sort_m(int count)
+{
+    int m = 2;
+    while (m < count) m <<= 1;
+    return m;
+}
+
+// merge sort by merge path for 2048 / 4096 padded keys (two buffers, 24 m bytes of dynamic LDS), the
+// bitonic network otherwise (12 max(m, 1024) bytes)
+__host__ __device__ inline bool rank_sort_merges(int m, int dbg)
+{
+    return (m == 2048 || m == 4096) && !(dbg & RANK_DBG_BITONIC);
+}
+
+// count: the host's bound on the keys of a population (lambda; DE: np of the launch); npop: the
+// populations of the handle.  Few populations: the counting kernels spread one ranking over many
+// CUs; many: one in-LDS sort (or one wavefront) per population is far less work in total.
+inline RankKernel rank_route(int count, int npop, int dbg)
+{
+    if (count <= 64 && count >= 2 && npop >= 4) return RK_WAVE;
+    if (count <= SORT_LDS_MAX && npop >= 4) {
+        const int m = rank_sort_m(count);
+        if (sort_threads(m) == 256) return RK_SORT_BITONIC256;
+        if (m <= 1024) return RK_SORT_BITONIC_E1;
+        if (m == 2048) return rank_sort_merges(m, dbg) ? RK_SORT_MERGE2 : RK_SORT_BITONIC_E2;
+        if (m == 4096) return rank_sort_merges(m, dbg) ? RK_SORT_MERGE4 : RK_SORT_BITONIC_E4;
+        return RK_SORT_BITONIC_E8;
+    }
+    // few candidates in flight: 4 or 8 per workgroup, 64 or 32 slices each (a fraction of the 64-bit
+    // compares per thread); RANK_DBG_COUNT32 keeps the 32-candidate form -- the same counts
+    const long wgs = (long) npop * ((count + 31) / 32);
+    if (wgs <= 256 && count >= 2048 && !(dbg & (RANK_DBG_COUNT32 | RANK_DBG_COUNT_NO64))) return RK_COUNT64;
+    if (wgs <= 512 && count >= 512 && !(dbg & RANK_DBG_COUNT32)) return RK_COUNT32;
+    return RK_COUNT8;
+}
+
 } // namespace bbo

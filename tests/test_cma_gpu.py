@@ -438,6 +438,9 @@ def test_single_run_sampler_and_ranking_equal_the_batch_kernels(hip, lam, obj):
         g.phase(_ffi.PHASE_SAMPLE_EVALUATE)
         g.phase(_ffi.PHASE_RANK)
         g.phase(_ffi.PHASE_UPDATE)
+        # enum RankKernel (bbo_rank.hpp): 8 = count8, 9 = count32, 10 = count64.  One population: 32 slices
+        # from lambda = 512, 64 from 2048; below 512 both sides count with 8 (only the sampler differs)
+        assert int(g.get_state("rank_route")[0]) == ((10 if lam >= 2048 else 9 if lam >= 512 else 8) if wide else 8)
         out.append({k: g.get_state(k).copy() for k in ("arx", "fitness", "fit_idx", "xmean", "sigma", "C", "ps")})
     for k in out[0]:
         np.testing.assert_array_equal(out[0][k], out[1][k], err_msg=k)
