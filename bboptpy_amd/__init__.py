@@ -9,8 +9,9 @@ from . import objectives
 from .objectives import vectorized, DeviceObjective
 from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, CMAES,
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
-                           SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES)
+                           SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES,
+                           SpiralSearch)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "objectives",
            "vectorized", "DeviceObjective"]

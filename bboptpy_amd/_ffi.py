@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
-    ALGO_HEES = range(15)
+    ALGO_HEES, ALGO_SPIRAL = range(16)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -23,6 +23,8 @@ ERR_ARG = -1
 PHASE_SAMPLE_EVALUATE, PHASE_RANK, PHASE_UPDATE, PHASE_EIGEN, PHASE_HISTORY_STOP = range(5)
 # bbo_hees_phase
 HEES_PHASE_SAMPLE, HEES_PHASE_RANK, HEES_PHASE_UPDATE, HEES_PHASE_FINISH = range(4)
+# bbo_spiral_phase
+SPIRAL_PHASE_DRAW, SPIRAL_PHASE_ROTATE, SPIRAL_PHASE_EVALUATE, SPIRAL_PHASE_BEST = range(4)
 
 BUILTIN_IDS = {"sphere": 0, "rosenbrock": 1, "rastrigin": 2, "ellipsoid": 3, "ackley": 4,
                "griewank": 5, "cigar": 6, "discus": 7, "diffpow": 8, "schwefel12": 9}
@@ -66,6 +68,12 @@ class DsaParams(C.Structure):
 class HeesParams(C.Structure):
     """bbo_hees_params: HEES's constructor arguments that bbo_params has no field for"""
     _fields_ = [("mres", C.c_int), ("print", C.c_int)]
+
+
+class SpiralParams(C.Structure):
+    """bbo_spiral_params: SpiralSearch's constructor arguments that bbo_params has no field for"""
+    _fields_ = [(k, C.c_double) for k in ("r", "theta", "taur", "tautheta", "rlow", "rhigh",
+                                          "thetalow", "thetahigh")]
 
 
 class Objective(C.Structure):
@@ -133,6 +141,11 @@ def lib():
     L.bbo_hees_configure.argtypes = [C.c_void_p, C.POINTER(HeesParams)]
     L.bbo_hees_phase.argtypes = [C.c_void_p, C.c_int]
     L.bbo_hees_inject_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.bbo_spiral_params_default.argtypes = [C.POINTER(SpiralParams)]
+    L.bbo_spiral_params_default.restype = None
+    L.bbo_spiral_configure.argtypes = [C.c_void_p, C.POINTER(SpiralParams)]
+    L.bbo_spiral_phase.argtypes = [C.c_void_p, C.c_int]
+    L.bbo_spiral_inject_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -144,7 +157,8 @@ def lib():
                  "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
                  "bbo_program_create", "bbo_program_destroy", "bbo_jaya_configure",
                  "bbo_dsa_configure", "bbo_hees_configure", "bbo_hees_phase",
-                 "bbo_hees_inject_normals"):
+                 "bbo_hees_inject_normals", "bbo_spiral_configure", "bbo_spiral_phase",
+                 "bbo_spiral_inject_uniforms"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -160,6 +174,8 @@ EXPORTED_SYMBOLS = (
     "bbo_jaya_params_default", "bbo_jaya_configure",
     "bbo_dsa_params_default", "bbo_dsa_configure",
     "bbo_hees_params_default", "bbo_hees_configure", "bbo_hees_phase", "bbo_hees_inject_normals",
+    "bbo_spiral_params_default", "bbo_spiral_configure", "bbo_spiral_phase",
+    "bbo_spiral_inject_uniforms",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

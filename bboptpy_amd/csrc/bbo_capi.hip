@@ -6,6 +6,7 @@
 #include "bbo_jaya.hpp"
 #include "bbo_dsa.hpp"
 #include "bbo_hees.hpp"
+#include "bbo_spiral.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -20,6 +21,7 @@ Optimizer* make_ccpso_engine(const bbo_params &p);    // bbo_ccpso.hip
 Optimizer* make_jaya_engine(const bbo_params &p);     // bbo_jaya.hip
 Optimizer* make_dsa_engine(const bbo_params &p);      // bbo_dsa.hip
 Optimizer* make_hees_engine(const bbo_params &p);     // bbo_hees.hip
+Optimizer* make_spiral_engine(const bbo_params &p);   // bbo_spiral.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -170,6 +172,7 @@ void bbo_params_default(bbo_params *p, int algo)
     p->vmax = 0.2;
     p->npps = 0;
     p->pcauchy = -1.;
+    if (algo == BBO_ALGO_SPIRAL) p->np = 20;   /* py/multivariate_py.cpp:348 */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -218,6 +221,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_HEES:
             h->opt.reset(bbo::make_hees_engine(*params));
+            break;
+        case BBO_ALGO_SPIRAL:
+            h->opt.reset(bbo::make_spiral_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -558,6 +564,47 @@ int bbo_hees_phase(bbo_handle h, int phase)
 int bbo_hees_inject_normals(bbo_handle h, const double *z, int count)
 {
     return guarded(h, [&] { as_hees(h)->inject_normals(z, count); });
+}
+
+void bbo_spiral_params_default(bbo_spiral_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp:348-350, as printed there
+    p->r = 0.95;
+    p->theta = 1.57079632679;
+    p->taur = 0.;
+    p->tautheta = 0.1;
+    p->rlow = 0.9;
+    p->rhigh = 1.;
+    p->thetalow = 0.;
+    p->thetahigh = 6.28318530718;
+}
+
+namespace {
+bbo::SpiralEngine* as_spiral(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::SpiralEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a SpiralSearch handle");
+    return e;
+}
+}
+
+int bbo_spiral_configure(bbo_handle h, const bbo_spiral_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_spiral_configure: NULL parameters");
+        as_spiral(h)->configure(*p);
+    });
+}
+
+int bbo_spiral_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_spiral(h)->phase(phase); });
+}
+
+int bbo_spiral_inject_uniforms(bbo_handle h, const double *u, int count)
+{
+    return guarded(h, [&] { as_spiral(h)->inject_uniforms(u, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

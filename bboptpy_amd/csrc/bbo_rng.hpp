@@ -34,7 +34,8 @@ enum Stream : uint32_t {
     STREAM_DSA_DIR = 15,
     STREAM_DSA_MAP = 16,
     STREAM_DSA_R = 17,
-    STREAM_HEES_NORMAL = 18
+    STREAM_HEES_NORMAL = 18,
+    STREAM_SPIRAL = 19
 };
 
 struct u32x4 {

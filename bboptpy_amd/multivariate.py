@@ -770,6 +770,47 @@ class HEES(MultivariateSearch):
             self._handle, z.ctypes.data_as(C.c_void_p), z.size))
 
 
+class SpiralSearch(MultivariateSearch):
+    """SpiralSearch(mfev, tol, np=20, r=0.95, theta=1.57079632679, taur=0.0, tautheta=0.1, rlow=0.9,
+    rhigh=1.0, thetalow=0.0, thetahigh=6.28318530718) -- :344-351 (adaptive spiral optimization,
+    Tamura & Yasuda 2011, Yuzgec & Inac 2016; spiral.cpp).  `tol` is stored and unused and `guess` is
+    ignored, as in the reference; the box seeds the points and never clamps them; `converged` is
+    always False."""
+    _algo = _ffi.ALGO_SPIRAL
+
+    def __init__(self, mfev, tol, np=20, r=0.95, theta=1.57079632679, taur=0.0, tautheta=0.1,
+                 rlow=0.9, rhigh=1.0, thetalow=0.0, thetahigh=6.28318530718, **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.np = int(mfev), float(tol), int(np)
+        s = self._spiral = _ffi.SpiralParams()
+        s.r, s.theta, s.taur, s.tautheta = float(r), float(theta), float(taur), float(tautheta)
+        s.rlow, s.rhigh, s.thetalow, s.thetahigh = float(rlow), float(rhigh), float(thetalow), float(thetahigh)
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_spiral_configure(h, C.byref(self._spiral))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def phase(self, which):
+        """one part of a generation: 0 draw, 1 rotate, 2 evaluate, 3 best"""
+        self._check(_ffi.lib().bbo_spiral_phase(self._handle, int(which)))
+
+    def inject_uniforms(self, u):
+        """the raw uniforms of the following generations, [populations][np][4] in [0, 1): per point
+        the coin of r, the value of r, the coin of theta, the value of theta; None: the device draws"""
+        if u is None:
+            self._check(_ffi.lib().bbo_spiral_inject_uniforms(self._handle, None, 0))
+            return
+        u = _np.ascontiguousarray(_np.asarray(u, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_spiral_inject_uniforms(
+            self._handle, u.ctypes.data_as(C.c_void_p), u.size))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

@@ -56,7 +56,8 @@ typedef enum {
     BBO_ALGO_CHOLESKY_CMAES = 11, /* CholeskyCmaes src/multivariate/cma/cholesky_cmaes.h:37 */
     BBO_ALGO_JAYA = 12,        /* JayaSearch   src/multivariate/jaya/jaya.h:50        */
     BBO_ALGO_DSA = 13,         /* DSSearch     src/multivariate/pso/ds.h:33           */
-    BBO_ALGO_HEES = 14         /* Hees         src/multivariate/hees/hees.h:53        */
+    BBO_ALGO_HEES = 14,        /* Hees         src/multivariate/hees/hees.h:53        */
+    BBO_ALGO_SPIRAL = 15       /* SpiralSearch src/multivariate/spiral/spiral.h:39    */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -384,6 +385,28 @@ void bbo_hees_params_default(bbo_hees_params *p);   /* 1, 0 */
 int bbo_hees_configure(bbo_handle h, const bbo_hees_params *p);
 int bbo_hees_phase(bbo_handle h, int phase);
 int bbo_hees_inject_normals(bbo_handle h, const double *z, int count);
+
+/* ---- SpiralSearch (BBO_ALGO_SPIRAL): SpiralSearch(mfev,tol,np=20,r=0.95,theta=1.57079632679,taur=0.0,
+ * tautheta=0.1,rlow=0.9,rhigh=1.0,thetalow=0.0,thetahigh=6.28318530718)  py/multivariate_py.cpp:344-351,
+ * the adaptive spiral optimization algorithm (Tamura & Yasuda 2011; Yuzgec & Inac 2016; spiral.cpp).
+ * `mfev`, `tol` (stored and unused, as in the reference) and `np` travel in bbo_params
+ * (bbo_params_default gives np = 20); the eight other constructor arguments travel here.
+ * bbo_spiral_configure is legal between bbo_create and bbo_init; without it the defaults hold.
+ * BBO_ERR_ARG: not a SpiralSearch handle or a value that is not finite; BBO_ERR_STATE after bbo_init.
+ * Limits: n in [1, 512], np in [1, 65536], a finite box (it seeds the points and never clamps them);
+ * `guess` is ignored; converged is always 0 and "flag" is 0 or 2 (the budget).  Objective programs are
+ * refused by bbo_init; SpiralSearch is no base of a restart driver.
+ * bbo_spiral_phase: one part of a generation (0 the draws of r and theta, 1 the rotation, 2 the
+ * evaluation, 3 the best point, the counters and the budget); the four in order are bbo_iterate.
+ * bbo_spiral_inject_uniforms: `populations` tables of np x 4 raw uniforms in [0, 1) -- per point the
+ * coin of r, the value of r, the coin of theta, the value of theta -- which the following
+ * generations consume instead of the device's draws.  NULL returns to the device generator;
+ * bbo_init does the same. */
+typedef struct { double r, theta, taur, tautheta, rlow, rhigh, thetalow, thetahigh; } bbo_spiral_params;
+void bbo_spiral_params_default(bbo_spiral_params *p);   /* 0.95, 1.57079632679, 0, 0.1, 0.9, 1, 0, 6.28318530718 */
+int bbo_spiral_configure(bbo_handle h, const bbo_spiral_params *p);
+int bbo_spiral_phase(bbo_handle h, int phase);
+int bbo_spiral_inject_uniforms(bbo_handle h, const double *u, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
