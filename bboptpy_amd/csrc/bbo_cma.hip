@@ -33,6 +33,28 @@ int pick_maxt(int ld)
     return 8;
 }
 
+// rows a workgroup of the n = 128 batch kernels walks: one workgroup per CU when the rows in flight allow
+// it (long tile loops amortise the fill of the operand), in steps of 128, at most `cap`
+int rows_per_workgroup(long rows, int cap)
+{
+    const int rw = (int) ((rows / 256 + 127) / 128) * 128;
+    return std::max(128, std::min(cap, rw));
+}
+
+// sep_sample_sum is built per objective: the instantiation of obj (sep_sum_objective holds)
+template<int NC>
+auto sep_sum_kernel(int obj) -> void (*)(CmaDev, CmaConst)
+{
+    switch (obj) {
+    case OBJ_SPHERE: return sep_sample_sum<256, NC, OBJ_SPHERE>;
+    case OBJ_ELLIPSOID: return sep_sample_sum<256, NC, OBJ_ELLIPSOID>;
+    case OBJ_RASTRIGIN: return sep_sample_sum<256, NC, OBJ_RASTRIGIN>;
+    case OBJ_CIGAR: return sep_sample_sum<256, NC, OBJ_CIGAR>;
+    case OBJ_DISCUS: return sep_sample_sum<256, NC, OBJ_DISCUS>;
+    default: return sep_sample_sum<256, NC, OBJ_DIFFPOW>;
+    }
+}
+
 int gram_ldy(int ld)
 {
     // rows k, k+1 of the slab must land 32 banks apart for the k-major fragment reads
@@ -457,134 +479,107 @@ void CmaEngine::launch_post(int mode)
     }
 }
 
-void CmaEngine::launch_sample_eval()
+// Which sampler serves this shape, objective and set of switches, and with what geometry: a decision from
+// the engine's constants alone, like eig_route -- nothing is launched or allocated here.
+SampleRoute CmaEngine::sample_route() const
 {
     const CmaConst &c = c_;
-    bool zn_valid = false;
-    timer_.begin(stream_, K_SAMPLE);
+    SampleRoute r {};
+    r.gy = c.npop;
+    r.writes_zn = c.variant != 2;
+    auto is = [&r](SampleKernel k, int gx, int block, size_t lds) {
+        r.k = k;
+        r.gx = gx;
+        r.block = block;
+        r.lds = lds;
+    };
     if (c.variant == 2) {
         // separable: 16 lanes per candidate for short rows, one wavefront per candidate beyond
         // (a workgroup stages the generator's table once and then walks chunks of candidates:
         // ~4096 workgroups in all, 16 per CU)
         const int per_pop = std::max(1, 4096 / c.npop);
-        if (c.ld <= 256) {   // (beyond that the 16-row LDS tile would leave one workgroup per CU)
-            allow_lds((const void*) sep_sample_eval<16>, 128 * 1024);
-            const size_t lds = (size_t) 16 * c.ld * sizeof(double);
-            hipLaunchKernelGGL(sep_sample_eval<16>,
-                    dim3(std::min((c.lambda_pad + 15) / 16, per_pop), c.npop), dim3(256), lds,
-                    stream_, d_, c_);
-        } else if (c.ld <= 2048) {
+        if (c.ld <= 256)     // (beyond that the 16-row LDS tile would leave one workgroup per CU)
+            is(SK_SEP_16, std::min((c.lambda_pad + 15) / 16, per_pop), 256, (size_t) 16 * c.ld * sizeof(double));
+        else if (c.ld <= 2048) {
             // 8 rows per workgroup of 512: rows + table leave room for two workgroups (16
             // wavefronts) per CU up to ld = 1024
-            const size_t lds = (size_t) 8 * c.ld * sizeof(double);
-            const dim3 grid(std::min((c.lambda_pad + 7) / 8, per_pop), c.npop);
-            if (nothing_to_guard()) {   // (the benchmark's SEP)
-                if (sep_sum_objective(c.obj) && !(d_.dbg & DBG_SEP_ROWS_LDS)) {
-                    // sums of per-coordinate terms: no row in LDS (sep_sample_sum); 256-thread
-                    // workgroups, as many rows in flight as the registers allow
-                    const dim3 sgrid(std::min(c.lambda_pad / (4 * SEP_K), per_pop), c.npop);
-#define BBO_SEP_SUM(NCV, OBJV) hipLaunchKernelGGL((sep_sample_sum<256, NCV, OBJV>), sgrid, dim3(256), 0, stream_, d_, c_)
-#define BBO_SEP_SUM_OBJ(NCV) \
-                    switch (c.obj) { \
-                    case OBJ_SPHERE: BBO_SEP_SUM(NCV, OBJ_SPHERE); break; \
-                    case OBJ_ELLIPSOID: BBO_SEP_SUM(NCV, OBJ_ELLIPSOID); break; \
-                    case OBJ_RASTRIGIN: BBO_SEP_SUM(NCV, OBJ_RASTRIGIN); break; \
-                    case OBJ_CIGAR: BBO_SEP_SUM(NCV, OBJ_CIGAR); break; \
-                    case OBJ_DISCUS: BBO_SEP_SUM(NCV, OBJ_DISCUS); break; \
-                    default: BBO_SEP_SUM(NCV, OBJ_DIFFPOW); break; \
-                    }
-                    // (the cosine / pow objectives inline a long body per coordinate: with the
-                    // lane's 32 constants resident as well they spill or fall to one wavefront
-                    // per SIMD -- Rastrigin took 512 registers and ran slower than from LDS rows)
-                    if (c.ld == 1024 && c.obj != OBJ_RASTRIGIN && c.obj != OBJ_DIFFPOW) { BBO_SEP_SUM_OBJ(4) }
-                    else { BBO_SEP_SUM_OBJ(0) }
-#undef BBO_SEP_SUM_OBJ
-#undef BBO_SEP_SUM
-                } else {
-                    allow_lds((const void*) sep_sample_eval<64, 512, true>, 140 * 1024);
-                    hipLaunchKernelGGL((sep_sample_eval<64, 512, true>), grid, dim3(512), lds,
-                            stream_, d_, c_);
-                }
-            } else {
-                allow_lds((const void*) sep_sample_eval<64, 512>, 140 * 1024);
-                hipLaunchKernelGGL((sep_sample_eval<64, 512>), grid, dim3(512), lds, stream_,
-                        d_, c_);
-            }
-        } else {
-            allow_lds((const void*) sep_sample_eval<64>, 140 * 1024);
-            const size_t lds = (size_t) 4 * c.ld * sizeof(double);
-            hipLaunchKernelGGL(sep_sample_eval<64>,
-                    dim3(std::min((c.lambda_pad + 3) / 4, per_pop), c.npop), dim3(256), lds,
-                    stream_, d_, c_);
-        }
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-        c_.use_zn = 0;
-        return;
-    }
-    if (c.ld == 128 && (long) c.npop * c.lambda_pad >= sample128_min_rows_
+            is(SK_SEP_64_512, std::min((c.lambda_pad + 7) / 8, per_pop), 512, (size_t) 8 * c.ld * sizeof(double));
+            r.full = nothing_to_guard() ? 1 : 0;     // (the benchmark's SEP)
+            if (r.full && sep_sum_objective(c.obj) && !(d_.dbg & DBG_SEP_ROWS_LDS))
+                // sums of per-coordinate terms: no row in LDS (sep_sample_sum); 256-thread
+                // workgroups, as many rows in flight as the registers allow.  NC = 4: the lane's 32
+                // constants resident -- not for the cosine / pow objectives, which inline a long body per
+                // coordinate: with them they spill or fall to one wavefront per SIMD (Rastrigin took 512
+                // registers and ran slower than from LDS rows)
+                is(c.ld == 1024 && c.obj != OBJ_RASTRIGIN && c.obj != OBJ_DIFFPOW ? SK_SEP_SUM4 : SK_SEP_SUM,
+                        std::min(c.lambda_pad / (4 * SEP_K), per_pop), 256, 0);
+            else if (r.full)
+                r.k = SK_SEP_64_512_LEAN;
+        } else
+            is(SK_SEP_64, std::min((c.lambda_pad + 3) / 4, per_pop), 256, (size_t) 4 * c.ld * sizeof(double));
+    } else if (c.ld == 128 && (long) c.npop * c.lambda_pad >= sample128_min_rows_
             && (c.obj < 0 || frag_objective_ok(c.obj))) {
         // whole populations in flight: packed operand in LDS, normals drawn into the A fragments
-        // one workgroup per CU when the populations allow it: long tile loops amortise the fill
-        int rw = (int) (((long) c.npop * c.lambda_pad / 256 + 127) / 128) * 128;
-        rw = std::max(128, std::min(4096, rw));
-        allow_lds((const void*) cma_sample_eval128, 128 * 1024);
-        dim3 grid((c.lambda_pad + rw - 1) / rw, c.npop);
-        // the lean build of the tile loop where nothing needs guarding (M, C3)
-        const int full = nothing_to_guard() ? 1 : 0;
-        if (c.variant == 3 && chol_tri_) {      // (lower-triangular operand: 36 of 64 block pairs)
-            allow_lds((const void*) cma_sample_eval128_tri, 128 * 1024);
-            hipLaunchKernelGGL(cma_sample_eval128_tri, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
-                    full);
-        } else
-            hipLaunchKernelGGL(cma_sample_eval128, grid, dim3(512), 128 * 1024, stream_, d_, c_, rw,
-                    full);
-        zn_valid = true;
-    } else if (c.ld == 128 && (long) c.npop * (c.lambda_pad / 16) <= sample_wide_max_tiles_) {
+        // (CholeskyCMAES, lower-triangular operand: 36 of 64 block pairs)
+        r.rows_per_wg = rows_per_workgroup((long) c.npop * c.lambda_pad, 4096);
+        is(c.variant == 3 && chol_tri_ ? SK_EVAL128_TRI : SK_EVAL128, (c.lambda_pad + r.rows_per_wg - 1) / r.rows_per_wg,
+                512, 128 * 1024);
+        r.full = nothing_to_guard() ? 1 : 0;     // the lean build of the tile loop where nothing needs guarding (M, C3)
+    } else if (c.ld == 128 && (long) c.npop * (c.lambda_pad / 16) <= sample_wide_max_tiles_)
         // one population at a time: a 16-row tile per WORKGROUP, one column tile per wavefront (the
         // form C5's handful of candidates takes at n = 256) -- a wavefront's chain is 32 MFMAs and
         // one Philox call instead of 256 and eight
-        const size_t lds = (size_t) 16 * (c.ld + 2) * sizeof(double);
-        if (c.variant == 3 && chol_tri_)
-            hipLaunchKernelGGL((cma_sample_eval<1, 8, true>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds,
-                    stream_, d_, c_);
-        else
-            hipLaunchKernelGGL((cma_sample_eval<1, 8>), dim3(c.lambda_pad / 16, c.npop), dim3(512), lds, stream_,
-                    d_, c_);
-        zn_valid = true;
-    } else if (c.ld <= 128) {
+        is(c.variant == 3 && chol_tri_ ? SK_TILE8_TRI : SK_TILE8, c.lambda_pad / 16, 512,
+                (size_t) 16 * (c.ld + 2) * sizeof(double));
+    else if (c.ld <= 128)
         // 64 candidates per workgroup, packed operand held in registers
-        dim3 grid((c.lambda_pad + 63) / 64, c.npop);
-        const size_t lds = (size_t) 64 * (c.ld + 2) * sizeof(double);
-        allow_lds((const void*) cma_sample_eval64<1>, 80 * 1024);
-        allow_lds((const void*) cma_sample_eval64<2>, 80 * 1024);
-        if (c.ld <= 32)      // (8 k-steps of operand in registers instead of 32: twice the occupancy)
-            hipLaunchKernelGGL((cma_sample_eval64<1, 8>), grid, dim3(256), lds, stream_, d_, c_);
-        else if (c.ld <= 64)
-            hipLaunchKernelGGL(cma_sample_eval64<1>, grid, dim3(256), lds, stream_, d_, c_);
-        else
-            hipLaunchKernelGGL(cma_sample_eval64<2>, grid, dim3(256), lds, stream_, d_, c_);
-        zn_valid = true;
-    } else {
-        dim3 grid(c.lambda_pad / 16, c.npop);
+        // (ld <= 32: 8 k-steps of operand in registers instead of 32: twice the occupancy)
+        is(c.ld <= 32 ? SK_EVAL64_1_8 : c.ld <= 64 ? SK_EVAL64_1 : SK_EVAL64_2, (c.lambda_pad + 63) / 64, 256,
+                (size_t) 64 * (c.ld + 2) * sizeof(double));
+    else {
+        const int tiles = c.lambda_pad / 16;
         const size_t lds = (size_t) 16 * (c.ld + 2) * sizeof(double);
-        allow_lds((const void*) cma_sample_eval<8>, 80 * 1024);   // ld = 512: 65 792 bytes
         // a handful of row tiles on the whole chip (C5: two): one column tile per wavefront
-        if ((long) grid.x * grid.y <= 32 && c.ld <= 256 && !(d_.dbg & DBG_SAMPLE_4WAVES))
-            hipLaunchKernelGGL((cma_sample_eval<1, 16>), grid, dim3(1024), lds, stream_, d_, c_);
-        else
-            switch (pick_maxt(c.ld)) {
-            case 1: hipLaunchKernelGGL(cma_sample_eval<1>, grid, dim3(256), lds, stream_, d_, c_); break;
-            case 2: hipLaunchKernelGGL(cma_sample_eval<2>, grid, dim3(256), lds, stream_, d_, c_); break;
-            case 4: hipLaunchKernelGGL(cma_sample_eval<4>, grid, dim3(256), lds, stream_, d_, c_); break;
-            default: hipLaunchKernelGGL(cma_sample_eval<8>, grid, dim3(256), lds, stream_, d_, c_); break;
-            }
-        zn_valid = true;
+        if ((long) tiles * c.npop <= 32 && c.ld <= 256 && !(d_.dbg & DBG_SAMPLE_4WAVES))
+            is(SK_TILE16, tiles, 1024, lds);
+        else       // (ld > 128: pick_maxt is 4 or 8)
+            is(pick_maxt(c.ld) == 4 ? SK_EVAL_4 : SK_EVAL_8, tiles, 256, lds);
+    }
+    return r;
+}
+
+void CmaEngine::launch_sample_eval()
+{
+    const SampleRoute r = sample_route();
+    auto go = [&](auto kernel, int allow, auto... args) {      // allow: the kernel's LDS attribute, 0 = the default
+        if (allow) allow_lds((const void*) kernel, allow);
+        hipLaunchKernelGGL(kernel, dim3(r.gx, r.gy), dim3(r.block), r.lds, stream_, d_, c_, args...);
+    };
+    timer_.begin(stream_, K_SAMPLE);
+    switch (r.k) {
+    case SK_NONE: break;
+    case SK_SEP_16: go(sep_sample_eval<16>, 128 * 1024); break;
+    case SK_SEP_64_512: go(sep_sample_eval<64, 512>, 140 * 1024); break;
+    case SK_SEP_64_512_LEAN: go(sep_sample_eval<64, 512, true>, 140 * 1024); break;
+    case SK_SEP_SUM: go(sep_sum_kernel<0>(c_.obj), 0); break;
+    case SK_SEP_SUM4: go(sep_sum_kernel<4>(c_.obj), 0); break;
+    case SK_SEP_64: go(sep_sample_eval<64>, 140 * 1024); break;
+    case SK_EVAL128: go(cma_sample_eval128, 128 * 1024, r.rows_per_wg, r.full); break;
+    case SK_EVAL128_TRI: go(cma_sample_eval128_tri, 128 * 1024, r.rows_per_wg, r.full); break;
+    case SK_TILE8: go(cma_sample_eval<1, 8>, 0); break;
+    case SK_TILE8_TRI: go(cma_sample_eval<1, 8, true>, 0); break;
+    case SK_EVAL64_1_8: go(cma_sample_eval64<1, 8>, 0); break;
+    case SK_EVAL64_1: go(cma_sample_eval64<1>, 80 * 1024); break;
+    case SK_EVAL64_2: go(cma_sample_eval64<2>, 80 * 1024); break;
+    case SK_TILE16: go(cma_sample_eval<1, 16>, 0); break;
+    case SK_EVAL_4: go(cma_sample_eval<4>, 0); break;
+    case SK_EVAL_8: go(cma_sample_eval<8>, 80 * 1024); break;      // ld = 512: 65 792 bytes
     }
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
     // ||z||^2 stands in for the whitened norm only if this launch wrote it and no x was clamped
-    c_.use_zn = (zn_valid && !c.bound) ? 1 : 0;
+    c_.use_zn = (r.writes_zn && !c_.bound) ? 1 : 0;
+    last_sample_ = r;
 }
 
 void CmaEngine::launch_rank()
@@ -625,104 +620,100 @@ void CmaEngine::launch_rank()
     BBO_HIP(hipGetLastError());
 }
 
-void CmaEngine::launch_update(bool with_cov)
+// The kernels of one update of the distribution, with their geometry: a decision like sample_route.
+UpdateRoute CmaEngine::update_route(bool norms_done, bool with_cov) const
 {
     const CmaConst &c = c_;
+    UpdateRoute r {};
+    auto add = [&r](UpdateKernel k, int slot, int gx, int gy, int gz, int block, size_t lds = 0, int arg = 0) {
+        r.step[r.count++] = UpdateRoute::Step { k, slot, gx, gy, gz, block, lds, arg };
+    };
+    const int NT = c.ld / 16, LT = NT * (NT + 1) / 2;      // 16 x 16 tiles of a row, of the lower triangle
     if (c.variant == 3) {
         // paths and C' read the old factor; chol_factor (launch_eigen's slot in the order of a
         // generation, but part of this phase: BBO_PHASE_EIGEN does nothing here) writes the new one
-        timer_.begin(stream_, K_PATHS);
-        hipLaunchKernelGGL(chol_paths, dim3(c.npop), dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        const int NT = c.ld / 16;
-        timer_.begin(stream_, K_GRAM);
-        hipLaunchKernelGGL(chol_cprime, dim3(NT * (NT + 1) / 2, c.npop), dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
         const int in_lds = c.ld <= 128 ? 1 : 0;
-        const size_t lds = in_lds ? (size_t) c.ld * (c.ld + 1) * sizeof(double) : 0;
-        timer_.begin(stream_, K_COV);
-        hipLaunchKernelGGL(chol_factor, dim3(c.npop), dim3(256), lds, stream_, d_, c_, in_lds);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-        return;
+        add(UK_CHOL_PATHS, K_PATHS, c.npop, 1, 1, 256);
+        add(UK_CHOL_CPRIME, K_GRAM, LT, c.npop, 1, 256);
+        add(UK_CHOL_FACTOR, K_COV, c.npop, 1, 1, 256, in_lds ? (size_t) c.ld * (c.ld + 1) * sizeof(double) : 0, in_lds);
+        return r;
     }
     if (c.variant == 2) {
-        timer_.begin(stream_, K_GRAM);
-        hipLaunchKernelGGL(sep_moments, dim3(c.splits, (c.ld + 511) / 512, c.npop), dim3(256), 0,
-                stream_, d_, c_);
-        timer_.end(stream_);
-        timer_.begin(stream_, K_PATHS);
-        hipLaunchKernelGGL(sep_paths, dim3(c.npop), dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-        return;
+        add(UK_SEP_MOMENTS, K_GRAM, c.splits, (c.ld + 511) / 512, c.npop, 256);
+        add(UK_SEP_PATHS, K_PATHS, c.npop, 1, 1, 256);
+        return r;
     }
-    const bool norms_done = rank_wrote_norms_;
-    rank_wrote_norms_ = false;             // (one ranking serves one update)
-    if (c.variant == 1 && !norms_done) {
-        timer_.begin(stream_, K_WHITEN);
+    if (c.variant == 1 && !norms_done) {      // the whitened norms of the worst mu, where the ranking has not written them
         if (c.ld == 128 && (long) c.npop * c.mu_pad >= 256 * 128) {
-            int rw = (int) (((long) c.npop * c.mu_pad / 256 + 127) / 128) * 128;
-            rw = std::max(128, std::min(2048, rw));
-            const size_t lds = (size_t) (128 * 128 + 128) * sizeof(double);
-            allow_lds((const void*) cma_whiten128, 132 * 1024);
-            dim3 grid128((c.mu_pad + rw - 1) / rw, c.npop);
-            hipLaunchKernelGGL(cma_whiten128, grid128, dim3(512), lds, stream_, d_, c_, rw);
-        } else {
-        dim3 grid(c.mu_pad / 16, c.npop);
-        const size_t lds = (size_t) (16 * (c.ld + 2) + 64) * sizeof(double);
-        allow_lds((const void*) cma_whiten<8>, 80 * 1024);        // ld = 512: 66 304 bytes
-        switch (pick_maxt(c.ld)) {
-        case 1: hipLaunchKernelGGL(cma_whiten<1>, grid, dim3(256), lds, stream_, d_, c_); break;
-        case 2: hipLaunchKernelGGL(cma_whiten<2>, grid, dim3(256), lds, stream_, d_, c_); break;
-        case 4: hipLaunchKernelGGL(cma_whiten<4>, grid, dim3(256), lds, stream_, d_, c_); break;
-        default: hipLaunchKernelGGL(cma_whiten<8>, grid, dim3(256), lds, stream_, d_, c_); break;
-        }
-        }
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+            const int rw = rows_per_workgroup((long) c.npop * c.mu_pad, 2048);
+            add(UK_WHITEN128, K_WHITEN, (c.mu_pad + rw - 1) / rw, c.npop, 1, 512, (size_t) (128 * 128 + 128) * sizeof(double),
+                    rw);
+        } else
+            add(UK_WHITEN, K_WHITEN, c.mu_pad / 16, c.npop, 1, 256, (size_t) (16 * (c.ld + 2) + 64) * sizeof(double),
+                    pick_maxt(c.ld));
     }
-    if (c.ld == 128) {
-        const size_t lds = (size_t) (2 * G128_CH * G128_LDY + 4 * G128_CH) * sizeof(double);
-        allow_lds((const void*) cma_gram128, 80 * 1024);
-        timer_.begin(stream_, K_GRAM);
-        if (d_.dbg & DBG_GRAM128_LDS)   // (diagnostic: the LDS-staged form, same bits)
-            hipLaunchKernelGGL(cma_gram128, dim3(c.splits, c.npop), dim3(256), lds, stream_, d_, c_);
-        else
-            hipLaunchKernelGGL(cma_gram128s, dim3(c.splits, c.npop), dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-    } else {
-        const int NT = c.ld / 16, LT = NT * (NT + 1) / 2;
-        const int ldy = gram_ldy(c.ld);
-        dim3 grid(c.splits, (LT + 4 * GRAM_TPW - 1) / (4 * GRAM_TPW), c.npop);
-        const size_t lds = gram_lds_bytes(c.ld, c.rps);
-        allow_lds((const void*) cma_gram, (int) GRAM_LDS_MAX);
-        timer_.begin(stream_, K_GRAM);
-        hipLaunchKernelGGL(cma_gram, grid, dim3(256), lds, stream_, d_, c_, ldy);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-    }
-    timer_.begin(stream_, K_PATHS);
+    if (c.ld != 128)
+        add(UK_GRAM, K_GRAM, c.splits, (LT + 4 * GRAM_TPW - 1) / (4 * GRAM_TPW), c.npop, 256, gram_lds_bytes(c.ld, c.rps),
+                gram_ldy(c.ld));
+    else if (d_.dbg & DBG_GRAM128_LDS)      // (diagnostic: the LDS-staged form, same bits)
+        add(UK_GRAM128, K_GRAM, c.splits, c.npop, 1, 256, (size_t) (2 * G128_CH * G128_LDY + 4 * G128_CH) * sizeof(double));
+    else
+        add(UK_GRAM128S, K_GRAM, c.splits, c.npop, 1, 256);
     if (c.lazy_isc && c.n >= 64 && !(d_.dbg & DBG_PATHS_LAZY256))
         // (1024 threads: a quarter of the dependent round trips of the two passes over B)
-        hipLaunchKernelGGL(cma_paths_lazy1k, dim3(c.npop), dim3(1024), 0, stream_, d_, c_);
-    else if (c.lazy_isc)
-        hipLaunchKernelGGL(cma_paths_lazy, dim3(c.npop), dim3(256), 0, stream_, d_, c_);
+        add(UK_PATHS_LAZY1K, K_PATHS, c.npop, 1, 1, 1024);
     else
-        hipLaunchKernelGGL(cma_paths, dim3(c.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+        add(c.lazy_isc ? UK_PATHS_LAZY : UK_PATHS, K_PATHS, c.npop, 1, 1, 256);
     // (with_cov == false: the fixed-shape eigensolver that follows forms C on its load, and the slot
     // is not opened -- a slot without calls is left out of the kernel table)
-    if (with_cov) {
-        const int total = c.n * (c.n + 1) / 2;
-        dim3 grid((total + 255) / 256, c.npop);
-        timer_.begin(stream_, K_COV);
-        hipLaunchKernelGGL(cma_cov, grid, dim3(256), 0, stream_, d_, c_);
+    if (with_cov) add(UK_COV, K_COV, (c.n * (c.n + 1) / 2 + 255) / 256, c.npop, 1, 256);
+    return r;
+}
+
+// cma_whiten<MAXT> of pick_maxt's four values (the one place they are switched on: the samplers of ld > 128
+// are two ids of SampleKernel)
+static auto whiten_kernel(int maxt) -> void (*)(CmaDev, CmaConst)
+{
+    switch (maxt) {
+    case 1: return cma_whiten<1>;
+    case 2: return cma_whiten<2>;
+    case 4: return cma_whiten<4>;
+    default: return cma_whiten<8>;
+    }
+}
+
+void CmaEngine::launch_update(bool with_cov)
+{
+    const bool norms_done = rank_wrote_norms_;
+    rank_wrote_norms_ = false;             // (one ranking serves one update)
+    const UpdateRoute r = update_route(norms_done, with_cov);
+    for (int i = 0; i < r.count; i++) {
+        const UpdateRoute::Step &s = r.step[i];
+        auto go = [&](auto kernel, int allow, auto... args) {      // allow: the kernel's LDS attribute, 0 = the default
+            if (allow) allow_lds((const void*) kernel, allow);
+            hipLaunchKernelGGL(kernel, dim3(s.gx, s.gy, s.gz), dim3(s.block), s.lds, stream_, d_, c_, args...);
+        };
+        timer_.begin(stream_, s.slot);
+        switch (s.k) {
+        case UK_CHOL_PATHS: go(chol_paths, 0); break;
+        case UK_CHOL_CPRIME: go(chol_cprime, 0); break;
+        case UK_CHOL_FACTOR: go(chol_factor, 0, s.arg); break;
+        case UK_SEP_MOMENTS: go(sep_moments, 0); break;
+        case UK_SEP_PATHS: go(sep_paths, 0); break;
+        case UK_WHITEN128: go(cma_whiten128, 132 * 1024, s.arg); break;
+        case UK_WHITEN: go(whiten_kernel(s.arg), s.arg == 8 ? 80 * 1024 : 0); break;      // ld = 512: 66 304 bytes
+        case UK_GRAM128S: go(cma_gram128s, 0); break;
+        case UK_GRAM128: go(cma_gram128, 80 * 1024); break;
+        case UK_GRAM: go(cma_gram, (int) GRAM_LDS_MAX, s.arg); break;
+        case UK_PATHS: go(cma_paths, 0); break;
+        case UK_PATHS_LAZY: go(cma_paths_lazy, 0); break;
+        case UK_PATHS_LAZY1K: go(cma_paths_lazy1k, 0); break;
+        case UK_COV: go(cma_cov, 0); break;
+        }
         timer_.end(stream_);
         BBO_HIP(hipGetLastError());
     }
+    last_update_ = r;
 }
 
 int CmaEngine::next_mw_xcd()
@@ -973,6 +964,7 @@ bool CmaEngine::small_fused_ok() const
 
 void CmaEngine::launch_small(int gens, bool honor_stop)
 {
+    small_fused_ = true;
     c_.honor_stop = honor_stop ? 1 : 0;
     c_.use_zn = c_.bound ? 0 : 1;          // cma_sample_eval64 always hands down ||z||^2
     const int ldy = gram_ldy(c_.ld);
@@ -994,6 +986,7 @@ void CmaEngine::generation(bool honor_stop)
         launch_small(1, honor_stop);
         return;
     }
+    small_fused_ = false;
     c_.honor_stop = honor_stop ? 1 : 0;
     launch_sample_eval();
     if (obj_.needs_host()) host_evaluate();
@@ -1283,6 +1276,14 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         return o.copy(ids, last_route_.count);
     }
     if (k == "rank_route") return o.one(last_rank_);                      // the form of the last launch_rank: RankKernel
+    if (k == "sample_route") return o.one(last_sample_.k);                // the last launch_sample_eval: SampleKernel, -1 before any
+    if (k == "sample_lean") return o.one(last_sample_.full);              // ... took a lean build
+    if (k == "update_route") {                                            // the last launch_update in launch order: UpdateKernel ids
+        double ids[sizeof(last_update_.step) / sizeof(last_update_.step[0])];
+        for (int i = 0; i < last_update_.count; i++) ids[i] = last_update_.step[i].k;
+        return o.copy(ids, last_update_.count);
+    }
+    if (k == "small_fused") return o.one(small_fused_ ? 1 : 0);           // the last generation or chunk ran in cma_small_generations
     if (k == "splits") return o.one(c.splits);                            // Gram slabs per population
     if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups

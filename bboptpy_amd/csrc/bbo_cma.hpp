@@ -164,6 +164,50 @@ struct EigRoute {
     long mw_workgroups;   // > 0: spread kernels that need this many workgroups reserved (mw_reserve)
 };
 
+// The samplers.  get "sample_route" returns the id of the last launch_sample_eval, so this order is that
+// key's contract: append, never renumber.  (sep_sample_sum's objective argument is not part of the id.)
+enum SampleKernel : int {
+    SK_NONE = -1,                                                           // no launch yet
+    SK_SEP_16 = 0, SK_SEP_64_512, SK_SEP_64_512_LEAN, SK_SEP_SUM, SK_SEP_SUM4, SK_SEP_64,   // 0 .. 5: sep_sample_eval<16>,
+                                    // <64, 512>, <64, 512, true>, sep_sample_sum<256, 0>, <256, 4>, sep_sample_eval<64>
+    SK_EVAL128, SK_EVAL128_TRI, SK_TILE8, SK_TILE8_TRI,                     // 6 .. 9: cma_sample_eval128, _tri,
+                                                                            // cma_sample_eval<1, 8>, <1, 8, true>
+    SK_EVAL64_1_8, SK_EVAL64_1, SK_EVAL64_2,                                // 10 .. 12: cma_sample_eval64<1, 8>, <1>, <2>
+    SK_TILE16, SK_EVAL_4, SK_EVAL_8                                         // 13 .. 15: cma_sample_eval<1, 16>, <4>, <8>
+};
+
+// What one launch_sample_eval does: plain data, computed by CmaEngine::sample_route and by nothing else.
+struct SampleRoute {
+    SampleKernel k;
+    int gx, gy, block;      // grid (gx, gy), threads of a workgroup
+    size_t lds;             // dynamic LDS bytes
+    int rows_per_wg;        // cma_sample_eval128 / _tri: kernel argument
+    int full;               // the lean build (get "sample_lean"): kernel argument of those two, the template
+                            // argument of sep_sample_eval<64, 512, true>, always for sep_sample_sum
+    bool writes_zn;         // the kernel hands down ||z||^2 of every candidate
+};
+
+// The kernels of one launch_update.  get "update_route" returns the ids of the last one in launch order:
+// append, never renumber.  (cma_whiten<MAXT> is one id.)
+enum UpdateKernel : int {
+    UK_CHOL_PATHS = 0, UK_CHOL_CPRIME, UK_CHOL_FACTOR, UK_SEP_MOMENTS, UK_SEP_PATHS,     // 0 .. 4
+    UK_WHITEN128, UK_WHITEN, UK_GRAM128S, UK_GRAM128, UK_GRAM,                           // 5 .. 9
+    UK_PATHS, UK_PATHS_LAZY, UK_PATHS_LAZY1K, UK_COV                                     // 10 .. 13
+};
+
+// What one launch_update does: plain data, computed by CmaEngine::update_route and by nothing else.
+struct UpdateRoute {
+    struct Step {
+        UpdateKernel k;
+        int slot;           // the profile's slot of the launch (cma_whiten, cma_gram, cma_paths, cma_cov)
+        int gx, gy, gz, block;
+        size_t lds;
+        int arg;            // chol_factor: in_lds; cma_whiten128: rows per workgroup; cma_whiten: MAXT; cma_gram: ldy
+    };
+    Step step[4];
+    int count;
+};
+
 class CmaEngine: public Engine<CmaScal> {
 public:
     explicit CmaEngine(const bbo_params &p);
@@ -211,6 +255,9 @@ private:
     void launch_post(int mode);
     void launch_rank();
     void launch_update(bool with_cov = true);
+    SampleRoute sample_route() const;
+    // norms_done: the ranking wrote the whitened norms; with_cov: cma_cov is not left to the eigensolver
+    UpdateRoute update_route(bool norms_done, bool with_cov) const;
     // spread_ok: the spread reduction may be used; fuse_ok: no cma_cov has gone before (a generation)
     EigRoute eig_route(bool spread_ok = true, bool fuse_ok = false) const;
     void launch_eigen(EigRoute r);
@@ -240,6 +287,9 @@ private:
     bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
     EigRoute last_route_ {};           // what the last launch_eigen did (get "eig_route", "eig_fixed128", "cov_fused")
+    SampleRoute last_sample_ { SK_NONE };   // what the last launch_sample_eval did (get "sample_route", "sample_lean")
+    UpdateRoute last_update_ {};       // what the last launch_update did (get "update_route")
+    bool small_fused_ = false;         // the last generation or chunk was a cma_small_generations launch (get "small_fused")
     int last_rank_ = -1;               // the form the last launch_rank took: RankKernel (get "rank_route"), -1 before
     bool rank_wrote_norms_ = false;    // this generation's cma_rank_sort wrote S: no whiten launch
     int last_n_ = -1;

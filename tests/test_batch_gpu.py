@@ -99,9 +99,11 @@ def test_fused_small_generations_equal_the_kernel_sequence(hip, variant, n, lam,
     a, b = make(0), make(64)
     a.run(13)                  # 8 + 5 generations: two launches
     b.run(13)
+    assert (int(a.get_state("small_fused")[0]), int(b.get_state("small_fused")[0])) == (1, 0)
     for _ in range(12):        # and one generation per launch
         a.iterate()
         b.iterate()
+    assert (int(a.get_state("small_fused")[0]), int(b.get_state("small_fused")[0])) == (1, 0)
     for p in (0, P // 2, P - 1):
         for key in ("xmean", "sigma", "pc", "ps", "C", "B", "D", "invsqrtC", "arx", "fitness",
                     "fit_idx", "it", "fev", "flag", "best_hist", "kth_hist", "fbest", "fworst"):
@@ -122,6 +124,7 @@ def test_fused_small_run_freezes_stopped_populations(hip):
         if dbg:
             g.set_state("dbg", [64.])
         g.run(10000)
+        assert int(g.get_state("small_fused")[0]) == (0 if dbg else 1)
         runs.append([(g.solution(p).n_evals, g.solution(p).converged, g.solution(p).x.tolist(),
                       int(g.get_state("it", p)[0])) for p in range(P)])
     assert runs[0] == runs[1]
@@ -143,6 +146,9 @@ def test_lean_sampler_build_equals_the_general_one(hip, lam, P):
         if dbg:
             g.set_state("dbg", [float(dbg)])
         g.run(5)
+        # enum SampleKernel (bbo_cma.hpp): 6 = cma_sample_eval128, both sides; its lean build without the bit
+        assert int(g.get_state("sample_route")[0]) == 6
+        assert int(g.get_state("sample_lean")[0]) == (0 if dbg else 1)
         runs.append([(g.get_state("arx", p), g.get_state("fitness", p), g.get_state("C", p),
                       g.get_state("sigma", p)) for p in (0, P - 1)])
     for a, b in zip(runs[0], runs[1]):
@@ -163,6 +169,9 @@ def test_lean_separable_sampler_equals_the_general_one(hip):
         g.initialize(hip.objectives.ellipsoid, lo, up, guess)
         g.set_state("dbg", [float(dbg)])
         g.run(5)
+        # enum SampleKernel (bbo_cma.hpp): 2 = sep_sample_eval<64, 512, true>, the lean build; 1 = <64, 512>
+        assert int(g.get_state("sample_route")[0]) == (2 if dbg == 1048576 else 1)
+        assert int(g.get_state("sample_lean")[0]) == (1 if dbg == 1048576 else 0)
         runs.append([(g.get_state("arx", p), g.get_state("fitness", p), g.get_state("D", p), g.get_state("csep", p),
                       g.get_state("sigma", p)) for p in (0, P - 1)])
     for a, b in zip(runs[0], runs[1]):
@@ -190,6 +199,10 @@ def test_sum_on_draw_separable_sampler(hip, obj, n, lam):
             g.set_state("dbg", [float(dbg)])
         g.run(2)
         g.phase(_ffi.PHASE_SAMPLE_EVALUATE)
+        # enum SampleKernel (bbo_cma.hpp): 3, 4 = sep_sample_sum<256, 0> and <256, 4> (n = 1024, no cosine / pow
+        # body); 2 = sep_sample_eval<64, 512, true>
+        sum4 = n == 1024 and obj not in ("rastrigin", "diffpow")
+        assert int(g.get_state("sample_route")[0]) == (2 if dbg else 4 if sum4 else 3)
         out.append([(g.get_state("arx", p).reshape(lam, n), g.get_state("fitness", p)[:lam]) for p in range(P)])
     t = np.arange(n) / (n - 1.)
     for (Xa, fa), (Xb, fb) in zip(*out):

@@ -373,5 +373,10 @@ def test_triangular_sampler_equals_the_full_operand_sampler(hip, P, guarded):
         for p in (0, P - 1):
             for key in ("arx", "fitness", "fit_idx", "xmean", "A", "sigma"):
                 np.testing.assert_array_equal(hs[0].get_state(key, p), hs[1].get_state(key, p))
+    # enum SampleKernel (bbo_cma.hpp): 8, 9 = cma_sample_eval<1, 8> and its triangular form, 6, 7 = cma_sample_eval128
+    # and cma_sample_eval128_tri, whose lean build runs unless guarded
+    assert [int(g.get_state("sample_route")[0]) for g in hs] == ([9, 8] if P == 1 else [7, 6])
+    if P == 16:
+        assert [int(g.get_state("sample_lean")[0]) for g in hs] == [0 if guarded else 1] * 2
     A = hs[0].get_state("A", 0).reshape(n, n)
     assert np.abs(np.tril(A, -1)).max() > 0.               # (a factor with off-diagonals was sampled through)

@@ -441,6 +441,8 @@ def test_single_run_sampler_and_ranking_equal_the_batch_kernels(hip, lam, obj):
         # enum RankKernel (bbo_rank.hpp): 8 = count8, 9 = count32, 10 = count64.  One population: 32 slices
         # from lambda = 512, 64 from 2048; below 512 both sides count with 8 (only the sampler differs)
         assert int(g.get_state("rank_route")[0]) == ((10 if lam >= 2048 else 9 if lam >= 512 else 8) if wide else 8)
+        # enum SampleKernel (bbo_cma.hpp): 8 = cma_sample_eval<1, 8>, 12 = cma_sample_eval64<2>
+        assert int(g.get_state("sample_route")[0]) == (8 if wide else 12)
         out.append({k: g.get_state(k).copy() for k in ("arx", "fitness", "fit_idx", "xmean", "sigma", "C", "ps")})
     for k in out[0]:
         np.testing.assert_array_equal(out[0][k], out[1][k], err_msg=k)

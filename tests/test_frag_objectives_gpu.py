@@ -130,6 +130,8 @@ def _generation(hip, obj, n, lam, batch, record=False, seed=20241, pops=P):
         g.set_state("record_normals", [1.0])
     it = int(g.get_state("it")[0])
     g.phase(_ffi.PHASE_SAMPLE_EVALUATE)
+    # enum SampleKernel (bbo_cma.hpp): 6 = cma_sample_eval128 -- what the knob selects, and nothing else does here
+    assert (int(g.get_state("sample_route")[0]) == 6) == bool(batch)
     X = np.stack([g.get_state("arx", p).reshape(lam, n) for p in range(pops)])
     f = np.stack([g.get_state("fitness", p) for p in range(pops)])
     z = g.get_state("zlast", 0).copy() if record else None
