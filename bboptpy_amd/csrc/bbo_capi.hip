@@ -7,6 +7,7 @@
 #include "bbo_dsa.hpp"
 #include "bbo_hees.hpp"
 #include "bbo_spiral.hpp"
+#include "bbo_nshs.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -22,6 +23,7 @@ Optimizer* make_jaya_engine(const bbo_params &p);     // bbo_jaya.hip
 Optimizer* make_dsa_engine(const bbo_params &p);      // bbo_dsa.hip
 Optimizer* make_hees_engine(const bbo_params &p);     // bbo_hees.hip
 Optimizer* make_spiral_engine(const bbo_params &p);   // bbo_spiral.hip
+Optimizer* make_nshs_engine(const bbo_params &p);     // bbo_nshs.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -173,6 +175,7 @@ void bbo_params_default(bbo_params *p, int algo)
     p->npps = 0;
     p->pcauchy = -1.;
     if (algo == BBO_ALGO_SPIRAL) p->np = 20;   /* py/multivariate_py.cpp:348 */
+    if (algo == BBO_ALGO_NSHS) p->poll_every = 0;   /* the engine's own chunk: iterations, not generations */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -224,6 +227,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_SPIRAL:
             h->opt.reset(bbo::make_spiral_engine(*params));
+            break;
+        case BBO_ALGO_NSHS:
+            h->opt.reset(bbo::make_nshs_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -605,6 +611,39 @@ int bbo_spiral_phase(bbo_handle h, int phase)
 int bbo_spiral_inject_uniforms(bbo_handle h, const double *u, int count)
 {
     return guarded(h, [&] { as_spiral(h)->inject_uniforms(u, count); });
+}
+
+void bbo_nshs_params_default(bbo_nshs_params *p)
+{
+    if (!p) return;
+    p->fstdmin = 0.0001;        // py/multivariate_py.cpp:204
+}
+
+namespace {
+bbo::NshsEngine* as_nshs(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::NshsEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an NSHS handle");
+    return e;
+}
+}
+
+int bbo_nshs_configure(bbo_handle h, const bbo_nshs_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_nshs_configure: NULL parameters");
+        as_nshs(h)->configure(*p);
+    });
+}
+
+int bbo_nshs_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_nshs(h)->phase(phase); });
+}
+
+int bbo_nshs_inject_uniforms(bbo_handle h, const double *u, int count)
+{
+    return guarded(h, [&] { as_nshs(h)->inject_uniforms(u, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

@@ -174,7 +174,7 @@ public:
                 }
             if (touched) scal_.upload(sc.data(), sc.size());
         }
-        const int poll = params_.poll_every > 0 ? params_.poll_every : 8;
+        const int poll = params_.poll_every > 0 ? params_.poll_every : default_poll();
         int done = 0;
         while (done < max_generations) {
             if (all_stopped()) break;
@@ -224,6 +224,8 @@ protected:
     // every poll's download of the scalars, before their stop flags are tested
     virtual void inspect(const std::vector<Scal>&) {}
     virtual int chunk_limit(int want) { return want; }
+    // generations between polls when bbo_params::poll_every is 0
+    virtual int default_poll() const { return 8; }
     virtual void launch_chunk(int gens)
     {
         for (int g = 0; g < gens; g++) generation(true);

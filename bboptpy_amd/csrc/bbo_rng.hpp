@@ -35,7 +35,8 @@ enum Stream : uint32_t {
     STREAM_DSA_MAP = 16,
     STREAM_DSA_R = 17,
     STREAM_HEES_NORMAL = 18,
-    STREAM_SPIRAL = 19
+    STREAM_SPIRAL = 19,
+    STREAM_NSHS = 20
 };
 
 struct u32x4 {

@@ -811,6 +811,55 @@ class SpiralSearch(MultivariateSearch):
             self._handle, u.ctypes.data_as(C.c_void_p), u.size))
 
 
+class NSHS(MultivariateSearch):
+    """NSHS(mfev, hms, fstdmin=0.0001) -- :200-205 (novel self-adaptive harmony search, Luo 2013;
+    nshs.cpp).  Steady-state: one iteration is one candidate and one evaluation; run() advances whole
+    chunks of iterations per launch (`poll_every` iterations; default: the engine's own chunk).
+    `guess` is ignored, as in the reference; `converged` is always False; the budget is met exactly.
+    Extension `record_draws=True` keeps the four raw uniforms of every coordinate of the last
+    iteration (get_state("draws"))."""
+    _algo = _ffi.ALGO_NSHS
+    _accepts_program = False
+
+    def __init__(self, mfev, hms, fstdmin=0.0001, **ext):
+        record_draws = ext.pop("record_draws", False)
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.np = int(mfev), int(hms)
+        s = self._nshs = _ffi.NshsParams()
+        s.fstdmin = float(fstdmin)
+        self._record_draws = bool(record_draws)
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_nshs_configure(h, C.byref(self._nshs))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def initialize(self, f, lower, upper, guess):
+        super().initialize(f, lower, upper, guess)
+        if self._record_draws:
+            self.set_state("record_draws", [1.])
+
+    def phase(self, which):
+        """one part of an iteration: 0 generate, 1 evaluate, 2 replace"""
+        self._check(_ffi.lib().bbo_nshs_phase(self._handle, int(which)))
+
+    def inject_uniforms(self, u):
+        """the raw uniforms of the following iterations, [populations][n][4] in [0, 1): per
+        coordinate the coin, the row (row j as (j + 0.5) / hms), the fresh value, the adjustment;
+        None: the device draws"""
+        if u is None:
+            self._check(_ffi.lib().bbo_nshs_inject_uniforms(self._handle, None, 0))
+            return
+        u = _np.ascontiguousarray(_np.asarray(u, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_nshs_inject_uniforms(
+            self._handle, u.ctypes.data_as(C.c_void_p), u.size))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

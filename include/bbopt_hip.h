@@ -57,7 +57,8 @@ typedef enum {
     BBO_ALGO_JAYA = 12,        /* JayaSearch   src/multivariate/jaya/jaya.h:50        */
     BBO_ALGO_DSA = 13,         /* DSSearch     src/multivariate/pso/ds.h:33           */
     BBO_ALGO_HEES = 14,        /* Hees         src/multivariate/hees/hees.h:53        */
-    BBO_ALGO_SPIRAL = 15       /* SpiralSearch src/multivariate/spiral/spiral.h:39    */
+    BBO_ALGO_SPIRAL = 15,      /* SpiralSearch src/multivariate/spiral/spiral.h:39    */
+    BBO_ALGO_NSHS = 16         /* NSHS         src/multivariate/harmony/nshs.h        */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -407,6 +408,32 @@ void bbo_spiral_params_default(bbo_spiral_params *p);   /* 0.95, 1.57079632679, 
 int bbo_spiral_configure(bbo_handle h, const bbo_spiral_params *p);
 int bbo_spiral_phase(bbo_handle h, int phase);
 int bbo_spiral_inject_uniforms(bbo_handle h, const double *u, int count);
+
+/* ---- NSHS (BBO_ALGO_NSHS): NSHS(mfev,hms,fstdmin=0.0001)  py/multivariate_py.cpp:200-205, the novel
+ * self-adaptive harmony search (Luo 2013; nshs.cpp).  `mfev` and `np` (which is hms: required, no
+ * default) travel in bbo_params; fstdmin travels here.  For this algorithm bbo_params_default gives
+ * poll_every = 0: bbo_run then launches the engine's own chunk of whole ITERATIONS per poll (one
+ * iteration is one evaluation), a positive poll_every is that many iterations per launch.
+ * bbo_nshs_configure is legal between bbo_create and bbo_init; without it the default holds.
+ * BBO_ERR_ARG: not an NSHS handle or a value that is not finite or negative; BBO_ERR_STATE after
+ * bbo_init.
+ * Limits: n in [1, 512], hms in [1, 4096], a finite box; `guess` is ignored; converged is always 0 and
+ * "flag" is 0 or 2 (the budget, reached exactly: fev == mfev).  With mfev <= hms bbo_init evaluates
+ * the memory, bbo_run does nothing and bbo_iterate / bbo_nshs_phase return BBO_ERR_STATE (the
+ * reference would divide by mfev - hms <= 0).  Objective programs are refused by bbo_init; NSHS is no
+ * base of a restart driver.
+ * bbo_nshs_phase: one part of an iteration (0 the candidate, 1 its evaluation, 2 the replacement of
+ * the worst row with fstd, best, worst, the counters and the budget); the three in order are
+ * bbo_iterate.
+ * bbo_nshs_inject_uniforms: `populations` tables of n x 4 raw uniforms in [0, 1) -- per coordinate
+ * the coin, the row, the fresh value, the adjustment; the row j travels as (j + 0.5) / hms and is
+ * mapped back by floor(u hms) -- which the following iterations consume instead of the device's
+ * draws.  NULL returns to the device generator; bbo_init does the same. */
+typedef struct { double fstdmin; } bbo_nshs_params;
+void bbo_nshs_params_default(bbo_nshs_params *p);   /* 0.0001 */
+int bbo_nshs_configure(bbo_handle h, const bbo_nshs_params *p);
+int bbo_nshs_phase(bbo_handle h, int phase);
+int bbo_nshs_inject_uniforms(bbo_handle h, const double *u, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
