@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
-    ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS = range(17)
+    ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES = range(18)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -27,6 +27,10 @@ HEES_PHASE_SAMPLE, HEES_PHASE_RANK, HEES_PHASE_UPDATE, HEES_PHASE_FINISH = range
 SPIRAL_PHASE_DRAW, SPIRAL_PHASE_ROTATE, SPIRAL_PHASE_EVALUATE, SPIRAL_PHASE_BEST = range(4)
 # bbo_nshs_phase
 NSHS_PHASE_GENERATE, NSHS_PHASE_EVALUATE, NSHS_PHASE_REPLACE = range(3)
+# bbo_lm_phase
+LM_PHASE_SAMPLE, LM_PHASE_EVALUATE, LM_PHASE_RANK, LM_PHASE_UPDATE, LM_PHASE_HISTORY_STOP = range(5)
+# LmCMAES "flag": the CMA engines' codes and sigma < 1e-16
+LM_FLAG_MAXITER, LM_FLAG_TOLHISTFUN, LM_FLAG_EQUALFUNVALS, LM_FLAG_SIGMA = 1, 2, 3, 11
 
 BUILTIN_IDS = {"sphere": 0, "rosenbrock": 1, "rastrigin": 2, "ellipsoid": 3, "ackley": 4,
                "griewank": 5, "cigar": 6, "discus": 7, "diffpow": 8, "schwefel12": 9}
@@ -81,6 +85,11 @@ class SpiralParams(C.Structure):
 class NshsParams(C.Structure):
     """bbo_nshs_params: the constructor argument of NSHS that bbo_params has no field for"""
     _fields_ = [("fstdmin", C.c_double)]
+
+
+class LmParams(C.Structure):
+    """bbo_lm_params: LmCMAES's constructor arguments that bbo_params has no field for"""
+    _fields_ = [("memory", C.c_int), ("rademacher", C.c_int), ("usenew", C.c_int)]
 
 
 class Objective(C.Structure):
@@ -158,6 +167,11 @@ def lib():
     L.bbo_nshs_configure.argtypes = [C.c_void_p, C.POINTER(NshsParams)]
     L.bbo_nshs_phase.argtypes = [C.c_void_p, C.c_int]
     L.bbo_nshs_inject_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.bbo_lm_params_default.argtypes = [C.POINTER(LmParams)]
+    L.bbo_lm_params_default.restype = None
+    L.bbo_lm_configure.argtypes = [C.c_void_p, C.POINTER(LmParams)]
+    L.bbo_lm_phase.argtypes = [C.c_void_p, C.c_int]
+    L.bbo_lm_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -171,7 +185,7 @@ def lib():
                  "bbo_dsa_configure", "bbo_hees_configure", "bbo_hees_phase",
                  "bbo_hees_inject_normals", "bbo_spiral_configure", "bbo_spiral_phase",
                  "bbo_spiral_inject_uniforms", "bbo_nshs_configure", "bbo_nshs_phase",
-                 "bbo_nshs_inject_uniforms"):
+                 "bbo_nshs_inject_uniforms", "bbo_lm_configure", "bbo_lm_phase", "bbo_lm_inject_draws"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -190,6 +204,7 @@ EXPORTED_SYMBOLS = (
     "bbo_spiral_params_default", "bbo_spiral_configure", "bbo_spiral_phase",
     "bbo_spiral_inject_uniforms",
     "bbo_nshs_params_default", "bbo_nshs_configure", "bbo_nshs_phase", "bbo_nshs_inject_uniforms",
+    "bbo_lm_params_default", "bbo_lm_configure", "bbo_lm_phase", "bbo_lm_inject_draws",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

@@ -8,6 +8,7 @@
 #include "bbo_hees.hpp"
 #include "bbo_spiral.hpp"
 #include "bbo_nshs.hpp"
+#include "bbo_lm.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -24,6 +25,7 @@ Optimizer* make_dsa_engine(const bbo_params &p);      // bbo_dsa.hip
 Optimizer* make_hees_engine(const bbo_params &p);     // bbo_hees.hip
 Optimizer* make_spiral_engine(const bbo_params &p);   // bbo_spiral.hip
 Optimizer* make_nshs_engine(const bbo_params &p);     // bbo_nshs.hip
+Optimizer* make_lm_engine(const bbo_params &p);       // bbo_lm.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -230,6 +232,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_NSHS:
             h->opt.reset(bbo::make_nshs_engine(*params));
+            break;
+        case BBO_ALGO_LM_CMAES:
+            h->opt.reset(bbo::make_lm_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -644,6 +649,42 @@ int bbo_nshs_phase(bbo_handle h, int phase)
 int bbo_nshs_inject_uniforms(bbo_handle h, const double *u, int count)
 {
     return guarded(h, [&] { as_nshs(h)->inject_uniforms(u, count); });
+}
+
+void bbo_lm_params_default(bbo_lm_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp:126-127
+    p->memory = 0;
+    p->rademacher = 1;
+    p->usenew = 1;
+}
+
+namespace {
+bbo::LmEngine* as_lm(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::LmEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an LmCMAES handle");
+    return e;
+}
+}
+
+int bbo_lm_configure(bbo_handle h, const bbo_lm_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_lm_configure: NULL parameters");
+        as_lm(h)->configure(*p);
+    });
+}
+
+int bbo_lm_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_lm(h)->phase(phase); });
+}
+
+int bbo_lm_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { as_lm(h)->inject_draws(table, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

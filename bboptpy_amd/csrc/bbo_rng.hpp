@@ -36,7 +36,9 @@ enum Stream : uint32_t {
     STREAM_DSA_R = 17,
     STREAM_HEES_NORMAL = 18,
     STREAM_SPIRAL = 19,
-    STREAM_NSHS = 20
+    STREAM_NSHS = 20,
+    STREAM_LM_Z = 21,
+    STREAM_LM_SUBSET = 22
 };
 
 struct u32x4 {

@@ -350,10 +350,73 @@ class CholeskyCMAES(BaseCMAES):
         p.sigma0, p.bound, p.ranked = float(sigma0), int(bool(bound)), int(bool(ranked))
 
 
+class LmCMAES(BaseCMAES):
+    """LmCMAES(mfev, tol, np, memory=0, sigma0=2., bound=False, rademacher=True, usenew=True) -- :123-128
+    (limited-memory CMA-ES, Loshchilov 2014 / 2015; lm_cmaes.cpp): m direction vectors instead of a
+    covariance matrix, O(m n) per candidate, n up to 4096.  memory <= 0 means m = int(2 sqrt(n)).
+    `bound` clamps the mean to the box and never a candidate, as in the reference.  An engine of its
+    own: no base of IPopCMAES / BiPopCMAES and no objective programs yet, and the methods BaseCMAES
+    adds for the restart drivers (set_params, set_seed, evaluate) and inject_normals raise
+    NotImplementedError; the draws are injected with inject_draws."""
+    _algo = _ffi.ALGO_LM_CMAES
+    _accepts_program = False
+
+    def __init__(self, mfev, tol, np, memory=0, sigma0=2., bound=False, rademacher=True, usenew=True, **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.np = int(mfev), float(tol), int(np)
+        p.sigma0, p.bound = float(sigma0), int(bool(bound))
+        s = self._lm = _ffi.LmParams()
+        s.memory, s.rademacher, s.usenew = int(memory), int(bool(rademacher)), int(bool(usenew))
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_lm_configure(h, C.byref(self._lm))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def phase(self, which):
+        """one part of a generation: 0 sample, 1 evaluate, 2 rank, 3 update of mean / pc / memory /
+        sigma, 4 history + counters + stop test"""
+        self._check(_ffi.lib().bbo_lm_phase(self._handle, int(which)))
+
+    def inject_draws(self, table):
+        """the draws of the following G generations, [G][populations][ceil(np / 2)][n + 1]: per "+"
+        candidate its z (normals, or +-1) and the normal of the subset selection (ignored where the
+        reference draws none); None: the device draws"""
+        if table is None:
+            self._check(_ffi.lib().bbo_lm_inject_draws(self._handle, None, 0))
+            return
+        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_lm_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+
+    def _not_here(self, what):
+        raise NotImplementedError("LmCMAES has no %s: it runs on an engine of its own, outside the "
+                                  "restart drivers' CMA-ES engine" % what)
+
+    def inject_normals(self, z):
+        self._not_here("inject_normals (use inject_draws)")
+
+    def set_params(self, np, sigma0, mfev):
+        self._not_here("set_params")
+
+    def set_seed(self, seed):
+        self._not_here("set_seed (use reseed)")
+
+    def evaluate(self, x):
+        self._not_here("evaluate")
+
+
 class _RestartDriver(MultivariateSearch):
     _accepts_program = True
 
     def __init__(self, base, **ext):
+        if isinstance(base, LmCMAES):
+            raise TypeError("LmCMAES is no base of a restart driver yet: base must be a CMAES, ActiveCMAES, "
+                            "SepCMAES or CholeskyCMAES optimizer")
         if not isinstance(base, BaseCMAES):
             raise TypeError("base must be a CMA-ES optimizer (CMAES / ActiveCMAES / SepCMAES / "
                             "CholeskyCMAES)")

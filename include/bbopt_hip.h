@@ -58,7 +58,8 @@ typedef enum {
     BBO_ALGO_DSA = 13,         /* DSSearch     src/multivariate/pso/ds.h:33           */
     BBO_ALGO_HEES = 14,        /* Hees         src/multivariate/hees/hees.h:53        */
     BBO_ALGO_SPIRAL = 15,      /* SpiralSearch src/multivariate/spiral/spiral.h:39    */
-    BBO_ALGO_NSHS = 16         /* NSHS         src/multivariate/harmony/nshs.h        */
+    BBO_ALGO_NSHS = 16,        /* NSHS         src/multivariate/harmony/nshs.h        */
+    BBO_ALGO_LM_CMAES = 17     /* LmCmaes      src/multivariate/cma/lm_cmaes.h:43     */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -434,6 +435,32 @@ void bbo_nshs_params_default(bbo_nshs_params *p);   /* 0.0001 */
 int bbo_nshs_configure(bbo_handle h, const bbo_nshs_params *p);
 int bbo_nshs_phase(bbo_handle h, int phase);
 int bbo_nshs_inject_uniforms(bbo_handle h, const double *u, int count);
+
+/* ---- LmCMAES (BBO_ALGO_LM_CMAES): LmCMAES(mfev,tol,np,memory=0,sigma0=2,bound=False,
+ * rademacher=True,usenew=True)  py/multivariate_py.cpp:123-128, the limited-memory CMA-ES (Loshchilov
+ * 2014 / 2015; lm_cmaes.cpp): m direction vectors instead of a covariance matrix, O(m n) per
+ * candidate.  mfev, tol, np (lambda), sigma0 and bound travel in bbo_params; memory (<= 0: m =
+ * int(2 sqrt(n))), rademacher and usenew travel here.  bbo_lm_configure is legal between bbo_create
+ * and bbo_init; without it the defaults hold.  BBO_ERR_ARG: not an LmCMAES handle; BBO_ERR_STATE
+ * after bbo_init.
+ * Limits, each refused by bbo_init with a message: n in [1, 4096], np in [2, 4096], m in [1, 256], a
+ * finite sigma0.  `bound` clamps the mean to the box and never a candidate, as in the reference.
+ * "flag": 1 MaxIter, 2 TolHistFun, 3 EqualFunVals (the CMA engines' codes), 11 sigma < 1e-16.
+ * Objective programs are refused by bbo_init; LmCMAES is no base of a restart driver.
+ * bbo_lm_phase: one part of a generation (0 the sampling, 1 the evaluation, 2 the ranking, 3 the
+ * update of the mean, pc, the memory and sigma, 4 the histories, the counters and the stop tests);
+ * the five in order are bbo_iterate.
+ * bbo_lm_inject_draws: G >= 1 generations of draws, count = G * populations * ceil(np / 2) * (n + 1)
+ * doubles as [G][populations][ceil(np / 2)][n + 1]: a row is the z of a "+" candidate (normals, or
+ * the +-1 of the Rademacher coin as values) followed by the normal g of selectSubset (ignored where
+ * the reference draws none: usenew off, or fewer than two slots in use).  The following G
+ * generations consume them; sampling a generation beyond them is BBO_ERR_STATE.  NULL returns to
+ * the device generator; bbo_init does the same. */
+typedef struct { int memory, rademacher, usenew; } bbo_lm_params;
+void bbo_lm_params_default(bbo_lm_params *p);   /* 0, 1, 1 */
+int bbo_lm_configure(bbo_handle h, const bbo_lm_params *p);
+int bbo_lm_phase(bbo_handle h, int phase);
+int bbo_lm_inject_draws(bbo_handle h, const double *table, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
