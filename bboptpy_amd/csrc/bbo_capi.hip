@@ -9,6 +9,7 @@
 #include "bbo_spiral.hpp"
 #include "bbo_nshs.hpp"
 #include "bbo_lm.hpp"
+#include "bbo_xnes.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -26,6 +27,7 @@ Optimizer* make_hees_engine(const bbo_params &p);     // bbo_hees.hip
 Optimizer* make_spiral_engine(const bbo_params &p);   // bbo_spiral.hip
 Optimizer* make_nshs_engine(const bbo_params &p);     // bbo_nshs.hip
 Optimizer* make_lm_engine(const bbo_params &p);       // bbo_lm.hip
+Optimizer* make_xnes_engine(const bbo_params &p);     // bbo_xnes.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -235,6 +237,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_LM_CMAES:
             h->opt.reset(bbo::make_lm_engine(*params));
+            break;
+        case BBO_ALGO_XNES:
+            h->opt.reset(bbo::make_xnes_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -685,6 +690,42 @@ int bbo_lm_phase(bbo_handle h, int phase)
 int bbo_lm_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { as_lm(h)->inject_draws(table, count); });
+}
+
+void bbo_xnes_params_default(bbo_xnes_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp (xNES: a0 = 1., etamu = 1.); from_guess is an extension
+    p->a0 = 1.;
+    p->etamu = 1.;
+    p->from_guess = 0;
+}
+
+namespace {
+bbo::XnesEngine* as_xnes(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::XnesEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an xNES handle");
+    return e;
+}
+}
+
+int bbo_xnes_configure(bbo_handle h, const bbo_xnes_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_xnes_configure: NULL parameters");
+        as_xnes(h)->configure(*p);
+    });
+}
+
+int bbo_xnes_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_xnes(h)->phase(phase); });
+}
+
+int bbo_xnes_inject_normals(bbo_handle h, const double *z, int count)
+{
+    return guarded(h, [&] { as_xnes(h)->inject_normals(z, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

@@ -38,7 +38,8 @@ enum Stream : uint32_t {
     STREAM_SPIRAL = 19,
     STREAM_NSHS = 20,
     STREAM_LM_Z = 21,
-    STREAM_LM_SUBSET = 22
+    STREAM_LM_SUBSET = 22,
+    STREAM_XNES_NORMAL = 23
 };
 
 struct u32x4 {

@@ -833,6 +833,45 @@ class HEES(MultivariateSearch):
             self._handle, z.ctypes.data_as(C.c_void_p), z.size))
 
 
+class xNES(MultivariateSearch):
+    """xNES(mfev, tol, a0=1., etamu=1.) -- the exponential natural evolution strategy (Glasmachers et
+    al. 2010; xnes.cpp).  The population size is 4 + int(3 ln n).  As in the reference the mean starts
+    at the ORIGIN with sigma = a0 and `guess` and the bounds are not used; from_guess=True (an
+    extension, keyword-only) starts the mean at `guess`.  solution() is the best point of the last
+    generation; get_state("xbest") / ("fbest") hold the best ever seen.  n is at most 512."""
+    _algo = _ffi.ALGO_XNES
+
+    def __init__(self, mfev, tol, a0=1., etamu=1., *, from_guess=False, **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol = int(mfev), float(tol)
+        x = self._xnes = _ffi.XnesParams()
+        x.a0, x.etamu, x.from_guess = float(a0), float(etamu), int(bool(from_guess))
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_xnes_configure(h, C.byref(self._xnes))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def phase(self, which):
+        """one part of a generation: 0 sample + evaluate, 1 rank, 2 small step, 3 adapt"""
+        self._check(_ffi.lib().bbo_xnes_phase(self._handle, int(which)))
+
+    def inject_normals(self, z):
+        """the normals of the following G generations, [G][populations][np][n] in sampling order;
+        None: the device draws"""
+        if z is None:
+            self._check(_ffi.lib().bbo_xnes_inject_normals(self._handle, None, 0))
+            return
+        z = _np.ascontiguousarray(_np.asarray(z, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_xnes_inject_normals(
+            self._handle, z.ctypes.data_as(C.c_void_p), z.size))
+
+
 class SpiralSearch(MultivariateSearch):
     """SpiralSearch(mfev, tol, np=20, r=0.95, theta=1.57079632679, taur=0.0, tautheta=0.1, rlow=0.9,
     rhigh=1.0, thetalow=0.0, thetahigh=6.28318530718) -- :344-351 (adaptive spiral optimization,

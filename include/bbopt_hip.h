@@ -59,7 +59,8 @@ typedef enum {
     BBO_ALGO_HEES = 14,        /* Hees         src/multivariate/hees/hees.h:53        */
     BBO_ALGO_SPIRAL = 15,      /* SpiralSearch src/multivariate/spiral/spiral.h:39    */
     BBO_ALGO_NSHS = 16,        /* NSHS         src/multivariate/harmony/nshs.h        */
-    BBO_ALGO_LM_CMAES = 17     /* LmCmaes      src/multivariate/cma/lm_cmaes.h:43     */
+    BBO_ALGO_LM_CMAES = 17,    /* LmCmaes      src/multivariate/cma/lm_cmaes.h:43     */
+    BBO_ALGO_XNES = 18         /* xNES         src/multivariate/nes/xnes.h:48         */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -461,6 +462,31 @@ void bbo_lm_params_default(bbo_lm_params *p);   /* 0, 1, 1 */
 int bbo_lm_configure(bbo_handle h, const bbo_lm_params *p);
 int bbo_lm_phase(bbo_handle h, int phase);
 int bbo_lm_inject_draws(bbo_handle h, const double *table, int count);
+
+/* ---- xNES (BBO_ALGO_XNES): xNES(mfev,tol,a0=1.,etamu=1.), the exponential natural evolution strategy
+ * (Glasmachers et al. 2010; xnes.cpp).  mfev and tol travel in bbo_params; a0 (the first sigma), etamu
+ * and from_guess travel here.  The population size is 4 + int(3 ln n), no parameter.  As in the
+ * reference the mean starts at the ORIGIN and neither `guess` nor the box is used; from_guess = 1 (an
+ * extension) starts the mean at `guess`.  bbo_solution returns the best point of the LAST generation
+ * (the reference's _points[0]); "xbest" / "fbest" hold the best ever seen.  "stop": 1 |f_best -
+ * f_worst| < tol in the ranked generation, 2 fev >= mfev (fev is a multiple of np).
+ * bbo_xnes_configure is legal between bbo_create and bbo_init; BBO_ERR_ARG: not an xNES handle, or a0
+ * not finite or not positive; BBO_ERR_STATE after bbo_init.  Limits: n in [1, 512]; objective
+ * programs are refused by bbo_init; xNES is no base of a restart driver.
+ * bbo_xnes_phase: one part of a generation (0 sample + evaluate, 1 rank, 2 the small step: mean,
+ * sigma, counters, stop test and the operator of the update of B, 3 the update of B); the four in
+ * order are bbo_iterate.
+ * bbo_xnes_inject_normals: count = G * populations * np * n doubles as [G][populations][np][n], the
+ * normals of the following G generations in sampling order; sampling beyond them is BBO_ERR_STATE.
+ * NULL returns to the device generator; bbo_init does the same.
+ * "route": 1 the low-rank update (n >= "lowrank_min_n", default 32, settable in [16, 32]), 0 the
+ * dense one.  "fact_fail": generations whose low-rank factorisation met a pivot that was not finite
+ * or not above 2^-40 of its diagonal (equal or dependent rows); B is left as it is in such a one. */
+typedef struct { double a0, etamu; int from_guess; } bbo_xnes_params;
+void bbo_xnes_params_default(bbo_xnes_params *p);   /* 1., 1., 0 */
+int bbo_xnes_configure(bbo_handle h, const bbo_xnes_params *p);
+int bbo_xnes_phase(bbo_handle h, int phase);
+int bbo_xnes_inject_normals(bbo_handle h, const double *z, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
