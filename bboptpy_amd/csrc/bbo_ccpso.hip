@@ -556,12 +556,14 @@ int CcpsoEngine::set(const std::string &k, int p, const double *in, int count)
         yhat_.upload(v.data(), c_.ld, (size_t) p * c_.ld);
         return 1;
     }
-    if (k == "fyhat" || k == "fev" || k == "improved") {
+    // "stop": freeze this population for run(), like the DE / PSO / CMA engines' key
+    if (k == "fyhat" || k == "fev" || k == "improved" || k == "stop") {
         BBO_REQUIRE(count == 1, "set: wrong element count");
         CcpScal s;
         scal_.download(&s, 1, p);
         if (k == "fyhat") s.fyhat = in[0];
         else if (k == "fev") s.fev = (int) in[0];
+        else if (k == "stop") s.stop = (int) in[0];
         else s.improved = in[0] != 0. ? 1 : 0;
         scal_.upload(&s, 1, p);
         return 1;

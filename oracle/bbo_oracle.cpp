@@ -1069,15 +1069,20 @@ int orc_zig_strip(int i, double *w, uint32_t *k, double *f)
     *f = bbo_zig_f[i];
     return BBO_ZIG_N;
 }
-void orc_philox_normals(uint64_t seed, int gen, int rows, int n, double *out)
+/* the sampling normals of population `sub` of a batched CMA handle, generation `gen` */
+void orc_philox_normals_sub(uint64_t seed, int sub, int gen, int rows, int n, double *out)
 {
     for (int k = 0; k < rows; k++)
         for (int j = 0; j < n; j++) {
             double z[4];
             bbo_normal_quad(seed, (uint32_t) k, (uint32_t) bbo_cma_quad_of_column(j),
-                    (uint32_t) gen, bbo_stream(BBO_STREAM_CMA_NORMAL, 0), z);
+                    (uint32_t) gen, bbo_stream(BBO_STREAM_CMA_NORMAL, (uint32_t) sub), z);
             out[(size_t) k * n + j] = z[bbo_cma_slot_of_column(j)];
         }
+}
+void orc_philox_normals(uint64_t seed, int gen, int rows, int n, double *out)
+{
+    orc_philox_normals_sub(seed, 0, gen, rows, n, out);
 }
 
 double orc_objective(int obj, int n, const double *x)

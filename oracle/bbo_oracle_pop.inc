@@ -2526,6 +2526,17 @@ void orc_pop_set_mode(void *p, int kind, int sync, int rng_mode, uint64_t seed)
     }
 }
 
+/* Philox sub-stream of a Philox-mode handle (same `kind` as orc_pop_set_mode): object `sub` draws
+ * what population `sub` of a batched device handle draws.  Call before init. */
+void orc_pop_set_sub(void *p, int kind, int sub)
+{
+    if (kind == 0) static_cast<De*>(p)->sub = sub;
+    else if (kind == 4) static_cast<Ccpso*>(p)->sub = sub;
+    else if (kind == 3) static_cast<Cso*>(p)->sub = sub;
+    else if (kind == 2) static_cast<Sansde*>(p)->sub = sub;
+    else static_cast<Apso*>(p)->sub = sub;
+}
+
 void orc_apso_set_chunk(void *p, int chunk) { static_cast<Apso*>(p)->chunk = chunk; }
 
 /* ---- restart drivers ------------------------------------------------------------ */

@@ -164,6 +164,13 @@ class _Lib:
             f("philox").restype = None
             f("philox_normals").argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, _dp]
             f("philox_normals").restype = None
+            if hasattr(L, p + "philox_normals_sub"):
+                f("philox_normals_sub").argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    _dp]
+                f("philox_normals_sub").restype = None
+            if hasattr(L, p + "pop_set_sub"):
+                f("pop_set_sub").argtypes = [C.c_void_p, C.c_int, C.c_int]
+                f("pop_set_sub").restype = None
             if hasattr(L, p + "log_unit"):
                 f("log_unit").argtypes = [C.c_double]
                 f("log_unit").restype = C.c_double
@@ -270,14 +277,23 @@ class Handle:
     def step(self, name, *args):
         self.lib.f("cma_" + name)(self.ptr, *args)
 
+    _POP_KIND = {"shade": 0, "jade": 0, "apso": 1, "sansde": 2, "cso": 3, "ccpso": 4}
+
     def set_mode(self, sync, rng_mode=RNG_MT, seed=0):
         """SHADE / JADE / APSO: async (reference) or sync (device) semantics + generator;
         restart drivers: generator of the driver and of its inner CMA"""
         if self.alg in ("bipop", "ipop"):
             self.lib.f("restart_set_rng")(self.ptr, rng_mode, seed)
         else:
-            kind = {"apso": 1, "sansde": 2, "cso": 3, "ccpso": 4}.get(self.alg, 0)
+            kind = self._POP_KIND.get(self.alg, 0)
             self.lib.f("pop_set_mode")(self.ptr, kind, 1 if sync else 0, rng_mode, seed)
+
+    def set_sub(self, sub):
+        """swarm classes, Philox mode (oracle only), before init(): draw from Philox sub-stream
+        `sub`, what population `sub` of a batched device handle draws from"""
+        if self.alg not in self._POP_KIND:
+            raise ValueError("%s has no population sub-stream" % self.alg)
+        self.lib.f("pop_set_sub")(self.ptr, self._POP_KIND[self.alg], int(sub))
 
     def set_chunk(self, chunk):
         """APSO, sync mode (oracle only): particles between two refreshes of the swarm's best inside
