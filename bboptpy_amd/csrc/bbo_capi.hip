@@ -10,6 +10,7 @@
 #include "bbo_nshs.hpp"
 #include "bbo_lm.hpp"
 #include "bbo_xnes.hpp"
+#include "bbo_amalgam.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -28,6 +29,7 @@ Optimizer* make_spiral_engine(const bbo_params &p);   // bbo_spiral.hip
 Optimizer* make_nshs_engine(const bbo_params &p);     // bbo_nshs.hip
 Optimizer* make_lm_engine(const bbo_params &p);       // bbo_lm.hip
 Optimizer* make_xnes_engine(const bbo_params &p);     // bbo_xnes.hip
+Optimizer* make_amalgam_engine(const bbo_params &p);  // bbo_amalgam.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -97,14 +99,14 @@ bbo::ObjectiveSpec to_spec(const bbo_objective *o)
 
 // bbo_params as a caller built against an earlier header knows it ends where `stol` begins.  Such a
 // caller can only name the algorithms of its header, so the fields appended for CholeskyCMAES are
-// read and written for BBO_ALGO_CHOLESKY_CMAES and BBO_ALGO_DSA (whose `stol` travels there: a
-// caller that can name algorithm 13 has the long struct) alone: nothing here touches memory past
+// read and written for BBO_ALGO_CHOLESKY_CMAES, BBO_ALGO_DSA and BBO_ALGO_AMALGAM (whose `stol` travels
+// there: a caller that can name algorithm 13 or 19 has the long struct) alone: nothing here touches memory past
 // the struct the caller allocated.
 constexpr size_t PARAMS_BASE_BYTES = offsetof(bbo_params, stol);
 
 inline bool has_long_params(int algo)
 {
-    return algo == BBO_ALGO_CHOLESKY_CMAES || algo == BBO_ALGO_DSA;
+    return algo == BBO_ALGO_CHOLESKY_CMAES || algo == BBO_ALGO_DSA || algo == BBO_ALGO_AMALGAM;
 }
 
 bbo_params own_copy(const bbo_params *params)
@@ -240,6 +242,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_XNES:
             h->opt.reset(bbo::make_xnes_engine(*params));
+            break;
+        case BBO_ALGO_AMALGAM:
+            h->opt.reset(bbo::make_amalgam_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -726,6 +731,50 @@ int bbo_xnes_phase(bbo_handle h, int phase)
 int bbo_xnes_inject_normals(bbo_handle h, const double *z, int count)
 {
     return guarded(h, [&] { as_xnes(h)->inject_normals(z, count); });
+}
+
+void bbo_amalgam_params_default(bbo_amalgam_params *p)
+{
+    if (!p) return;
+    // defaults of py/multivariate_py.cpp (AMALGAM: iamalgam, noparam, print = true); the rest are extensions
+    p->iamalgam = 1;
+    p->noparam = 1;
+    p->print = 1;
+    p->keep_elite = 0;
+    p->concurrent = 1;
+    p->substream = 0;
+}
+
+namespace {
+bbo::AmalgamEngine* as_amalgam(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::AmalgamEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an AMALGAM handle");
+    return e;
+}
+}
+
+int bbo_amalgam_configure(bbo_handle h, const bbo_amalgam_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_amalgam_configure: NULL parameters");
+        as_amalgam(h)->configure(*p);
+    });
+}
+
+int bbo_amalgam_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_amalgam(h)->phase(phase); });
+}
+
+int bbo_amalgam_inject_draws(bbo_handle h, const double *z, int zcount, const int *rows, int rcount)
+{
+    return guarded(h, [&] { as_amalgam(h)->inject_draws(z, zcount, rows, rcount); });
+}
+
+int bbo_amalgam_inject_points(bbo_handle h, const double *x, int count)
+{
+    return guarded(h, [&] { as_amalgam(h)->inject_points(x, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

@@ -39,7 +39,10 @@ enum Stream : uint32_t {
     STREAM_NSHS = 20,
     STREAM_LM_Z = 21,
     STREAM_LM_SUBSET = 22,
-    STREAM_XNES_NORMAL = 23
+    STREAM_XNES_NORMAL = 23,
+    STREAM_AMALGAM_NORMAL = 24,
+    STREAM_AMALGAM_SHIFT = 25,
+    STREAM_AMALGAM_INIT = 26
 };
 
 struct u32x4 {

@@ -872,6 +872,85 @@ class xNES(MultivariateSearch):
             self._handle, z.ctypes.data_as(C.c_void_p), z.size))
 
 
+class AMALGAM(MultivariateSearch):
+    """AMALGAM(mfev, tol, stol, np=0, iamalgam=True, noparam=True, print=True) -- AMaLGaM-IDEA and
+    iAMaLGaM-IDEA (Bosman, Grahl & Thierens 2009; amalgam.cpp).  np = 0 means int(10 sqrt n) for
+    iAMaLGaM and int(17 + 3 n^1.5) for AMaLGaM.  The population starts uniform in the box (a finite box
+    is mandatory); `guess` is not read.  As in the reference the sampler redraws the x of the elite
+    row 0 and keeps its old value, and solution() is that row; keep_elite=True (an extension,
+    keyword-only) leaves its x alone.  get_state("xbest") / ("fbest") hold the best point ever
+    evaluated.  noparam=True, the default, is the parameter-free mode: iterate() is one stage of
+    2^(s/2) inner runs on growing populations, run as the populations of one inner handle
+    (concurrent=True) or one after another (concurrent=False) with the same results; it needs
+    populations=1 and print=True writes the reference's table.  n is at most 512, np in [3, 65536]."""
+    _algo = _ffi.ALGO_AMALGAM
+    _accepts_program = False
+
+    def __init__(self, mfev, tol, stol, np=0, iamalgam=True, noparam=True, print=True, *,
+                 keep_elite=False, concurrent=True, **ext):
+        substream = ext.pop("substream", 0)
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.tol, p.stol, p.np = int(mfev), float(tol), float(stol), int(np)
+        a = self._amalgam = _ffi.AmalgamParams()
+        a.iamalgam, a.noparam, a.print = int(bool(iamalgam)), int(bool(noparam)), int(bool(print))
+        a.keep_elite, a.concurrent, a.substream = int(bool(keep_elite)), int(bool(concurrent)), int(substream)
+        if a.noparam and p.populations != 1:
+            raise ValueError("AMALGAM: the parameter-free mode (noparam=True) works on populations=1 only")
+        self._points = None
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_amalgam_configure(h, C.byref(self._amalgam))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def _flush(self):
+        if self._amalgam.print and self._amalgam.noparam:
+            sys.stdout.flush()      # the table is written by the library
+
+    def optimize(self, f, lower, upper, guess):
+        self._flush()
+        self._send_points()
+        return super().optimize(f, lower, upper, guess)
+
+    def initialize(self, f, lower, upper, guess):
+        self._flush()
+        self._send_points()
+        super().initialize(f, lower, upper, guess)
+
+    def _send_points(self):
+        if self._points is None:
+            return
+        x, self._points = self._points, None
+        self._check(_ffi.lib().bbo_amalgam_inject_points(
+            self._ensure_handle(), x.ctypes.data_as(C.c_void_p), x.size))
+
+    def phase(self, which):
+        """one part of a generation: 0 distribution, 1 sample + evaluate, 2 adapt + stop"""
+        self._check(_ffi.lib().bbo_amalgam_phase(self._handle, int(which)))
+
+    def inject_points(self, x):
+        """the initial points of the next initialize() / optimize(), [populations][np][n]"""
+        self._points = None if x is None else _np.ascontiguousarray(
+            _np.asarray(x, dtype=_np.float64)).ravel()
+
+    def inject_draws(self, z, rows=None):
+        """the draws of the following G generations: the normals [G][populations][np][n] in
+        sampling order and the rows that take the anticipated mean shift, [G][populations][nams],
+        each in 1 .. np - 1; None: the device draws"""
+        if z is None:
+            self._check(_ffi.lib().bbo_amalgam_inject_draws(self._handle, None, 0, None, 0))
+            return
+        z = _np.ascontiguousarray(_np.asarray(z, dtype=_np.float64)).ravel()
+        r = _np.ascontiguousarray(_np.asarray([] if rows is None else rows, dtype=_np.int32)).ravel()
+        self._check(_ffi.lib().bbo_amalgam_inject_draws(
+            self._handle, z.ctypes.data_as(C.c_void_p), z.size, r.ctypes.data_as(C.c_void_p), r.size))
+
+
 class SpiralSearch(MultivariateSearch):
     """SpiralSearch(mfev, tol, np=20, r=0.95, theta=1.57079632679, taur=0.0, tautheta=0.1, rlow=0.9,
     rhigh=1.0, thetalow=0.0, thetahigh=6.28318530718) -- :344-351 (adaptive spiral optimization,

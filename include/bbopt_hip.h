@@ -60,7 +60,8 @@ typedef enum {
     BBO_ALGO_SPIRAL = 15,      /* SpiralSearch src/multivariate/spiral/spiral.h:39    */
     BBO_ALGO_NSHS = 16,        /* NSHS         src/multivariate/harmony/nshs.h        */
     BBO_ALGO_LM_CMAES = 17,    /* LmCmaes      src/multivariate/cma/lm_cmaes.h:43     */
-    BBO_ALGO_XNES = 18         /* xNES         src/multivariate/nes/xnes.h:48         */
+    BBO_ALGO_XNES = 18,        /* xNES         src/multivariate/nes/xnes.h:48         */
+    BBO_ALGO_AMALGAM = 19      /* Amalgam      src/multivariate/amalgam/amalgam.h     */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -487,6 +488,43 @@ void bbo_xnes_params_default(bbo_xnes_params *p);   /* 1., 1., 0 */
 int bbo_xnes_configure(bbo_handle h, const bbo_xnes_params *p);
 int bbo_xnes_phase(bbo_handle h, int phase);
 int bbo_xnes_inject_normals(bbo_handle h, const double *z, int count);
+
+/* ---- AMALGAM (BBO_ALGO_AMALGAM): AMALGAM(mfev,tol,stol,np=0,iamalgam=True,noparam=True,print=True), the
+ * AMaLGaM-IDEA and iAMaLGaM-IDEA of Bosman, Grahl & Thierens 2009 (amalgam.cpp).  mfev, tol, stol and np
+ * travel in bbo_params (np <= 0: int(10 sqrt n) for iAMaLGaM, int(17 + 3 n^1.5) for AMaLGaM); the rest
+ * travels here.  The population starts uniform in the box: a finite box is mandatory, `guess` is not
+ * read.  keep_elite = 1 (an extension) leaves the x of row 0 alone in the sampler; the default, as the
+ * reference, resamples it and keeps its old value.  substream (an extension): the sub-stream of
+ * population 0; population p draws from substream + p.
+ * noparam = 1, the parameter-free mode: bbo_iterate is one stage, runs = 2^(s/2) copies of size
+ * (1 + s/2) nbase (s even) or one copy of size 2^(1 + s/2) nbase (s odd), each a complete inner run
+ * whose budget is what the copies before it left, plus one evaluation of its result.  populations must
+ * be 1.  concurrent = 1 runs the copies of a stage as the populations of one inner handle, copy r on
+ * sub-stream (s << 16) + r, and charges the budget afterwards in the sequential order, replaying a
+ * copy that ran beyond its cap alone; concurrent = 0 runs them one after another: the same results.
+ * print = 1 writes the reference's table to stdout.  Keys of this mode: "stages" (rows of s, runs,
+ * pop, f*, best f*, fev), "fbest", "xbest", "s", "budget", "fev", "nbase"; phase and inject are
+ * BBO_ERR_STATE.
+ * bbo_amalgam_configure is legal between bbo_create and bbo_init.  Limits: n in [1, 512], np in
+ * [3, 65536]; objective programs, np < 3 and a non-finite box are refused by bbo_init (BBO_ERR_ARG).
+ * bbo_amalgam_phase: 0 distribution (mean, covariance, factor), 1 sample + evaluate, 2 adapt + stop
+ * (and the ranking of the new values); the three in order are bbo_iterate.
+ * bbo_amalgam_inject_draws: the normals of the following G generations, zcount = G * populations * np
+ * * n doubles as [G][populations][np][n] in sampling order (row m is the reference's sorted row m),
+ * and the rows that take the anticipated mean shift, rcount = G * populations * nams ints as
+ * [G][populations][nams], each in 1 .. np - 1.  Sampling beyond them is BBO_ERR_STATE; z = NULL returns
+ * to the device generator.  bbo_amalgam_inject_points: the initial points of the next bbo_init,
+ * populations * np * n doubles, before bbo_init.
+ * "stop": 1 cmult < 1e-10 or the variance of the np stored values <= stol^2, 2 fev >= mfev; fev counts
+ * np per generation as the reference does, though np - 1 points are evaluated.  "route": the slabs
+ * of the Gram's K dimension and whether the factorisation ran in LDS.  "fact_fail": factorisations
+ * that ended at a non-positive pivot, left unrepaired as in the reference; "fail_at": its step. */
+typedef struct { int iamalgam, noparam, print, keep_elite, concurrent, substream; } bbo_amalgam_params;
+void bbo_amalgam_params_default(bbo_amalgam_params *p);   /* 1, 1, 1, 0, 1, 0 */
+int bbo_amalgam_configure(bbo_handle h, const bbo_amalgam_params *p);
+int bbo_amalgam_phase(bbo_handle h, int phase);
+int bbo_amalgam_inject_draws(bbo_handle h, const double *z, int zcount, const int *rows, int rcount);
+int bbo_amalgam_inject_points(bbo_handle h, const double *x, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);

@@ -2,7 +2,8 @@
 # Run on the GPU box (through gpurun): one bench.py line per workload into gpurun_out/<tag>_<WL>.json
 # usage: scripts/run_all_benches.sh <tag> [workloads...]
 # (the engines outside bench.py have their own scripts, one JSON line per measurement:
-#  bench_spiral.py, bench_hees.py, bench_nshs.py, bench_lm.py, bench_xnes.py, bench_program_objective.py)
+#  bench_spiral.py, bench_hees.py, bench_nshs.py, bench_lm.py, bench_xnes.py, bench_amalgam.py,
+#  bench_program_objective.py)
 TAG=$1; shift
 WLS=${@:-"M C1 C3 C2 JADE SANSDE SEP CSO CCPSO C4 C5"}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}

@@ -1,0 +1,390 @@
+"""GPU: the AMALGAM kernels against the device form of tests/amalgam_model.py under the device's own
+draws, and the contract of the class.
+
+The device's initial points, normals and shifted rows are read back (get_state "arx" after
+initialize, "arz" and "shifted" after a generation) and fed to the model.  Integer keys are equal;
+floats are relative to the key's largest entry under the bound rule of tests/test_amalgam_model.py
+(the next power of ten at least 100 times the largest deviation measured, capped at 1e-9).
+
+Measured on an MI355X over the six shapes: 2.2e-15 at most (n = 33, fbest), so BOUND = 1e-12.
+
+The outcome distribution: 32 seeds of the model driven by NumPy draws (iAMaLGaM, Rosenbrock n = 10 in
+[-5, 5], stol = 1e-8) give 28 runs below f = 1e-6 and 4 in the local minimum f = 3.99, median 12183
+counted evaluations, inside the 9765 ... 15345 of the recorded reference's 15 successes of 16."""
+import base64
+import ctypes as C
+import io
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import _tabular
+import amalgam_model as am
+import xnes_model as xm
+from _golden import load
+
+pytestmark = pytest.mark.gpu
+
+GOLD = load("amalgam_runs.json")
+BOUND = 1e-12
+FLOAT_KEYS = ("arx", "fit_val", "mu", "mushift", "cov", "chol", "cmult", "sdr", "fbest", "xbest")
+INT_KEYS = ("fit_idx", "t", "it", "fev", "nis", "stop", "fact_fail")
+ALL_KEYS = FLOAT_KEYS + INT_KEYS + ("arz", "shifted")
+WIDTHS = [5, 5, 10, 25, 25, 10]
+
+
+def unpack(s):
+    return np.frombuffer(base64.b64decode(s), dtype="<f8").astype(np.float64)
+
+
+def _bits(a, b, what):
+    a, b = np.asarray(a, float).ravel(), np.asarray(b, float).ravel()
+    assert a.shape == b.shape, what
+    assert a.tobytes() == b.tobytes(), (what, np.flatnonzero(a != b)[:8], a[a != b][:4], b[a != b][:4])
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, float).ravel(), np.asarray(b, float).ravel()
+    assert a.shape == b.shape
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+def _snapshot(g, p=0, keys=ALL_KEYS):
+    return {k: g.get_state(k, p).copy() for k in keys}
+
+
+def _model_state(m):
+    return {"arx": m.X, "fit_val": m.fit, "mu": m.mu, "mushift": m.mushift, "cov": m.cov, "chol": m.chol,
+            "cmult": [m.cmult], "sdr": [m.sdr], "fbest": [m.fbest], "xbest": m.xbest, "fit_idx": m.order, "t": [m.t],
+            "it": [m.t], "fev": [m.fev], "nis": [m.nis], "stop": [m.stop()], "fact_fail": [m.fact_fail]}
+
+
+def _generation(g, gen):
+    """the generations alternate between iterate(), run(1) and the three phases"""
+    if gen % 3 == 1:
+        g.iterate()
+    elif gen % 3 == 2:
+        assert g.run(1) == 1
+    else:
+        for ph in range(3):
+            g.phase(ph)
+
+
+def _inner(hip, mfev=10 ** 9, stol=0., np_=0, iam=True, **kw):
+    return hip.AMALGAM(mfev, 0., stol, np_, iam, False, False, **kw)
+
+
+def _box(n):
+    return -5. * np.ones(n), 5. * np.ones(n), np.zeros(n)
+
+
+# n = 5 and 17 AMaLGaM, 33 iAMaLGaM; n = 130 with np = 114: the factorisation through the global image;
+# n = 5 with np = 800: ss = 280, two slabs of the Gram
+@pytest.mark.parametrize("n,iam,np_,gens", [(5, True, 0, 6), (5, False, 0, 6), (17, False, 0, 4), (33, True, 0, 6),
+                                            (130, True, 114, 3), (5, False, 800, 3)])
+def test_generations_against_the_device_form_of_the_model(hip, n, iam, np_, gens):
+    P = 2
+    obj = ["rosenbrock", "ellipsoid"][n % 2] if n != 5 else "rosenbrock"
+    lo, up, guess = _box(n)
+    g = _inner(hip, np_=np_, iam=iam, seed=50 + n, populations=P)
+    g.initialize(obj, lo, up, np.zeros(P * n))
+    frows = xm.device_objective(obj, n)
+    f = lambda x: float(frows(x)[0])
+    npop = int(g.get_state("np")[0])
+    assert npop == (np_ or am.default_np(n, iam))
+    route = g.get_state("route").astype(int).tolist()
+    assert route == [(int(0.35 * npop) + am.SLAB - 1) // am.SLAB, 1 if n <= 128 else 0]
+    if np_ == 800:
+        assert route[0] == 2
+    if n == 130:
+        assert route[1] == 0
+    models = []
+    for p in range(P):
+        m = am.Amalgam(f, n, 10 ** 9, 0., npop, iam, form="device")
+        m.init(g.get_state("arx", p))
+        models.append(m)
+        assert _rel(g.get_state("fit_val", p), m.fit) <= BOUND and _rel(g.get_state("mu", p), m.mu) <= BOUND
+        assert _rel(g.get_state("cov", p), m.cov) <= BOUND
+        assert g.get_state("fit_idx", p).astype(int).tolist() == list(m.order)
+    assert not np.array_equal(g.get_state("arx", 0), g.get_state("arx", 1))
+    x0 = g.get_state("arx", 0)
+    assert x0.min() >= -5. and x0.max() <= 5. and np.unique(x0).size == x0.size and abs(x0.mean()) < 1.
+    worst = (-1., "")
+    for gen in range(1, gens + 1):
+        _generation(g, gen)
+        for p in range(P):
+            have = _snapshot(g, p)
+            sh = np.flatnonzero(have["shifted"])
+            assert sh.size == models[p].nams and (sh.size == 0 or sh.min() >= 1)
+            models[p].iterate(have["arz"], sh)
+            want = _model_state(models[p])
+            for k in INT_KEYS:
+                assert have[k].astype(int).tolist() == [int(v) for v in want[k]], (k, gen, p)
+            for k in FLOAT_KEYS:
+                err = _rel(have[k], want[k])
+                worst = max(worst, (err, "%s generation %d population %d" % (k, gen, p)))
+                assert err <= BOUND, (k, gen, p, err)
+    z = g.get_state("arz", 0)
+    assert abs(z.mean()) < 0.6 and 0.5 < z.std() < 1.5
+    print("n = %d, np = %d: worst relative deviation from the model over %d generations %.3e (%s)"
+          % ((n, npop, gens) + worst))
+
+
+def test_iterate_run_and_phases_give_the_same_bits_and_a_seed_repeats(hip):
+    n, P = 20, 2
+    lo, up, guess = _box(n)
+    hs = [_inner(hip, seed=s, populations=P) for s in (7, 7, 7, 7, 8)]
+    for h in hs:
+        h.initialize("ellipsoid", lo, up, np.zeros(P * n))
+    for _ in range(6):
+        hs[0].iterate()
+        for ph in range(3):
+            hs[2].phase(ph)
+    assert hs[1].run(6) == 6 and hs[3].run(6) == 6 and hs[4].run(6) == 6
+    for p in range(P):
+        ref = _snapshot(hs[0], p)
+        for h, what in ((hs[1], "run"), (hs[2], "phases"), (hs[3], "the same seed again")):
+            s = _snapshot(h, p)
+            for k in ref:
+                _bits(ref[k], s[k], "%s: %s" % (what, k))
+    assert not np.array_equal(hs[0].get_state("arz", 0), hs[4].get_state("arz", 0))
+
+
+def test_population_p_is_a_single_handle_on_sub_stream_p(hip):
+    n, P = 12, 5
+    lo, up, guess = _box(n)
+    many = _inner(hip, seed=11, populations=P)
+    many.initialize("rosenbrock", lo, up, np.zeros(P * n))
+    assert many.run(7) == 7
+    for p in range(P):
+        one = _inner(hip, seed=11, substream=p)
+        one.initialize("rosenbrock", lo, up, guess)
+        assert one.run(7) == 7
+        a, b = _snapshot(many, p), _snapshot(one, 0)
+        for k in a:
+            _bits(a[k], b[k], "population %d: %s" % (p, k))
+        _bits(many.solution(p).x, one.solution().x, "solution")
+
+
+def test_each_stop_flag(hip):
+    n = 6
+    lo, up, guess = _box(n)
+    # the multiplier
+    g = _inner(hip, seed=1)
+    g.initialize("sphere", lo, up, guess)
+    g.iterate()
+    assert int(g.get_state("stop")[0]) == 0 and not g.solution().converged
+    # the multiplier shrinks only in a generation without improvement once nis has reached nismax (:223-231):
+    # values no row improves on, nis at its ceiling, the multiplier just above the threshold
+    f = g.get_state("fit_val")
+    f[0] = f.min() - 1.
+    g.set_state("fit_val", f)
+    g.set_state("nis", [float(g.get_state("nismax")[0])])
+    g.set_state("cmult", [1.05e-10])
+    g.phase(2)
+    assert int(g.get_state("stop")[0]) == 1 and float(g.get_state("cmult")[0]) == 1.05e-10 * 0.9
+    assert g.solution().converged
+    assert g.run(5) == 0
+    # flat values
+    g = _inner(hip, stol=1e-8, seed=2)
+    g.initialize("sphere", lo, up, guess)
+    g.iterate()
+    assert int(g.get_state("stop")[0]) == 0
+    g.set_state("fit_val", np.full(int(g.get_state("np")[0]), 3.25))
+    g.phase(2)
+    assert int(g.get_state("stop")[0]) == 1 and int(g.get_state("conv")[0]) == 1
+    # the budget: np is counted per generation, the run ends with the first count at or above mfev
+    g = _inner(hip, mfev=100, seed=3)
+    g.initialize("rosenbrock", lo, up, guess)
+    np_ = int(g.get_state("np")[0])
+    g.run(1000)
+    gens = int(g.get_state("t")[0])
+    assert gens == -(-100 // np_) - 1 and int(g.get_state("fev")[0]) == np_ * (gens + 1) >= 100
+    assert int(g.get_state("stop")[0]) == 2 and g.solution().converged and g.solution().n_evals == np_ * (gens + 1)
+    # optimize() iterates before it tests: mfev <= np still takes one generation
+    g = _inner(hip, mfev=5, seed=3)
+    sol = g.optimize("rosenbrock", lo, up, guess)
+    assert sol.n_evals == 2 * np_ and int(g.get_state("t")[0]) == 1 and int(g.get_state("stop")[0]) == 2
+
+
+@pytest.mark.parametrize("k", range(len(GOLD["pivot"])))
+def test_crafted_pivot_failure_equals_the_model_and_is_counted(hip, k):
+    """measured: the device's partial factor equals the recorded reference's bit for bit"""
+    rec = GOLD["pivot"][k]
+    n = rec["n"]
+    cov = am.crafted(n, rec["rank"], rec["drop"])
+    lo, up, guess = _box(n)
+    g = _inner(hip, iam=False, seed=4)
+    g.initialize("rosenbrock", lo, up, guess)
+    g.set_state("etasigma", [0.])
+    g.set_state("cov", cov)
+    g.phase(0)
+    _bits(g.get_state("cov"), cov, "etasigma = 0 keeps the crafted matrix")
+    chol, fail = am.factor(cov, 1.)
+    assert fail == rec["fail_at"] and int(g.get_state("fail_at")[0]) == fail and int(g.get_state("fact_fail")[0]) == 1
+    have = g.get_state("chol").reshape(n, n)
+    assert _rel(have, chol) <= BOUND and _rel(have, unpack(rec["chol"])) <= BOUND
+    assert np.all(np.triu(have, 1) == 0.) and have[fail, fail] < 0.
+    g.phase(0)
+    assert int(g.get_state("fact_fail")[0]) == 2      # sticky: a count, never reset
+
+
+def test_the_elite_row(hip):
+    n = 8
+    lo, up, guess = _box(n)
+    for keep in (False, True):
+        g = _inner(hip, seed=6, keep_elite=keep)
+        g.initialize("rosenbrock", lo, up, guess)
+        for _ in range(3):
+            f, x = g.get_state("fit_val"), g.get_state("arx").reshape(-1, n)
+            best = int(g.get_state("fit_idx")[0])
+            g.iterate()
+            f1, x1 = g.get_state("fit_val"), g.get_state("arx").reshape(-1, n)
+            assert f1[0] == f[best]                         # the old value either way
+            assert np.array_equal(x1[0], x[best]) == keep   # the old x only with keep_elite
+            _bits(g.solution().x, x1[0], "solution() is row 0")
+            assert float(g.get_state("fbest")[0]) <= f1.min()
+
+
+def test_a_callable_in_the_builtins_order_gives_the_builtins_run(hip):
+    n, gens = 9, 6
+    lo, up, guess = _box(n)
+    frows = xm.device_objective("sphere", n)
+    calls = []
+
+    def host(x):
+        calls.append(1)
+        return float(frows(np.asarray(x, float))[0])
+
+    a, b = _inner(hip, seed=5), _inner(hip, seed=5)
+    a.initialize("sphere", lo, up, guess)
+    b.initialize(host, lo, up, guess)
+    np_ = int(a.get_state("np")[0])
+    assert len(calls) == np_
+    assert a.run(gens) == gens and b.run(gens) == gens
+    assert len(calls) == np_ + gens * (np_ - 1)
+    assert b.solution().n_evals == np_ * (gens + 1) == a.solution().n_evals
+    sa, sb = _snapshot(a), _snapshot(b)
+    for k in sa:
+        _bits(sa[k], sb[k], k)
+
+
+def test_limits_and_refusals(hip):
+    n = 4
+    lo, up, guess = _box(n)
+    with pytest.raises(Exception, match="np must be at least 3"):
+        _inner(hip, np_=2).initialize("sphere", lo, up, guess)
+    with pytest.raises(Exception, match="finite"):
+        _inner(hip).initialize("sphere", lo, np.array([5., 5., np.inf, 5.]), guess)
+    with pytest.raises(Exception, match="finite"):
+        hip.AMALGAM(1000, 1e-8, 1e-8, print=False).initialize("sphere", -np.inf * np.ones(n), up, guess)
+    with pytest.raises(Exception, match="dimension"):
+        _inner(hip).initialize("sphere", *_box(513))
+    # an objective program: refused by the class and by the library, naming who takes one
+    from bboptpy_amd import _ffi
+    L = _ffi.lib()
+    prog = hip.DeviceObjective('extern "C" __device__ double bbo_user_objective(const double *x, int n, '
+                               'const double *data) { return x[0] * x[0]; }')
+    g = _inner(hip)
+    with pytest.raises(ValueError, match="AMALGAM does not take a DeviceObjective"):
+        g.initialize(prog, lo, up, guess)
+    ob = _ffi.Objective()
+    ob.kind, ob.user = _ffi.OBJ_PROGRAM, prog._handle
+    h = g._ensure_handle()
+    st = L.bbo_init(h, n, lo, up, guess, C.byref(ob))
+    msg = L.bbo_last_error(h).decode()
+    assert st == -1 and "AMALGAM" in msg and "CMAES" in msg, (st, msg)
+    g.initialize("sphere", lo, up, guess)
+    with pytest.raises(Exception, match="phase"):
+        g.phase(3)
+    with pytest.raises(Exception, match="shifted rows"):
+        g.inject_draws(np.zeros((1, 1, int(g.get_state("np")[0]), n)), [0] * int(g.get_state("nams")[0]))
+    d = hip.AMALGAM(1000, 1e-8, 1e-8, print=False)
+    d.initialize("sphere", lo, up, guess)
+    with pytest.raises(Exception, match="parameter-free"):
+        d.phase(0)
+
+
+def _capture(fn):
+    """what the library writes to the process's stdout while fn runs"""
+    sys.stdout.flush()
+    r, w = os.pipe()
+    saved = os.dup(1)
+    os.dup2(w, 1)
+    try:
+        out = fn()
+    finally:
+        os.dup2(saved, 1)
+        os.close(w)
+        os.close(saved)
+    with io.open(r, "r") as fh:
+        return out, fh.read()
+
+
+def _stages(g):
+    return g.get_state("stages").reshape(-1, 6)
+
+
+# the second case's budget binds inside the two copies of stage 2
+@pytest.mark.parametrize("n,mfev,tol", [(4, 400000, 1e-6), (5, 9000, 0.)])
+def test_parameter_free_driver_concurrent_and_sequential_agree(hip, n, mfev, tol):
+    lo, up, guess = _box(n)
+    out = []
+    for conc in (True, False):
+        g = hip.AMALGAM(mfev, tol, 1e-8, print=False, concurrent=conc, seed=21)
+        sol = g.optimize("rosenbrock", lo, up, guess)
+        out.append((sol, _stages(g), g))
+    (sa, ta, ga), (sb, tb, _) = out
+    _bits(sa.x, sb.x, "solution")
+    assert sa.n_evals == sb.n_evals and sa.converged == sb.converged is True
+    _bits(ta, tb, "stage rows")
+    nbase = am.default_np(n, True)
+    for row in ta:
+        assert (int(row[2]), int(row[1])) == am.stage_shape(int(row[0]), nbase)
+    assert ta[:, 0].astype(int).tolist() == list(range(len(ta))) and len(ta) >= 2
+    assert np.all(np.diff(ta[:, 4]) <= 0.) and np.all(ta[:, 4] <= ta[:, 3]) and int(ta[-1, 5]) == sa.n_evals
+    assert float(ga.get_state("fbest")[0]) == ta[-1, 4]
+    _bits(ga.get_state("xbest"), sa.x, "xbest")
+    if tol == 0.:
+        # the stage that exhausts the budget has two copies, and it overdraws as the reference does
+        assert int(ta[-1, 1]) == 2 and sa.n_evals >= mfev and int(ta[-2, 5]) < mfev
+    else:
+        assert sa.n_evals < mfev and 0. < abs(ta[-1, 3] - ta[-2, 3]) <= tol
+
+
+def test_the_printed_rows_are_the_reference_format(hip):
+    n = 3
+    lo, up, guess = _box(n)
+    g = hip.AMALGAM(4000, 0., 1e-8, seed=5)
+    _, text = _capture(lambda: g.optimize("rosenbrock", lo, up, guess))
+    lines = text.splitlines()
+    rows = _stages(g)
+    want = [_tabular.fmt_row(["iter", "runs", "pop", "f*", "best f*", "fev"], WIDTHS), _tabular.rule(WIDTHS)]
+    for r in rows:
+        want.append(_tabular.fmt_row([int(r[0]), int(r[1]), int(r[2]), float(r[3]), float(r[4]), int(r[5])], WIDTHS))
+    assert lines == want
+    assert lines[:2] == GOLD["noparam"][0]["table"][:2]
+
+
+def test_outcome_distribution_of_the_rosenbrock_runs(hip):
+    """measured on an MI355X: see the module's docstring"""
+    runs = GOLD["runs"]
+    n, P = runs["n"], 32
+    ok = sorted(r["fev"] for r in runs["converging"] if float.fromhex(r["f"]) < 1e-6)
+    assert len(ok) == 15 and len(runs["converging"]) == 16
+    lo, up, guess = _box(n)
+    g = _inner(hip, mfev=runs["mfev"], stol=runs["stol"], seed=2024, populations=P, poll_every=32)
+    g.initialize("rosenbrock", lo, up, np.zeros(P * n))
+    g.run(10 ** 6)
+    frows = xm.device_objective("rosenbrock", n)
+    sols = [g.solution(p) for p in range(P)]
+    assert all(s.converged for s in sols) and all(int(g.get_state("stop", p)[0]) == 1 for p in range(P))
+    good = sorted(s.n_evals for s in sols if float(frows(s.x)[0]) < 1e-6)
+    print("device: %d of %d runs below 1e-6, n_evals %d ... %d, median %.1f; the reference's successes %d ... %d"
+          % (len(good), P, good[0], good[-1], float(np.median(good)), ok[0], ok[-1]))
+    # the reference lands in the local minimum f = 3.99 once in 16 runs; with 1 of 16 observed the share
+    # is below 0.26 at 95 % confidence: at most 8 of 32 here
+    assert len(good) >= P - 8
+    assert ok[0] <= np.median(good) <= ok[-1]
