@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
-    ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM = range(20)
+    ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO = range(21)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -33,6 +33,8 @@ LM_PHASE_SAMPLE, LM_PHASE_EVALUATE, LM_PHASE_RANK, LM_PHASE_UPDATE, LM_PHASE_HIS
 XNES_PHASE_SAMPLE, XNES_PHASE_RANK, XNES_PHASE_STEP, XNES_PHASE_ADAPT = range(4)
 # bbo_amalgam_phase
 AMALGAM_PHASE_DISTRIBUTION, AMALGAM_PHASE_SAMPLE, AMALGAM_PHASE_ADAPT = range(3)
+# bbo_slpso_phase
+SLPSO_PHASE_ADVANCE, SLPSO_PHASE_EVALUATE, SLPSO_PHASE_ABSORB = range(3)
 # LmCMAES "flag": the CMA engines' codes and sigma < 1e-16
 LM_FLAG_MAXITER, LM_FLAG_TOLHISTFUN, LM_FLAG_EQUALFUNVALS, LM_FLAG_SIGMA = 1, 2, 3, 11
 
@@ -105,6 +107,11 @@ class AmalgamParams(C.Structure):
     """bbo_amalgam_params: AMALGAM's constructor arguments that bbo_params has no field for"""
     _fields_ = [(k, C.c_int) for k in ("iamalgam", "noparam", "print", "keep_elite", "concurrent",
                                        "substream")]
+
+
+class SlpsoParams(C.Structure):
+    """bbo_slpso_params: SLPSO's constructor arguments that bbo_params has no field for"""
+    _fields_ = [(k, C.c_double) for k in ("omegamin", "omegamax", "eta", "gamma", "vmax", "Ufmax")]
 
 
 class Objective(C.Structure):
@@ -198,6 +205,11 @@ def lib():
     L.bbo_amalgam_phase.argtypes = [C.c_void_p, C.c_int]
     L.bbo_amalgam_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.bbo_amalgam_inject_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.bbo_slpso_params_default.argtypes = [C.POINTER(SlpsoParams)]
+    L.bbo_slpso_params_default.restype = None
+    L.bbo_slpso_configure.argtypes = [C.c_void_p, C.POINTER(SlpsoParams)]
+    L.bbo_slpso_phase.argtypes = [C.c_void_p, C.c_int]
+    L.bbo_slpso_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -214,7 +226,8 @@ def lib():
                  "bbo_nshs_inject_uniforms", "bbo_lm_configure", "bbo_lm_phase", "bbo_lm_inject_draws",
                  "bbo_xnes_configure", "bbo_xnes_phase", "bbo_xnes_inject_normals",
                  "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
-                 "bbo_amalgam_inject_points"):
+                 "bbo_amalgam_inject_points", "bbo_slpso_configure", "bbo_slpso_phase",
+                 "bbo_slpso_inject_draws"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -237,6 +250,7 @@ EXPORTED_SYMBOLS = (
     "bbo_xnes_params_default", "bbo_xnes_configure", "bbo_xnes_phase", "bbo_xnes_inject_normals",
     "bbo_amalgam_params_default", "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
     "bbo_amalgam_inject_points",
+    "bbo_slpso_params_default", "bbo_slpso_configure", "bbo_slpso_phase", "bbo_slpso_inject_draws",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

@@ -11,6 +11,7 @@
 #include "bbo_lm.hpp"
 #include "bbo_xnes.hpp"
 #include "bbo_amalgam.hpp"
+#include "bbo_slpso.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -30,6 +31,7 @@ Optimizer* make_nshs_engine(const bbo_params &p);     // bbo_nshs.hip
 Optimizer* make_lm_engine(const bbo_params &p);       // bbo_lm.hip
 Optimizer* make_xnes_engine(const bbo_params &p);     // bbo_xnes.hip
 Optimizer* make_amalgam_engine(const bbo_params &p);  // bbo_amalgam.hip
+Optimizer* make_slpso_engine(const bbo_params &p);    // bbo_slpso.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -99,14 +101,15 @@ bbo::ObjectiveSpec to_spec(const bbo_objective *o)
 
 // bbo_params as a caller built against an earlier header knows it ends where `stol` begins.  Such a
 // caller can only name the algorithms of its header, so the fields appended for CholeskyCMAES are
-// read and written for BBO_ALGO_CHOLESKY_CMAES, BBO_ALGO_DSA and BBO_ALGO_AMALGAM (whose `stol` travels
-// there: a caller that can name algorithm 13 or 19 has the long struct) alone: nothing here touches memory past
+// read and written for BBO_ALGO_CHOLESKY_CMAES, BBO_ALGO_DSA, BBO_ALGO_AMALGAM and BBO_ALGO_SLPSO (whose `stol` travels
+// there: a caller that can name algorithm 13, 19 or 20 has the long struct) alone: nothing here touches memory past
 // the struct the caller allocated.
 constexpr size_t PARAMS_BASE_BYTES = offsetof(bbo_params, stol);
 
 inline bool has_long_params(int algo)
 {
-    return algo == BBO_ALGO_CHOLESKY_CMAES || algo == BBO_ALGO_DSA || algo == BBO_ALGO_AMALGAM;
+    return algo == BBO_ALGO_CHOLESKY_CMAES || algo == BBO_ALGO_DSA || algo == BBO_ALGO_AMALGAM
+            || algo == BBO_ALGO_SLPSO;
 }
 
 bbo_params own_copy(const bbo_params *params)
@@ -245,6 +248,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_AMALGAM:
             h->opt.reset(bbo::make_amalgam_engine(*params));
+            break;
+        case BBO_ALGO_SLPSO:
+            h->opt.reset(bbo::make_slpso_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -775,6 +781,45 @@ int bbo_amalgam_inject_draws(bbo_handle h, const double *z, int zcount, const in
 int bbo_amalgam_inject_points(bbo_handle h, const double *x, int count)
 {
     return guarded(h, [&] { as_amalgam(h)->inject_points(x, count); });
+}
+
+void bbo_slpso_params_default(bbo_slpso_params *p)
+{
+    if (!p) return;
+    // py/multivariate_py.cpp:292-299
+    p->omegamin = 0.4;
+    p->omegamax = 0.9;
+    p->eta = 1.496;
+    p->gamma = 0.01;
+    p->vmax = 0.2;
+    p->Ufmax = 10.;
+}
+
+namespace {
+bbo::SlpsoEngine* as_slpso(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::SlpsoEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an SLPSO handle");
+    return e;
+}
+}
+
+int bbo_slpso_configure(bbo_handle h, const bbo_slpso_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_slpso_configure: NULL parameters");
+        as_slpso(h)->configure(*p);
+    });
+}
+
+int bbo_slpso_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_slpso(h)->phase(phase); });
+}
+
+int bbo_slpso_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { as_slpso(h)->inject_draws(table, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

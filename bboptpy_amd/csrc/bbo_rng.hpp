@@ -42,7 +42,11 @@ enum Stream : uint32_t {
     STREAM_XNES_NORMAL = 23,
     STREAM_AMALGAM_NORMAL = 24,
     STREAM_AMALGAM_SHIFT = 25,
-    STREAM_AMALGAM_INIT = 26
+    STREAM_AMALGAM_INIT = 26,
+    STREAM_SLPSO_CTRL = 27,
+    STREAM_SLPSO_R = 28,
+    STREAM_SLPSO_PERM = 29,
+    STREAM_SLPSO_INIT = 30
 };
 
 struct u32x4 {

@@ -1041,6 +1041,79 @@ class NSHS(MultivariateSearch):
             self._handle, u.ctypes.data_as(C.c_void_p), u.size))
 
 
+class SLPSO(MultivariateSearch):
+    """SLPSO(mfev, stol, np, omegamin=0.4, omegamax=0.9, eta=1.496, gamma=0.01, vmax=0.2, Ufmax=10.) --
+    :292-299 (self-learning particle swarm, Li, Yang & Nguyen 2012; slpso.cpp).  One iterate() walks the
+    swarm particle by particle, each improving move followed by the coordinate walk of Algorithm 2 over
+    the swarm's best point.  `guess` is ignored, as in the reference, and a finite box is mandatory.  The
+    budget is tested between generations: n_evals may pass mfev by up to one generation.
+    Extension `record_draws=True` keeps the draws of the last generation in the layout of
+    inject_draws (get_state("draws"))."""
+    _algo = _ffi.ALGO_SLPSO
+    _accepts_program = False
+    MAX_N, MAX_NP = 512, 4096
+
+    def __init__(self, mfev, stol, np, omegamin=0.4, omegamax=0.9, eta=1.496, gamma=0.01, vmax=0.2,
+                 Ufmax=10., **ext):
+        record_draws = ext.pop("record_draws", False)
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.stol, p.np = int(mfev), float(stol), int(np)
+        s = self._slpso = _ffi.SlpsoParams()
+        s.omegamin, s.omegamax, s.eta = float(omegamin), float(omegamax), float(eta)
+        s.gamma, s.vmax, s.Ufmax = float(gamma), float(vmax), float(Ufmax)
+        self._record_draws = bool(record_draws)
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 2 <= self._params.np <= self.MAX_NP:
+            raise ValueError("SLPSO: np must be in [2, %d]" % self.MAX_NP)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("SLPSO: dimension must be in [1, %d]" % self.MAX_N)
+        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
+            raise ValueError("SLPSO draws its swarm from [lower, upper]: the bounds must be finite")
+        return n, lower, upper, guess
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_slpso_configure(h, C.byref(self._slpso))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def initialize(self, f, lower, upper, guess):
+        super().initialize(f, lower, upper, guess)
+        if self._record_draws:
+            self.set_state("record_draws", [1.])
+
+    def table_len(self):
+        """doubles per population of the table of inject_draws and of get_state("draws")"""
+        np_ = self._params.np
+        return 1 + np_ + np_ * (3 + 4 * self._n)
+
+    def phase(self, which):
+        """the generation one evaluation at a time: 0 advance to the next pending point ("cand"), 1
+        evaluate it, 2 absorb the value.  Phase 0 returns the number of populations that have a point
+        pending: 0 when the generation is complete."""
+        self._check(_ffi.lib().bbo_slpso_phase(self._handle, int(which)))
+        if int(which) != 0:
+            return None
+        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+
+    def inject_draws(self, table):
+        """the draws of the following generations, [populations][1 + np + np (3 + 4 n)]: alpha, the
+        permutation after its shuffle, then per particle step the forcing coin, the roulette uniform, the
+        partner j as (j + 0.5) / np and per coordinate r, the normal of operator 1, the redraw of eq. 11
+        and the coin of Algorithm 2; None: the device draws"""
+        if table is None:
+            self._check(_ffi.lib().bbo_slpso_inject_draws(self._handle, None, 0))
+            return
+        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_slpso_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

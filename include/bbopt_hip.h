@@ -61,7 +61,8 @@ typedef enum {
     BBO_ALGO_NSHS = 16,        /* NSHS         src/multivariate/harmony/nshs.h        */
     BBO_ALGO_LM_CMAES = 17,    /* LmCmaes      src/multivariate/cma/lm_cmaes.h:43     */
     BBO_ALGO_XNES = 18,        /* xNES         src/multivariate/nes/xnes.h:48         */
-    BBO_ALGO_AMALGAM = 19      /* Amalgam      src/multivariate/amalgam/amalgam.h     */
+    BBO_ALGO_AMALGAM = 19,     /* Amalgam      src/multivariate/amalgam/amalgam.h     */
+    BBO_ALGO_SLPSO = 20        /* SLPSOSearch  src/multivariate/pso/slpso.h           */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -525,6 +526,36 @@ int bbo_amalgam_configure(bbo_handle h, const bbo_amalgam_params *p);
 int bbo_amalgam_phase(bbo_handle h, int phase);
 int bbo_amalgam_inject_draws(bbo_handle h, const double *z, int zcount, const int *rows, int rcount);
 int bbo_amalgam_inject_points(bbo_handle h, const double *x, int count);
+
+/* ---- SLPSO (BBO_ALGO_SLPSO): SLPSO(mfev,stol,np,omegamin=0.4,omegamax=0.9,eta=1.496,gamma=0.01,vmax=0.2,
+ * Ufmax=10.)  py/multivariate_py.cpp:292-299, the self-learning particle swarm of Li, Yang & Nguyen 2012
+ * (slpso.cpp).  mfev, stol and np travel in bbo_params; the rest travels here.  The swarm starts uniform in
+ * the box: a finite box is mandatory, `guess` is not read.  Limits: n in [1, 512], np in [2, 4096];
+ * objective programs, np < 2 and a non-finite box are refused (BBO_ERR_ARG).
+ * bbo_slpso_configure is legal between bbo_create and bbo_init.
+ * One bbo_iterate is one iterate() of the reference: every particle in swarm order, each with its move,
+ * its evaluation and, on an improvement, the coordinate walk of Algorithm 2 over abest; then updatePar.
+ * The budget is tested between generations only, so fev may pass mfev by up to one generation.
+ * bbo_slpso_phase walks the same generation one EVALUATION at a time: 0 advances every population to
+ * its next pending point ("cand": a moved particle or an Algorithm 2 trial; "pending" is 0 once the
+ * generation is complete and updatePar has run), 1 evaluates "cand" into "fcand", 2 absorbs the value.
+ * bbo_slpso_inject_draws: `populations` tables of 1 + np + np * (3 + 4 n) doubles that replace the
+ * generator from the next generation on: alpha, the permutation after its shuffle (np values), then per
+ * particle step the forcing coin, the roulette uniform and the partner j as (j + 0.5) / np, and per
+ * coordinate the uniform r, the normal of operator 1 (its value), the redraw of eq. 11 and the coin of
+ * Algorithm 2.  Uniforms are raw canonicals in [0, 1); a draw the generation does not use is padding.
+ * NULL returns to the device generator.  "record_draws" keeps the same table of the last generation
+ * ("draws").  "dbg" 1 forces the sequential form of Algorithm 2 where the speculative one would run
+ * ("speculative": which form runs; the two give the same bits).  "x" loads positions (re-evaluated;
+ * pbest, abest in index order and the learning state follow, velocities are zeroed), "perm" the
+ * permutation (Uf and Pl follow), "substream" (an extension) the sub-stream of population 0, from which
+ * the swarm is drawn again; population p draws from substream + p.
+ * "stop": 1 the spread of the particles' norms fell under stol, 2 fev >= mfev. */
+typedef struct { double omegamin, omegamax, eta, gamma, vmax, Ufmax; } bbo_slpso_params;
+void bbo_slpso_params_default(bbo_slpso_params *p);   /* 0.4, 0.9, 1.496, 0.01, 0.2, 10. */
+int bbo_slpso_configure(bbo_handle h, const bbo_slpso_params *p);
+int bbo_slpso_phase(bbo_handle h, int phase);
+int bbo_slpso_inject_draws(bbo_handle h, const double *table, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
