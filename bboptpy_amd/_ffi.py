@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 # bbo_algo
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
-    ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO = range(21)
+    ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
+    ALGO_CRS = range(22)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -35,6 +36,10 @@ XNES_PHASE_SAMPLE, XNES_PHASE_RANK, XNES_PHASE_STEP, XNES_PHASE_ADAPT = range(4)
 AMALGAM_PHASE_DISTRIBUTION, AMALGAM_PHASE_SAMPLE, AMALGAM_PHASE_ADAPT = range(3)
 # bbo_slpso_phase
 SLPSO_PHASE_ADVANCE, SLPSO_PHASE_EVALUATE, SLPSO_PHASE_ABSORB = range(3)
+# bbo_crs_phase
+CRS_PHASE_ADVANCE, CRS_PHASE_EVALUATE, CRS_PHASE_ABSORB = range(3)
+# CRS "flag": the tolerance, the budget, the depth cap
+CRS_FLAG_TOL, CRS_FLAG_BUDGET, CRS_FLAG_DEPTH = 1, 2, 3
 # LmCMAES "flag": the CMA engines' codes and sigma < 1e-16
 LM_FLAG_MAXITER, LM_FLAG_TOLHISTFUN, LM_FLAG_EQUALFUNVALS, LM_FLAG_SIGMA = 1, 2, 3, 11
 
@@ -112,6 +117,11 @@ class AmalgamParams(C.Structure):
 class SlpsoParams(C.Structure):
     """bbo_slpso_params: SLPSO's constructor arguments that bbo_params has no field for"""
     _fields_ = [(k, C.c_double) for k in ("omegamin", "omegamax", "eta", "gamma", "vmax", "Ufmax")]
+
+
+class CrsParams(C.Structure):
+    """bbo_crs_params: the extensions of CRS that bbo_params has no field for"""
+    _fields_ = [("max_depth", C.c_int), ("repair", C.c_int)]
 
 
 class Objective(C.Structure):
@@ -210,6 +220,11 @@ def lib():
     L.bbo_slpso_configure.argtypes = [C.c_void_p, C.POINTER(SlpsoParams)]
     L.bbo_slpso_phase.argtypes = [C.c_void_p, C.c_int]
     L.bbo_slpso_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.bbo_crs_params_default.argtypes = [C.POINTER(CrsParams)]
+    L.bbo_crs_params_default.restype = None
+    L.bbo_crs_configure.argtypes = [C.c_void_p, C.POINTER(CrsParams)]
+    L.bbo_crs_phase.argtypes = [C.c_void_p, C.c_int]
+    L.bbo_crs_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -227,7 +242,7 @@ def lib():
                  "bbo_xnes_configure", "bbo_xnes_phase", "bbo_xnes_inject_normals",
                  "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
                  "bbo_amalgam_inject_points", "bbo_slpso_configure", "bbo_slpso_phase",
-                 "bbo_slpso_inject_draws"):
+                 "bbo_slpso_inject_draws", "bbo_crs_configure", "bbo_crs_phase", "bbo_crs_inject_draws"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -251,6 +266,7 @@ EXPORTED_SYMBOLS = (
     "bbo_amalgam_params_default", "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
     "bbo_amalgam_inject_points",
     "bbo_slpso_params_default", "bbo_slpso_configure", "bbo_slpso_phase", "bbo_slpso_inject_draws",
+    "bbo_crs_params_default", "bbo_crs_configure", "bbo_crs_phase", "bbo_crs_inject_draws",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

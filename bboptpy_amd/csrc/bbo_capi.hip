@@ -12,6 +12,7 @@
 #include "bbo_xnes.hpp"
 #include "bbo_amalgam.hpp"
 #include "bbo_slpso.hpp"
+#include "bbo_crs.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -32,6 +33,7 @@ Optimizer* make_lm_engine(const bbo_params &p);       // bbo_lm.hip
 Optimizer* make_xnes_engine(const bbo_params &p);     // bbo_xnes.hip
 Optimizer* make_amalgam_engine(const bbo_params &p);  // bbo_amalgam.hip
 Optimizer* make_slpso_engine(const bbo_params &p);    // bbo_slpso.hip
+Optimizer* make_crs_engine(const bbo_params &p);      // bbo_crs.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -184,7 +186,7 @@ void bbo_params_default(bbo_params *p, int algo)
     p->npps = 0;
     p->pcauchy = -1.;
     if (algo == BBO_ALGO_SPIRAL) p->np = 20;   /* py/multivariate_py.cpp:348 */
-    if (algo == BBO_ALGO_NSHS) p->poll_every = 0;   /* the engine's own chunk: iterations, not generations */
+    if (algo == BBO_ALGO_NSHS || algo == BBO_ALGO_CRS) p->poll_every = 0;   /* the engine's own chunk: iterations, not generations */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -251,6 +253,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_SLPSO:
             h->opt.reset(bbo::make_slpso_engine(*params));
+            break;
+        case BBO_ALGO_CRS:
+            h->opt.reset(bbo::make_crs_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -820,6 +825,40 @@ int bbo_slpso_phase(bbo_handle h, int phase)
 int bbo_slpso_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { as_slpso(h)->inject_draws(table, count); });
+}
+
+void bbo_crs_params_default(bbo_crs_params *p)
+{
+    if (!p) return;
+    p->max_depth = 4096;
+    p->repair = 0;
+}
+
+namespace {
+bbo::CrsEngine* as_crs(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::CrsEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a CRS handle");
+    return e;
+}
+}
+
+int bbo_crs_configure(bbo_handle h, const bbo_crs_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_crs_configure: NULL parameters");
+        as_crs(h)->configure(*p);
+    });
+}
+
+int bbo_crs_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_crs(h)->phase(phase); });
+}
+
+int bbo_crs_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { as_crs(h)->inject_draws(table, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

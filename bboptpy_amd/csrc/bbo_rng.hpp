@@ -46,7 +46,10 @@ enum Stream : uint32_t {
     STREAM_SLPSO_CTRL = 27,
     STREAM_SLPSO_R = 28,
     STREAM_SLPSO_PERM = 29,
-    STREAM_SLPSO_INIT = 30
+    STREAM_SLPSO_INIT = 30,
+    STREAM_CRS_INIT = 31,
+    STREAM_CRS_IDX = 32,
+    STREAM_CRS_W = 33
 };
 
 struct u32x4 {

@@ -1114,6 +1114,77 @@ class SLPSO(MultivariateSearch):
         self._check(_ffi.lib().bbo_slpso_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
 
 
+class CRS(MultivariateSearch):
+    """CRS(mfev, np, tol) -- :339-342 (controlled random search with local mutation, Kaelo & Ali 2006;
+    crs.cpp).  Steady-state: an iteration replaces the worst of the np stored points, after as many
+    trials and evaluations as the reference's recursive trial() takes; run() advances chunks of whole
+    iterations (`poll_every`; default: the engine's own chunk) in launches of bounded length.  `guess` is
+    ignored, as in the reference, and a finite box is mandatory.  The budget is tested between
+    iterations: n_evals may pass mfev.  The default walks the reference's recursion, quirks included
+    (get_state("stale") counts the iterations whose replacement was no better than the worst point).
+    Extensions, keyword-only: `repair=True` is the loop of the paper (redraw instead of recursing, only
+    an accepted point replaces the worst); `max_depth` bounds the recursion (flag 3, where the reference
+    overflows its stack); `record_draws=True` keeps the draws of the last iteration in the layout of
+    inject_draws (get_state("draws"))."""
+    _algo = _ffi.ALGO_CRS
+    _accepts_program = False
+    MAX_N, MAX_NP = 512, 65536
+
+    def __init__(self, mfev, np, tol, **ext):
+        repair = ext.pop("repair", False)
+        max_depth = ext.pop("max_depth", 4096)
+        record_draws = ext.pop("record_draws", False)
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.np, p.tol = int(mfev), int(np), float(tol)
+        s = self._crs = _ffi.CrsParams()
+        s.max_depth, s.repair = int(max_depth), int(bool(repair))
+        self._record_draws = bool(record_draws)
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 2 <= self._params.np <= self.MAX_NP:
+            raise ValueError("CRS: np must be in [2, %d]" % self.MAX_NP)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("CRS: dimension must be in [1, %d]" % self.MAX_N)
+        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
+            raise ValueError("CRS draws its pool from [lower, upper]: the bounds must be finite")
+        return n, lower, upper, guess
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_crs_configure(h, C.byref(self._crs))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def initialize(self, f, lower, upper, guess):
+        super().initialize(f, lower, upper, guess)
+        if self._record_draws:
+            self.set_state("record_draws", [1.])
+
+    def phase(self, which):
+        """the iteration one evaluation at a time: 0 advance to the next pending point ("cand" in stage
+        1, "cand2" in stage 2), 1 evaluate it ("value"), 2 absorb the value and advance again.  Phases 0
+        and 2 return the number of populations that have a point pending: 0 when the iteration is
+        complete."""
+        self._check(_ffi.lib().bbo_crs_phase(self._handle, int(which)))
+        if int(which) == 1:
+            return None
+        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+
+    def inject_draws(self, table):
+        """the draws of the following trials, [populations][records][2 n]: per record the n row indices
+        of a trial (-1 where none is drawn) and the n uniforms of a mutation; None: the device draws"""
+        if table is None:
+            self._check(_ffi.lib().bbo_crs_inject_draws(self._handle, None, 0))
+            return
+        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_crs_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

@@ -62,7 +62,8 @@ typedef enum {
     BBO_ALGO_LM_CMAES = 17,    /* LmCmaes      src/multivariate/cma/lm_cmaes.h:43     */
     BBO_ALGO_XNES = 18,        /* xNES         src/multivariate/nes/xnes.h:48         */
     BBO_ALGO_AMALGAM = 19,     /* Amalgam      src/multivariate/amalgam/amalgam.h     */
-    BBO_ALGO_SLPSO = 20        /* SLPSOSearch  src/multivariate/pso/slpso.h           */
+    BBO_ALGO_SLPSO = 20,       /* SLPSOSearch  src/multivariate/pso/slpso.h           */
+    BBO_ALGO_CRS = 21          /* CrsSearch    src/multivariate/crs/crs.h             */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -556,6 +557,48 @@ void bbo_slpso_params_default(bbo_slpso_params *p);   /* 0.4, 0.9, 1.496, 0.01, 
 int bbo_slpso_configure(bbo_handle h, const bbo_slpso_params *p);
 int bbo_slpso_phase(bbo_handle h, int phase);
 int bbo_slpso_inject_draws(bbo_handle h, const double *table, int count);
+
+/* ---- CRS (BBO_ALGO_CRS): CRS(mfev,np,tol)  py/multivariate_py.cpp:339-342, the controlled random search
+ * with local mutation of Kaelo & Ali 2006 (crs.cpp).  mfev, np and tol travel in bbo_params, all three
+ * required; `max_depth` and `repair` (extensions) travel here.  The pool starts uniform in the box: a finite
+ * box is mandatory, `guess` is not read.  Limits: n in [1, 512], np in [2, 65536]; objective programs and
+ * a non-finite box are refused by bbo_init (BBO_ERR_ARG).  CRS is no base of a restart driver and is not
+ * sharded over devices.  bbo_crs_configure is legal between bbo_create and bbo_init.
+ * One bbo_iterate is one iterate() of the reference: trial(), whose recursion is walked as a state machine
+ * over a stack of bits, then update(), which replaces the worst point.  The walk is the reference's, its
+ * quirks included: a reflected point that left the box is redrawn and the point accepted in its place is
+ * evaluated and counted a second time; after a rejected mutation the inner call's result is overwritten
+ * with the mutation computed last, so the worst point may be replaced by one no better ("stale" counts
+ * these iterations).  The budget is tested between iterations only, so fev may pass mfev.
+ * repair = 1 is the loop of the paper instead: an out-of-box reflection and a rejected pair are redrawn,
+ * only an accepted point replaces the worst, the budget is also tested where a pair is rejected.
+ * The reference recurses until its stack overflows once every stored value is equal.  Here a push beyond
+ * max_depth frames (repair: max_depth out-of-box redraws in a row) ends the run with "flag" 3: the pool is
+ * as the last complete iteration left it, fev keeps what was spent.
+ * bbo_run advances `poll_every` iterations per population and chunk (0: 256) in launches that end, for a
+ * population, after "launch_evals" steps (drawn trials and evaluations; 0, the default: 8 per iteration of
+ * the chunk); a population cut there resumes in the next launch with the same bits.
+ * bbo_crs_phase walks the iteration one EVALUATION at a time: 0 advances every population to its next
+ * pending point ("pending"; "stage" 1: "cand", 2: "cand2"), 1 evaluates it into "value", 2 absorbs the
+ * value and advances again; "pending" is 0 once the iteration is complete.
+ * bbo_crs_inject_draws: populations * records * 2 n doubles that replace the generator: a record holds
+ * the n row indices of a trial (n - 1 for the centroid, then the reflected point; -1 where none is drawn)
+ * and n uniforms in [0, 1) for a mutation.  A trial takes the next record; a mutation takes the uniforms
+ * of the current record, or of the next one when they are spent or the table is new.  When the table runs
+ * out inside an iteration the call returns with "starved" 1 and the next table continues it (bbo_run
+ * returns BBO_ERR_STATE instead).  NULL returns to the device generator.  "record_draws" (1: 64 records,
+ * or their number) keeps the records of the last iteration in the same layout ("draws", "nrec").
+ * Keys: "x" / "f" the pool in RANK order (set: rows in place, re-evaluated / re-ranked, the walk starts
+ * over), "order" rank -> row, "rows" the pool in place, "cand" "fcand" "cand2" "fcand2" the trial, the
+ * mutation and their values, "fbest" "fworst" "fev" "it" "trials" "muts" "depth" "maxdepth" "stage"
+ * "pending" "stale" "flag" "conv", "max_depth" (settable up to the configured depth), "launch_evals".
+ * "flag": 1 |f_best - f_worst| < tol after an iteration, 2 fev >= mfev, 3 max_depth.  A NaN value counts
+ * as +inf. */
+typedef struct { int max_depth; int repair; } bbo_crs_params;
+void bbo_crs_params_default(bbo_crs_params *p);   /* 4096, 0 */
+int bbo_crs_configure(bbo_handle h, const bbo_crs_params *p);
+int bbo_crs_phase(bbo_handle h, int phase);
+int bbo_crs_inject_draws(bbo_handle h, const double *table, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
