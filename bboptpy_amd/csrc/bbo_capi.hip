@@ -13,6 +13,7 @@
 #include "bbo_amalgam.hpp"
 #include "bbo_slpso.hpp"
 #include "bbo_crs.hpp"
+#include "bbo_ssde.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -34,6 +35,7 @@ Optimizer* make_xnes_engine(const bbo_params &p);     // bbo_xnes.hip
 Optimizer* make_amalgam_engine(const bbo_params &p);  // bbo_amalgam.hip
 Optimizer* make_slpso_engine(const bbo_params &p);    // bbo_slpso.hip
 Optimizer* make_crs_engine(const bbo_params &p);      // bbo_crs.hip
+Optimizer* make_ssde_engine(const bbo_params &p);     // bbo_ssde.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -256,6 +258,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_CRS:
             h->opt.reset(bbo::make_crs_engine(*params));
+            break;
+        case BBO_ALGO_SSDE:
+            h->opt.reset(bbo::make_ssde_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -859,6 +864,45 @@ int bbo_crs_phase(bbo_handle h, int phase)
 int bbo_crs_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { as_crs(h)->inject_draws(table, count); });
+}
+
+void bbo_ssde_params_default(bbo_ssde_params *p)
+{
+    if (!p) return;
+    /* the Python binding's defaults (py/multivariate_py.cpp): its usede is false, the C++ header's true */
+    p->patience = 1000;
+    p->npmin = 4;
+    p->ptop = 0.11;
+    p->h = 100;
+    p->usede = 0;
+    p->repaircr = 1;
+}
+
+namespace {
+bbo::SsdeEngine* as_ssde(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::SsdeEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an SSDE handle");
+    return e;
+}
+}
+
+int bbo_ssde_configure(bbo_handle h, const bbo_ssde_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_ssde_configure: NULL parameters");
+        as_ssde(h)->configure(*p);
+    });
+}
+
+int bbo_ssde_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_ssde(h)->phase(phase); });
+}
+
+int bbo_ssde_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { as_ssde(h)->inject_draws(table, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

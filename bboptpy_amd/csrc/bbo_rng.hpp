@@ -49,7 +49,11 @@ enum Stream : uint32_t {
     STREAM_SLPSO_INIT = 30,
     STREAM_CRS_INIT = 31,
     STREAM_CRS_IDX = 32,
-    STREAM_CRS_W = 33
+    STREAM_CRS_W = 33,
+    STREAM_SSDE_INIT = 34,
+    STREAM_SSDE_CTRL = 35,
+    STREAM_SSDE_R = 36,
+    STREAM_SSDE_PERM = 37
 };
 
 struct u32x4 {

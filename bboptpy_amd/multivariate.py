@@ -1185,6 +1185,74 @@ class CRS(MultivariateSearch):
         self._check(_ffi.lib().bbo_crs_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
 
 
+class SSDE(MultivariateSearch):
+    """SSDE(mfev, npinit, tol, patience=1000, npmin=4, ptop=0.11, h=100, usede=False, repaircr=True)
+    (spherical search, Kumar et al. 2019, with the DE fallback of Zhao et al. 2022; ssde.cpp).  The pool is
+    updated in place, member after member, so a generation is one launch of one workgroup per population
+    that walks the reference's iterate(); the device earns its keep across `populations`.  `guess` is
+    ignored, as in the reference, and a finite box is mandatory.  The budget is tested between
+    generations: n_evals may pass mfev by up to one generation.  The pool never shrinks under 4 members
+    and ptop must lie in (0, 1).  `record_draws=True` (an extension) keeps the draws of the last
+    generation in the layout of inject_draws (get_state("draws"))."""
+    _algo = _ffi.ALGO_SSDE
+    _accepts_program = False
+    MAX_N, MIN_NP, MAX_NP = 512, 4, 4096
+
+    def __init__(self, mfev, npinit, tol, patience=1000, npmin=4, ptop=0.11, h=100, usede=False,
+                 repaircr=True, **ext):
+        record_draws = ext.pop("record_draws", False)
+        super().__init__(**ext)
+        p = self._params
+        p.mfev, p.np, p.tol = int(mfev), int(npinit), float(tol)
+        s = self._ssde = _ffi.SsdeParams()
+        s.patience, s.npmin, s.ptop, s.h = int(patience), int(npmin), float(ptop), int(h)
+        s.usede, s.repaircr = int(bool(usede)), int(bool(repaircr))
+        self._record_draws = bool(record_draws)
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not self.MIN_NP <= self._params.np <= self.MAX_NP:
+            raise ValueError("SSDE: npinit must be in [4, %d]" % self.MAX_NP)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("SSDE: dimension must be in [1, %d]" % self.MAX_N)
+        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
+            raise ValueError("SSDE draws its pool from [lower, upper]: the bounds must be finite")
+        return n, lower, upper, guess
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_ssde_configure(h, C.byref(self._ssde))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def initialize(self, f, lower, upper, guess):
+        super().initialize(f, lower, upper, guess)
+        if self._record_draws:
+            self.set_state("record_draws", [1.])
+
+    def phase(self, which):
+        """the generation one evaluation at a time: 0 advance to the next pending point ("cand"), 1
+        evaluate it ("fcand"), 2 absorb the value.  Phases 0 and 2 return the number of populations that
+        have a point pending: 0 when the generation is complete."""
+        self._check(_ffi.lib().bbo_ssde_phase(self._handle, int(which)))
+        if int(which) == 1:
+            return None
+        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+
+    def inject_draws(self, table):
+        """the draws of the following generations, [populations][n + npinit * (9 + 3 n)]: the permutation,
+        then per member iL, the normal of prank, p, q, r, pbest, ci, the normal of CRi, j0 and the n
+        uniforms each of b, the crossover and the redraw; None: the device draws"""
+        if table is None:
+            self._check(_ffi.lib().bbo_ssde_inject_draws(self._handle, None, 0))
+            return
+        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
+        self._check(_ffi.lib().bbo_ssde_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

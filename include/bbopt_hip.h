@@ -63,7 +63,8 @@ typedef enum {
     BBO_ALGO_XNES = 18,        /* xNES         src/multivariate/nes/xnes.h:48         */
     BBO_ALGO_AMALGAM = 19,     /* Amalgam      src/multivariate/amalgam/amalgam.h     */
     BBO_ALGO_SLPSO = 20,       /* SLPSOSearch  src/multivariate/pso/slpso.h           */
-    BBO_ALGO_CRS = 21          /* CrsSearch    src/multivariate/crs/crs.h             */
+    BBO_ALGO_CRS = 21,         /* CrsSearch    src/multivariate/crs/crs.h             */
+    BBO_ALGO_SSDE = 22         /* SSDESearch   src/multivariate/de/ssde.h             */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -599,6 +600,48 @@ void bbo_crs_params_default(bbo_crs_params *p);   /* 4096, 0 */
 int bbo_crs_configure(bbo_handle h, const bbo_crs_params *p);
 int bbo_crs_phase(bbo_handle h, int phase);
 int bbo_crs_inject_draws(bbo_handle h, const double *table, int count);
+
+/* ---- SSDE (BBO_ALGO_SSDE): SSDE(mfev,npinit,tol,patience=1000,npmin=4,ptop=0.11,h=100,usede=false,
+ * repaircr=true)  py/multivariate_py.cpp, the spherical search of Kumar et al. 2019 with the DE fallback
+ * of Zhao et al. 2022 (ssde.cpp).  mfev, np (= npinit) and tol travel in bbo_params; the rest travels here
+ * (the defaults are the Python binding's: usede = 0).  The pool starts uniform in the box, with usede
+ * joined by its opposites lower + upper - x, the best npinit of which stay (fev = 2 npinit): a finite box
+ * is mandatory, `guess` is not read.  bbo_init refuses (BBO_ERR_ARG) a box that is not finite, n outside
+ * [1, 512], npinit outside [4, 4096], npmin < 4 or > npinit, h < 1 or > 65536, ptop outside (0, 1),
+ * patience < 0, usede / repaircr other than 0 or 1, and an objective program.  ptop = 1 is refused because
+ * the reference draws pbest from [0, int(ptop np)] inclusive and would read past the pool.
+ * bbo_ssde_configure is legal between bbo_create and bbo_init.  SSDE is no base of a restart driver and
+ * is not sharded over devices.
+ * One bbo_iterate is one iterate() of the reference: the members in rank order, each reading the rows the
+ * members before it have replaced, R = fev / mfev read at every member, the spherical trial and, with
+ * usede, on its failure the DE trial; then the memory update (L1, L2, LCR), the sort (stable on ties),
+ * convcount and the linear shrink of np, which here never falls under 4.  The budget is tested between
+ * generations only, so fev may pass mfev by up to one generation.  The pool stays in place: "order" maps
+ * a rank to its row, "x" and "f" are in rank order.
+ * bbo_ssde_phase walks the same generation one EVALUATION at a time: 0 advances every population to its
+ * next pending point ("cand": the spherical or the DE trial; "pending" is 0 once the generation is
+ * complete), 1 evaluates "cand" into "fcand", 2 absorbs the value.
+ * bbo_ssde_inject_draws: `populations` tables of n + npinit * (9 + 3 n) doubles that replace the generator
+ * from the next generation on: the permutation whose consecutive pairs are the rotated planes (n values),
+ * then per member i the OUTCOMES of its draws: iL, the normal of prank, p, q, r, pbest, the accepted ci
+ * (in (0, 1]), the normal of CRi, j0, then n uniforms of the binary vector, n of the crossover and n of
+ * the redraw inside the box.  Uniforms are raw canonicals in [0, 1); a draw the generation does not make
+ * is padding.  NULL returns to the device generator, which is Philox keyed by (generation, member,
+ * purpose, coordinate, attempt).  Its rejection loops are bounded: after 64 attempts sample3 takes the
+ * next free index cyclically and ci becomes min(1, L2[iL]).  "record_draws" keeps the same table of the
+ * last generation ("draws").
+ * Keys: "x" "f" "order" "L1" "L2" "LCR" (h values each) "k" "kCR" "np" "fev" "gen" "convcount" "perm"
+ * "cand" "fcand" "pending" "stage" "member" "stop" "conv" "npinit" "n".  Writable: "x" (m rows, 4 <= m <=
+ * npinit: np becomes m; re-evaluated and re-sorted), "L1" "L2" "LCR" "k" "kCR" "fev" "convcount", "perm"
+ * (the next generation keeps it instead of drawing one), "cand" "fcand", "substream" (an extension: the
+ * sub-stream of population 0, from which the pool is drawn again; population p draws from substream + p).
+ * "stop": 1 converged() (the spread of the members' norms under tol, or convcount > patience), 2 fev >=
+ * mfev.  A NaN value counts as +inf. */
+typedef struct { int patience, npmin; double ptop; int h, usede, repaircr; } bbo_ssde_params;
+void bbo_ssde_params_default(bbo_ssde_params *p);   /* 1000, 4, 0.11, 100, 0, 1 */
+int bbo_ssde_configure(bbo_handle h, const bbo_ssde_params *p);
+int bbo_ssde_phase(bbo_handle h, int phase);
+int bbo_ssde_inject_draws(bbo_handle h, const double *table, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
