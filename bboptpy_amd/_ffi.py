@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
     ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
-    ALGO_CRS, ALGO_SSDE = range(23)
+    ALGO_CRS, ALGO_SSDE, ALGO_ACD = range(24)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -40,6 +40,11 @@ SLPSO_PHASE_ADVANCE, SLPSO_PHASE_EVALUATE, SLPSO_PHASE_ABSORB = range(3)
 CRS_PHASE_ADVANCE, CRS_PHASE_EVALUATE, CRS_PHASE_ABSORB = range(3)
 # bbo_ssde_phase
 SSDE_PHASE_ADVANCE, SSDE_PHASE_EVALUATE, SSDE_PHASE_ABSORB = range(3)
+# bbo_acd_phase
+ACD_PHASE_ADVANCE, ACD_PHASE_EVALUATE, ACD_PHASE_ABSORB = range(3)
+# ACD "flag" and "rule"
+ACD_FLAG_CONVERGED, ACD_FLAG_BUDGET = 1, 2
+ACD_RULE_FTOL, ACD_RULE_XTOL = 1, 2
 # CRS "flag": the tolerance, the budget, the depth cap
 CRS_FLAG_TOL, CRS_FLAG_BUDGET, CRS_FLAG_DEPTH = 1, 2, 3
 # LmCMAES "flag": the CMA engines' codes and sigma < 1e-16
@@ -130,6 +135,12 @@ class SsdeParams(C.Structure):
     """bbo_ssde_params: the arguments of SSDE that bbo_params has no field for"""
     _fields_ = [("patience", C.c_int), ("npmin", C.c_int), ("ptop", C.c_double), ("h", C.c_int),
                 ("usede", C.c_int), ("repaircr", C.c_int)]
+
+
+class AcdParams(C.Structure):
+    """bbo_acd_params: the arguments of ACD that bbo_params has no field for"""
+    _fields_ = [("ksucc", C.c_double), ("kunsucc", C.c_double), ("from_guess", C.c_int),
+                ("speculate", C.c_int)]
 
 
 class Objective(C.Structure):
@@ -238,6 +249,10 @@ def lib():
     L.bbo_ssde_configure.argtypes = [C.c_void_p, C.POINTER(SsdeParams)]
     L.bbo_ssde_phase.argtypes = [C.c_void_p, C.c_int]
     L.bbo_ssde_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.bbo_acd_params_default.argtypes = [C.POINTER(AcdParams)]
+    L.bbo_acd_params_default.restype = None
+    L.bbo_acd_configure.argtypes = [C.c_void_p, C.POINTER(AcdParams)]
+    L.bbo_acd_phase.argtypes = [C.c_void_p, C.c_int]
     L.bbo_last_error.argtypes = [C.c_void_p]
     L.bbo_last_error.restype = C.c_char_p
     L.bbo_version.restype = C.c_char_p
@@ -256,7 +271,8 @@ def lib():
                  "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
                  "bbo_amalgam_inject_points", "bbo_slpso_configure", "bbo_slpso_phase",
                  "bbo_slpso_inject_draws", "bbo_crs_configure", "bbo_crs_phase", "bbo_crs_inject_draws",
-                 "bbo_ssde_configure", "bbo_ssde_phase", "bbo_ssde_inject_draws"):
+                 "bbo_ssde_configure", "bbo_ssde_phase", "bbo_ssde_inject_draws",
+                 "bbo_acd_configure", "bbo_acd_phase"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -282,6 +298,7 @@ EXPORTED_SYMBOLS = (
     "bbo_slpso_params_default", "bbo_slpso_configure", "bbo_slpso_phase", "bbo_slpso_inject_draws",
     "bbo_crs_params_default", "bbo_crs_configure", "bbo_crs_phase", "bbo_crs_inject_draws",
     "bbo_ssde_params_default", "bbo_ssde_configure", "bbo_ssde_phase", "bbo_ssde_inject_draws",
+    "bbo_acd_params_default", "bbo_acd_configure", "bbo_acd_phase",
     "bbo_last_error", "bbo_version",
     "bbo_device_count",
 )

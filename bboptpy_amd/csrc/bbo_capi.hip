@@ -14,6 +14,7 @@
 #include "bbo_slpso.hpp"
 #include "bbo_crs.hpp"
 #include "bbo_ssde.hpp"
+#include "bbo_acd.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -36,6 +37,7 @@ Optimizer* make_amalgam_engine(const bbo_params &p);  // bbo_amalgam.hip
 Optimizer* make_slpso_engine(const bbo_params &p);    // bbo_slpso.hip
 Optimizer* make_crs_engine(const bbo_params &p);      // bbo_crs.hip
 Optimizer* make_ssde_engine(const bbo_params &p);     // bbo_ssde.hip
+Optimizer* make_acd_engine(const bbo_params &p);      // bbo_acd.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -105,15 +107,15 @@ bbo::ObjectiveSpec to_spec(const bbo_objective *o)
 
 // bbo_params as a caller built against an earlier header knows it ends where `stol` begins.  Such a
 // caller can only name the algorithms of its header, so the fields appended for CholeskyCMAES are
-// read and written for BBO_ALGO_CHOLESKY_CMAES, BBO_ALGO_DSA, BBO_ALGO_AMALGAM and BBO_ALGO_SLPSO (whose `stol` travels
-// there: a caller that can name algorithm 13, 19 or 20 has the long struct) alone: nothing here touches memory past
+// read and written for BBO_ALGO_CHOLESKY_CMAES, BBO_ALGO_DSA, BBO_ALGO_AMALGAM, BBO_ALGO_SLPSO and BBO_ALGO_ACD (whose
+// `stol` travels there: a caller that can name algorithm 13, 19, 20 or 23 has the long struct) alone: nothing here touches memory past
 // the struct the caller allocated.
 constexpr size_t PARAMS_BASE_BYTES = offsetof(bbo_params, stol);
 
 inline bool has_long_params(int algo)
 {
     return algo == BBO_ALGO_CHOLESKY_CMAES || algo == BBO_ALGO_DSA || algo == BBO_ALGO_AMALGAM
-            || algo == BBO_ALGO_SLPSO;
+            || algo == BBO_ALGO_SLPSO || algo == BBO_ALGO_ACD;
 }
 
 bbo_params own_copy(const bbo_params *params)
@@ -189,6 +191,7 @@ void bbo_params_default(bbo_params *p, int algo)
     p->pcauchy = -1.;
     if (algo == BBO_ALGO_SPIRAL) p->np = 20;   /* py/multivariate_py.cpp:348 */
     if (algo == BBO_ALGO_NSHS || algo == BBO_ALGO_CRS) p->poll_every = 0;   /* the engine's own chunk: iterations, not generations */
+    if (algo == BBO_ALGO_ACD) p->poll_every = 0;    /* one sweep of n coordinate steps */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -261,6 +264,9 @@ int bbo_create(const bbo_params *params, bbo_handle *out)
             break;
         case BBO_ALGO_SSDE:
             h->opt.reset(bbo::make_ssde_engine(*params));
+            break;
+        case BBO_ALGO_ACD:
+            h->opt.reset(bbo::make_acd_engine(*params));
             break;
         default:
             throw bbo::Error(BBO_ERR_ARG,
@@ -903,6 +909,37 @@ int bbo_ssde_phase(bbo_handle h, int phase)
 int bbo_ssde_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { as_ssde(h)->inject_draws(table, count); });
+}
+
+void bbo_acd_params_default(bbo_acd_params *p)
+{
+    if (!p) return;
+    p->ksucc = 2.;      /* py/multivariate_py.cpp:44-48 */
+    p->kunsucc = 0.5;
+    p->from_guess = 0;
+    p->speculate = 0;
+}
+
+namespace {
+bbo::AcdEngine* as_acd(bbo_handle h)
+{
+    auto *e = dynamic_cast<bbo::AcdEngine*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an ACD handle");
+    return e;
+}
+}
+
+int bbo_acd_configure(bbo_handle h, const bbo_acd_params *p)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_acd_configure: NULL parameters");
+        as_acd(h)->configure(*p);
+    });
+}
+
+int bbo_acd_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { as_acd(h)->phase(phase); });
 }
 
 const char* bbo_last_error(bbo_handle h)

@@ -1473,4 +1473,27 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
     return 1;
 }
 
+// The eigensolver for an engine that is not CMA-ES (ACD, bbo_acd.hpp): the one-workgroup decomposition,
+// n <= 128 with the matrix in LDS, of every matrix of the view d, c whose CmaScal says it is due.  The
+// kernels are the ones launch_eigen uses for a batch (EK_EIGEN_128, EK_EIGEN_256, EK_EIGEN); the view needs
+// C, B, D, eig_work (eigen_view_scratch doubles a matrix) and scal, lazy_isc = 0 and no diagnostics.
+size_t eigen_view_scratch(int ld)
+{
+    return 4 * eig_slab(ld);
+}
+
+void launch_eigen_view(hipStream_t stream, const CmaDev &d, const CmaConst &c)
+{
+    const EigPlan pl = eig_plan(c.n, c.ld);
+    if (!pl.use_lds || !pl.reg_path || c.lazy_isc || d.dbg || d.stamps)
+        throw Error(BBO_ERR_ARG, "launch_eigen_view: n <= 128, no lazy_isc, no diagnostics");
+    auto per_matrix = [&](auto kernel, int threads) {
+        allow_lds((const void*) kernel, 160 * 1024 - 768);
+        hipLaunchKernelGGL(kernel, dim3(c.npop), dim3(threads), pl.lds_bytes, stream, d, c, pl, 0);
+    };
+    if (pl.threads == 128) per_matrix(cma_eigen_128, 128);
+    else if (pl.threads == 256) per_matrix(cma_eigen_256, 256);
+    else per_matrix(cma_eigen, 512);
+}
+
 } // namespace bbo

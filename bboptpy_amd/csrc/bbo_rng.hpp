@@ -53,7 +53,8 @@ enum Stream : uint32_t {
     STREAM_SSDE_INIT = 34,
     STREAM_SSDE_CTRL = 35,
     STREAM_SSDE_R = 36,
-    STREAM_SSDE_PERM = 37
+    STREAM_SSDE_PERM = 37,
+    STREAM_ACD_INIT = 38
 };
 
 struct u32x4 {

@@ -1253,6 +1253,61 @@ class SSDE(MultivariateSearch):
         self._check(_ffi.lib().bbo_ssde_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
 
 
+class ACD(MultivariateSearch):
+    """ACD(mfev, ftol, xtol, ksucc=2., kunsucc=0.5) -- :44-48 (adaptive coordinate descent, Loshchilov,
+    Schoenauer & Sebag 2011; acd.cpp).  A coordinate search along the columns of B with an archive of 2 n
+    points; behind every sweep that improved, the rank-one update of C and its eigendecomposition give
+    the next B.  iterate() is ONE coordinate step (two evaluations, x1 then x2); run(g) counts coordinate
+    steps and polls once per sweep (`poll_every` = 0, the default) or every `poll_every` steps.  x_best
+    starts uniform in the box: a finite box is mandatory and `guess` is not read, as in the reference;
+    from_guess=True (an extension, keyword-only) starts population p at its row of `guess`.  The budget
+    is tested between steps: n_evals may pass mfev by 1.  get_state("flag") is 1 converged, 2 budget;
+    get_state("rule") says which rule converged: 1 ftol over the history, 2 xtol.  n is at most 128: the
+    eigensolver's routes beyond that are driven from inside the CMA-ES engine only.  `speculate` (the
+    speculative sweep over the next pending coordinates) was built, measured slower at 4096 populations
+    and dropped: only False is accepted."""
+    _algo = _ffi.ALGO_ACD
+    _accepts_program = False
+    MAX_N = 128
+
+    def __init__(self, mfev, ftol, xtol, ksucc=2., kunsucc=0.5, *, from_guess=False, speculate=False,
+                 **ext):
+        super().__init__(**ext)
+        if speculate:
+            raise ValueError("ACD: the speculative sweep was measured and dropped; speculate must be False")
+        p = self._params
+        p.mfev, p.tol, p.stol = int(mfev), float(ftol), float(xtol)
+        a = self._acd = _ffi.AcdParams()
+        a.ksucc, a.kunsucc = float(ksucc), float(kunsucc)
+        a.from_guess, a.speculate = int(bool(from_guess)), 0
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("ACD: dimension must be in [1, %d]" % self.MAX_N)
+        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
+            raise ValueError("ACD draws x_best from [lower, upper]: the bounds must be finite")
+        return n, lower, upper, guess
+
+    def _create(self):
+        h = super()._create()
+        status = _ffi.lib().bbo_acd_configure(h, C.byref(self._acd))
+        if status < 0:
+            msg = _ffi.lib().bbo_last_error(h)
+            _ffi.lib().bbo_destroy(h)
+            raise _ffi.BboError(status, msg.decode() if msg else "")
+        return h
+
+    def phase(self, which):
+        """a coordinate step one part at a time: 0 form x1 and x2 ("cand", 2 x n), 1 evaluate them
+        ("value"), 2 absorb the values, finish the step and, where due, update the encoding.  Phase 0
+        returns the number of populations that have a pair pending."""
+        self._check(_ffi.lib().bbo_acd_phase(self._handle, int(which)))
+        if int(which) != 0:
+            return None
+        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

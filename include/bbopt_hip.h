@@ -64,7 +64,8 @@ typedef enum {
     BBO_ALGO_AMALGAM = 19,     /* Amalgam      src/multivariate/amalgam/amalgam.h     */
     BBO_ALGO_SLPSO = 20,       /* SLPSOSearch  src/multivariate/pso/slpso.h           */
     BBO_ALGO_CRS = 21,         /* CrsSearch    src/multivariate/crs/crs.h             */
-    BBO_ALGO_SSDE = 22         /* SSDESearch   src/multivariate/de/ssde.h             */
+    BBO_ALGO_SSDE = 22,        /* SSDESearch   src/multivariate/de/ssde.h             */
+    BBO_ALGO_ACD = 23          /* ACD          src/multivariate/acd/acd.h             */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -642,6 +643,42 @@ void bbo_ssde_params_default(bbo_ssde_params *p);   /* 1000, 4, 0.11, 100, 0, 1 
 int bbo_ssde_configure(bbo_handle h, const bbo_ssde_params *p);
 int bbo_ssde_phase(bbo_handle h, int phase);
 int bbo_ssde_inject_draws(bbo_handle h, const double *table, int count);
+
+/* ---- ACD (BBO_ALGO_ACD): ACD(mfev,ftol,xtol,ksucc=2.,kunsucc=0.5)  py/multivariate_py.cpp:44-48, the
+ * adaptive coordinate descent of Loshchilov, Schoenauer & Sebag 2011 (acd.cpp): a coordinate search along
+ * the columns of B, an archive of 2 n points, and after every sweep that improved a rank-one covariance
+ * update with a symmetric eigendecomposition (adaptive encoding).  mfev travels in bbo_params, ftol in `tol`
+ * and xtol in `stol` (bbo_params_default writes the long struct for this algorithm); the rest travels here.
+ * x_best starts uniform in the box: a finite box is mandatory; `guess` is read only with from_guess = 1
+ * (an extension: population p starts at its row of `guess`).  Limits: n in [1, 128], any `populations`;
+ * bbo_init refuses (BBO_ERR_ARG) a box that is not finite, n outside the limits and an objective program;
+ * speculate = 1 (the speculative sweep) was built, measured slower at 4096 populations and dropped: it is
+ * refused by bbo_acd_configure.
+ * bbo_acd_configure is legal between bbo_create and bbo_init.  ACD is no base of a restart driver and is not
+ * sharded over devices.
+ * One bbo_iterate is one iterate() of the reference: ONE coordinate step (two evaluations, x1 then x2), with
+ * the archive ranking, updateAE() and the decomposition behind the last step of a sweep that improved.
+ * bbo_run counts coordinate steps; it advances `poll_every` of them per population and poll (0: n, one
+ * sweep).  The budget is tested between steps, so fev may pass mfev by 1.
+ * bbo_acd_phase walks a step with a host objective's granularity: 0 forms x1 and x2 ("cand", 2 n values;
+ * "pending" 1), 1 evaluates them into "value" (2 values), 2 absorbs the values, does the step's bookkeeping
+ * and, where due, the update.
+ * The archive is ranked stably with respect to the persisting `order` (the reference's std::sort is stable
+ * only while 2 n <= 16).  From the second update on C has a degenerate eigenspace whose basis rounding
+ * decides, so B is the reference's only up to that choice.
+ * Keys: "xbest" "fbest" "sigma" "B" "invB" "C" (n x n, row-major) "p" "m" "mold" "diagd" "colmax", "x" / "f"
+ * the archive in place (2 n rows), "order", "ix" "it" "itae" "improved" "fev", "fhist" (the ring, cp values),
+ * "cp", "cand" "value" "pending", "flag" (1 converged, 2 fev >= mfev), "rule" (1 ftol, 2 xtol), "conv",
+ * "due".  Writable: "xbest" "fbest" "sigma" "B" (recomputes "colmax") "invB" "C" "p" "m" "mold"
+ * "diagd" "x" "f" "order" "fhist" "value" "ix" "it" "itae" "improved" "fev", and "substream" (write-only, an
+ * extension: x_best of the population is drawn again from that sub-stream); every other key is read-only.
+ * The device's history rule takes the newest entry of the ring from "fbest", which is what the last step
+ * wrote there: after a set of "fbest", "it" or "fhist" without a step, "conv" and bbo_solution (which read
+ * the ring) may say otherwise until the next step.  A NaN value counts as +inf. */
+typedef struct { double ksucc, kunsucc; int from_guess; int speculate; } bbo_acd_params;
+void bbo_acd_params_default(bbo_acd_params *p);   /* 2., 0.5, 0, 0 */
+int bbo_acd_configure(bbo_handle h, const bbo_acd_params *p);
+int bbo_acd_phase(bbo_handle h, int phase);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
