@@ -157,6 +157,75 @@ class BboError(RuntimeError):
 _lib = None
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _ip = C.POINTER(C.c_int)
+_h, _i = C.c_void_p, C.c_int
+_TABLE = [C.c_void_p, C.c_int]      # an injected table and its length; NULL: the device draws
+
+# the entry points every handle has, and those of the CMA-ES, CCPSO and program objects:
+# name -> (argtypes, restype); no argtypes: the function takes none
+CORE = {
+    "bbo_params_default": ([C.POINTER(Params), _i], None),
+    "bbo_create": ([C.POINTER(Params), C.POINTER(_h)], _i),
+    "bbo_create_restart": ([C.POINTER(Params), _h, C.POINTER(_h)], _i),
+    "bbo_destroy": ([_h], _i),
+    "bbo_init": ([_h, _i, _dp, _dp, _dp, C.POINTER(Objective)], _i),
+    "bbo_iterate": ([_h], _i),
+    "bbo_solution": ([_h, _dp, _ip, _ip], _i),
+    "bbo_solution_of": ([_h, _i, _dp, _ip, _ip], _i),
+    "bbo_optimize": ([_h, _i, _dp, _dp, _dp, C.POINTER(Objective), _dp, _ip, _ip], _i),
+    "bbo_run": ([_h, _i, _ip], _i),
+    "bbo_get": ([_h, C.c_char_p, _i, C.c_void_p, _i], _i),
+    "bbo_set": ([_h, C.c_char_p, _i, _dp, _i], _i),
+    "bbo_cma_phase_run": ([_h, _i], _i),
+    "bbo_cma_inject_normals": ([_h] + _TABLE, _i),
+    "bbo_cma_set_params": ([_h, _i, C.c_double, _i], _i),
+    "bbo_cma_set_seed": ([_h, C.c_uint64], _i),
+    "bbo_cma_evaluate": ([_h, _dp, C.POINTER(C.c_double)], _i),
+    "bbo_ccpso_set_shard": ([_h, _i, _i], _i),
+    "bbo_ccpso_set_local": ([_h, _h, _i], _i),
+    "bbo_ccpso_phase": ([_h, _i], _i),
+    "bbo_ccpso_table_record": ([_h], _i),
+    "bbo_ccpso_export_tables": ([_h, C.c_void_p, _i], _i),
+    "bbo_ccpso_merge_tables": ([_h, C.c_void_p, _i, _i], _i),
+    "bbo_program_create": ([C.c_char_p, C.c_char_p, C.c_void_p, _i, C.POINTER(_h)], _i),
+    "bbo_program_destroy": ([_h], _i),
+    "bbo_last_error": ([_h], C.c_char_p),
+    "bbo_version": (None, C.c_char_p),
+    "bbo_device_count": (None, _i),
+}
+
+# the engines with an extension struct: prefix -> (the struct of bbo_<prefix>_params_default and
+# bbo_<prefix>_configure, whether bbo_<prefix>_phase exists, the bbo_<prefix>_inject_<what> entry points
+# with their arguments behind the handle)
+EXTENSIONS = {
+    "jaya": (JayaParams, False, {}),
+    "dsa": (DsaParams, False, {}),
+    "hees": (HeesParams, True, {"normals": _TABLE}),
+    "spiral": (SpiralParams, True, {"uniforms": _TABLE}),
+    "nshs": (NshsParams, True, {"uniforms": _TABLE}),
+    "lm": (LmParams, True, {"draws": _TABLE}),
+    "xnes": (XnesParams, True, {"normals": _TABLE}),
+    "amalgam": (AmalgamParams, True, {"draws": _TABLE + _TABLE, "points": _TABLE}),
+    "slpso": (SlpsoParams, True, {"draws": _TABLE}),
+    "crs": (CrsParams, True, {"draws": _TABLE}),
+    "ssde": (SsdeParams, True, {"draws": _TABLE}),
+    "acd": (AcdParams, True, {}),
+}
+
+
+def _signatures():
+    """every exported function: name -> (argtypes, restype)"""
+    sig = dict(CORE)
+    for prefix, (struct, has_phase, injects) in EXTENSIONS.items():
+        sig["bbo_%s_params_default" % prefix] = ([C.POINTER(struct)], None)
+        sig["bbo_%s_configure" % prefix] = ([_h, C.POINTER(struct)], _i)
+        if has_phase:
+            sig["bbo_%s_phase" % prefix] = ([_h, _i], _i)
+        for what, args in injects.items():
+            sig["bbo_%s_inject_%s" % (prefix, what)] = ([_h] + args, _i)
+    return sig
+
+
+EXPORTED_SYMBOLS = tuple(_signatures())
 
 
 def lib():
@@ -169,139 +238,13 @@ def lib():
             "bboptpy_amd: %s is missing. Build it with `python __graft_entry__.py` (hipcc, "
             "gfx950). There is no CPU fallback." % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    L.bbo_params_default.argtypes = [C.POINTER(Params), C.c_int]
-    L.bbo_params_default.restype = None
-    L.bbo_create.argtypes = [C.POINTER(Params), C.POINTER(C.c_void_p)]
-    L.bbo_create_restart.argtypes = [C.POINTER(Params), C.c_void_p, C.POINTER(C.c_void_p)]
-    L.bbo_destroy.argtypes = [C.c_void_p]
-    L.bbo_init.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, C.POINTER(Objective)]
-    L.bbo_iterate.argtypes = [C.c_void_p]
-    L.bbo_solution.argtypes = [C.c_void_p, _dp, _ip, _ip]
-    L.bbo_solution_of.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _ip]
-    L.bbo_optimize.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, C.POINTER(Objective), _dp,
-                               _ip, _ip]
-    L.bbo_run.argtypes = [C.c_void_p, C.c_int, _ip]
-    L.bbo_get.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int]
-    L.bbo_set.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _dp, C.c_int]
-    L.bbo_cma_phase_run.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_cma_inject_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_cma_set_params.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int]
-    L.bbo_cma_set_seed.argtypes = [C.c_void_p, C.c_uint64]
-    L.bbo_cma_evaluate.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_double)]
-    L.bbo_ccpso_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.bbo_ccpso_set_local.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_ccpso_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_ccpso_table_record.argtypes = [C.c_void_p]
-    L.bbo_ccpso_export_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_ccpso_merge_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    L.bbo_program_create.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int,
-                                     C.POINTER(C.c_void_p)]
-    L.bbo_program_destroy.argtypes = [C.c_void_p]
-    L.bbo_jaya_params_default.argtypes = [C.POINTER(JayaParams)]
-    L.bbo_jaya_params_default.restype = None
-    L.bbo_jaya_configure.argtypes = [C.c_void_p, C.POINTER(JayaParams)]
-    L.bbo_dsa_params_default.argtypes = [C.POINTER(DsaParams)]
-    L.bbo_dsa_params_default.restype = None
-    L.bbo_dsa_configure.argtypes = [C.c_void_p, C.POINTER(DsaParams)]
-    L.bbo_hees_params_default.argtypes = [C.POINTER(HeesParams)]
-    L.bbo_hees_params_default.restype = None
-    L.bbo_hees_configure.argtypes = [C.c_void_p, C.POINTER(HeesParams)]
-    L.bbo_hees_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_hees_inject_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_spiral_params_default.argtypes = [C.POINTER(SpiralParams)]
-    L.bbo_spiral_params_default.restype = None
-    L.bbo_spiral_configure.argtypes = [C.c_void_p, C.POINTER(SpiralParams)]
-    L.bbo_spiral_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_spiral_inject_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_nshs_params_default.argtypes = [C.POINTER(NshsParams)]
-    L.bbo_nshs_params_default.restype = None
-    L.bbo_nshs_configure.argtypes = [C.c_void_p, C.POINTER(NshsParams)]
-    L.bbo_nshs_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_nshs_inject_uniforms.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_lm_params_default.argtypes = [C.POINTER(LmParams)]
-    L.bbo_lm_params_default.restype = None
-    L.bbo_lm_configure.argtypes = [C.c_void_p, C.POINTER(LmParams)]
-    L.bbo_lm_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_lm_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_xnes_params_default.argtypes = [C.POINTER(XnesParams)]
-    L.bbo_xnes_params_default.restype = None
-    L.bbo_xnes_configure.argtypes = [C.c_void_p, C.POINTER(XnesParams)]
-    L.bbo_xnes_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_xnes_inject_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_amalgam_params_default.argtypes = [C.POINTER(AmalgamParams)]
-    L.bbo_amalgam_params_default.restype = None
-    L.bbo_amalgam_configure.argtypes = [C.c_void_p, C.POINTER(AmalgamParams)]
-    L.bbo_amalgam_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_amalgam_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.bbo_amalgam_inject_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_slpso_params_default.argtypes = [C.POINTER(SlpsoParams)]
-    L.bbo_slpso_params_default.restype = None
-    L.bbo_slpso_configure.argtypes = [C.c_void_p, C.POINTER(SlpsoParams)]
-    L.bbo_slpso_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_slpso_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_crs_params_default.argtypes = [C.POINTER(CrsParams)]
-    L.bbo_crs_params_default.restype = None
-    L.bbo_crs_configure.argtypes = [C.c_void_p, C.POINTER(CrsParams)]
-    L.bbo_crs_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_crs_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_ssde_params_default.argtypes = [C.POINTER(SsdeParams)]
-    L.bbo_ssde_params_default.restype = None
-    L.bbo_ssde_configure.argtypes = [C.c_void_p, C.POINTER(SsdeParams)]
-    L.bbo_ssde_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_ssde_inject_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bbo_acd_params_default.argtypes = [C.POINTER(AcdParams)]
-    L.bbo_acd_params_default.restype = None
-    L.bbo_acd_configure.argtypes = [C.c_void_p, C.POINTER(AcdParams)]
-    L.bbo_acd_phase.argtypes = [C.c_void_p, C.c_int]
-    L.bbo_last_error.argtypes = [C.c_void_p]
-    L.bbo_last_error.restype = C.c_char_p
-    L.bbo_version.restype = C.c_char_p
-    L.bbo_device_count.restype = C.c_int
-    for name in ("bbo_create", "bbo_create_restart", "bbo_destroy", "bbo_init", "bbo_iterate",
-                 "bbo_solution", "bbo_solution_of", "bbo_optimize", "bbo_run", "bbo_get",
-                 "bbo_set", "bbo_cma_phase_run", "bbo_cma_inject_normals", "bbo_cma_set_params",
-                 "bbo_cma_set_seed", "bbo_cma_evaluate", "bbo_ccpso_set_shard", "bbo_ccpso_set_local", "bbo_ccpso_phase",
-                 "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
-                 "bbo_program_create", "bbo_program_destroy", "bbo_jaya_configure",
-                 "bbo_dsa_configure", "bbo_hees_configure", "bbo_hees_phase",
-                 "bbo_hees_inject_normals", "bbo_spiral_configure", "bbo_spiral_phase",
-                 "bbo_spiral_inject_uniforms", "bbo_nshs_configure", "bbo_nshs_phase",
-                 "bbo_nshs_inject_uniforms", "bbo_lm_configure", "bbo_lm_phase", "bbo_lm_inject_draws",
-                 "bbo_xnes_configure", "bbo_xnes_phase", "bbo_xnes_inject_normals",
-                 "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
-                 "bbo_amalgam_inject_points", "bbo_slpso_configure", "bbo_slpso_phase",
-                 "bbo_slpso_inject_draws", "bbo_crs_configure", "bbo_crs_phase", "bbo_crs_inject_draws",
-                 "bbo_ssde_configure", "bbo_ssde_phase", "bbo_ssde_inject_draws",
-                 "bbo_acd_configure", "bbo_acd_phase"):
-        getattr(L, name).restype = C.c_int
+    for name, (argtypes, restype) in _signatures().items():
+        fn = getattr(L, name)
+        if argtypes is not None:
+            fn.argtypes = argtypes
+        fn.restype = restype
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = (
-    "bbo_params_default", "bbo_create", "bbo_create_restart", "bbo_destroy", "bbo_init",
-    "bbo_iterate", "bbo_solution", "bbo_solution_of", "bbo_optimize", "bbo_run", "bbo_get",
-    "bbo_set", "bbo_cma_phase_run", "bbo_cma_inject_normals", "bbo_cma_set_params",
-    "bbo_cma_set_seed", "bbo_cma_evaluate", "bbo_ccpso_set_shard", "bbo_ccpso_set_local", "bbo_ccpso_phase",
-    "bbo_ccpso_table_record", "bbo_ccpso_export_tables", "bbo_ccpso_merge_tables",
-    "bbo_program_create", "bbo_program_destroy",
-    "bbo_jaya_params_default", "bbo_jaya_configure",
-    "bbo_dsa_params_default", "bbo_dsa_configure",
-    "bbo_hees_params_default", "bbo_hees_configure", "bbo_hees_phase", "bbo_hees_inject_normals",
-    "bbo_spiral_params_default", "bbo_spiral_configure", "bbo_spiral_phase",
-    "bbo_spiral_inject_uniforms",
-    "bbo_nshs_params_default", "bbo_nshs_configure", "bbo_nshs_phase", "bbo_nshs_inject_uniforms",
-    "bbo_lm_params_default", "bbo_lm_configure", "bbo_lm_phase", "bbo_lm_inject_draws",
-    "bbo_xnes_params_default", "bbo_xnes_configure", "bbo_xnes_phase", "bbo_xnes_inject_normals",
-    "bbo_amalgam_params_default", "bbo_amalgam_configure", "bbo_amalgam_phase", "bbo_amalgam_inject_draws",
-    "bbo_amalgam_inject_points",
-    "bbo_slpso_params_default", "bbo_slpso_configure", "bbo_slpso_phase", "bbo_slpso_inject_draws",
-    "bbo_crs_params_default", "bbo_crs_configure", "bbo_crs_phase", "bbo_crs_inject_draws",
-    "bbo_ssde_params_default", "bbo_ssde_configure", "bbo_ssde_phase", "bbo_ssde_inject_draws",
-    "bbo_acd_params_default", "bbo_acd_configure", "bbo_acd_phase",
-    "bbo_last_error", "bbo_version",
-    "bbo_device_count",
-)
 
 
 def check(status, handle=None):

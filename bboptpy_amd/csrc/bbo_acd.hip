@@ -145,57 +145,33 @@ void AcdEngine::init(int n, const double *lower, const double *upper, const doub
 
 void AcdEngine::launch_sweep(int mode, int k, bool begin)
 {
-    timer_.begin(stream_, K_SWEEP);
-    hipLaunchKernelGGL(acd_sweep, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_, mode, k, begin ? 1 : 0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_SWEEP, [&] {
+        hipLaunchKernelGGL(acd_sweep, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_, mode, k, begin ? 1 : 0);
+    });
 }
 
 // the values of every population's pending pair, x1 then x2
 void AcdEngine::launch_eval()
 {
     if (!obj_.needs_host()) {
-        timer_.begin(stream_, K_EVAL);
-        hipLaunchKernelGGL(acd_eval, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+        timed(K_EVAL, [&] { hipLaunchKernelGGL(acd_eval, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_); });
         return;
     }
-    // in population order, f1 then f2 (:131-132): the callable is called exactly fev times
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int P = c_.npop;
-    std::vector<AcdScal> sc(P);
-    scal_.download(sc.data(), P);
-    std::vector<double> xh((size_t) 2 * c_.ld);
-    for (int p = 0; p < P; p++) {
-        if (!sc[p].pending || (c_.honor_stop && sc[p].stop)) continue;
-        cand_.download(xh.data(), xh.size(), (size_t) p * 2 * c_.ld);
-        double f[2] = { 0., 0. };
-        obj_.eval_host(xh.data(), 1, c_.n, c_.ld, &f[0]);
-        obj_.eval_host(xh.data() + c_.ld, 1, c_.n, c_.ld, &f[1]);
-        nan_to_inf(f, 2);
-        value_.upload(f, 2, (size_t) 2 * p);
-    }
+    // in population order, f1 then f2 (:131-132)
+    host_evaluate_pending(c_.honor_stop != 0, [&](int p, const AcdScal&) {
+        return PendingPoints { &cand_, (size_t) p * 2 * c_.ld, 2, c_.ld, &value_ };
+    });
 }
 
 // acd_ae, the decomposition and acd_post: no-ops for the populations that are not due
 void AcdEngine::launch_update()
 {
-    timer_.begin(stream_, K_AE);
-    hipLaunchKernelGGL(acd_ae, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_AE, [&] { hipLaunchKernelGGL(acd_ae, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_); });
     if (c_.n > 1) {
         eig_->c.honor_stop = 0;
-        timer_.begin(stream_, K_EIGEN);
-        launch_eigen_view(stream_, eig_->d, eig_->c);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+        timed(K_EIGEN, [&] { launch_eigen_view(stream_, eig_->d, eig_->c); });
     }
-    timer_.begin(stream_, K_POST);
-    hipLaunchKernelGGL(acd_post, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_POST, [&] { hipLaunchKernelGGL(acd_post, dim3(c_.npop), dim3(ACD_THREADS), 0, stream_, d_, c_); });
 }
 
 // k coordinate steps of every population with a device objective: a launch ends with the sweep or where an
@@ -416,14 +392,7 @@ int AcdEngine::set(const std::string &k, int p, const double *in, int count)
     }
     if (k == "order") {
         BBO_REQUIRE(count == 2 * n, "order: 2 n values");
-        std::vector<int> ord(count), seen(count, 0);
-        for (int i = 0; i < count; i++) {
-            BBO_REQUIRE(in[i] == std::floor(in[i]) && in[i] >= 0. && in[i] < count && !seen[(int) in[i]],
-                    "order: a permutation of 0 .. 2 n - 1");
-            ord[i] = (int) in[i];
-            seen[ord[i]] = 1;
-        }
-        order_.upload(ord.data(), count, (size_t) p * 2 * n);
+        order_.upload(permutation_of(in, count, "order: a permutation of 0 .. 2 n - 1").data(), count, (size_t) p * 2 * n);
         return count;
     }
     if (k == "fhist") {

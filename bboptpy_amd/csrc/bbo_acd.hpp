@@ -97,6 +97,7 @@ struct AcdDev {
 
 class AcdEngine: public Engine<AcdScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an ACD handle";
     explicit AcdEngine(const bbo_params &p);
     ~AcdEngine() override;
     void init(int n, const double *lower, const double *upper, const double *guess,

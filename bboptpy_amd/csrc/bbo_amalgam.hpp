@@ -69,6 +69,7 @@ struct AmalgamStage {
 
 class AmalgamEngine: public Engine<AmalgamScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an AMALGAM handle";
     explicit AmalgamEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

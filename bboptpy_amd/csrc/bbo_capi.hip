@@ -61,13 +61,13 @@ std::mutex g_create_mutex;
 std::set<bbo_program> g_programs;
 std::mutex g_programs_mutex;
 
+// the tail of every entry point on a handle: `fn` returns the call's int (a count, or BBO_OK)
 template<class F>
-int guarded(bbo_handle h, F fn)
+int guarded_value(bbo_handle h, F fn)
 {
     if (!h || !h->opt) return BBO_ERR_ARG;
     try {
-        fn();
-        return BBO_OK;
+        return fn();
     } catch (const bbo::Error &e) {
         h->error = e.what();
         return e.status;
@@ -76,6 +76,78 @@ int guarded(bbo_handle h, F fn)
         return BBO_ERR_HIP;
     }
 }
+
+template<class F>
+int guarded(bbo_handle h, F fn)
+{
+    return guarded_value(h, [&] {
+        fn();
+        return (int) BBO_OK;
+    });
+}
+
+// the same for the calls that make an object: their message is the one of bbo_last_error(NULL)
+template<class F>
+int created(const char *fn, bool have_args, F make)
+{
+    std::lock_guard<std::mutex> lock(g_create_mutex);
+    if (!have_args) {
+        g_create_error = std::string(fn) + ": NULL argument";
+        return BBO_ERR_ARG;
+    }
+    try {
+        make();
+        return BBO_OK;
+    } catch (const bbo::Error &e) {
+        g_create_error = e.what();
+        return e.status;
+    } catch (const std::exception &e) {
+        g_create_error = e.what();
+        return BBO_ERR_HIP;
+    }
+}
+
+// the engine behind a handle as the class an extension entry point needs; T::HANDLE_NAME is its refusal
+template<class T>
+T *engine_of(bbo_handle h)
+{
+    auto *e = dynamic_cast<T*>(h->opt.get());
+    if (!e) throw bbo::Error(BBO_ERR_ARG, T::HANDLE_NAME);
+    return e;
+}
+
+// bbo_<engine>_configure
+template<class T, class Params>
+int configure_of(bbo_handle h, const Params *p, const char *fn)
+{
+    return guarded(h, [&] {
+        if (!p) throw bbo::Error(BBO_ERR_ARG, std::string(fn) + ": NULL parameters");
+        engine_of<T>(h)->configure(*p);
+    });
+}
+
+bbo::Optimizer *make_cma_engine(const bbo_params &p)
+{
+    return new bbo::CmaEngine(p);
+}
+
+// bbo_create: the engine of every algorithm (the restart drivers have bbo_create_restart)
+const struct {
+    int algo;
+    bbo::Optimizer *(*make)(const bbo_params&);
+} FACTORIES[] = {
+    { BBO_ALGO_CMAES, make_cma_engine }, { BBO_ALGO_ACTIVE_CMAES, make_cma_engine },
+    { BBO_ALGO_SEP_CMAES, make_cma_engine }, { BBO_ALGO_CHOLESKY_CMAES, make_cma_engine },
+    { BBO_ALGO_SHADE, bbo::make_de_engine }, { BBO_ALGO_JADE, bbo::make_de_engine },
+    { BBO_ALGO_SANSDE, bbo::make_de_engine }, { BBO_ALGO_APSO, bbo::make_pso_engine },
+    { BBO_ALGO_CSO, bbo::make_cso_engine }, { BBO_ALGO_CCPSO, bbo::make_ccpso_engine },
+    { BBO_ALGO_JAYA, bbo::make_jaya_engine }, { BBO_ALGO_DSA, bbo::make_dsa_engine },
+    { BBO_ALGO_HEES, bbo::make_hees_engine }, { BBO_ALGO_SPIRAL, bbo::make_spiral_engine },
+    { BBO_ALGO_NSHS, bbo::make_nshs_engine }, { BBO_ALGO_LM_CMAES, bbo::make_lm_engine },
+    { BBO_ALGO_XNES, bbo::make_xnes_engine }, { BBO_ALGO_AMALGAM, bbo::make_amalgam_engine },
+    { BBO_ALGO_SLPSO, bbo::make_slpso_engine }, { BBO_ALGO_CRS, bbo::make_crs_engine },
+    { BBO_ALGO_SSDE, bbo::make_ssde_engine }, { BBO_ALGO_ACD, bbo::make_acd_engine },
+};
 
 bbo::ObjectiveSpec to_spec(const bbo_objective *o)
 {
@@ -200,98 +272,25 @@ void bbo_params_default(bbo_params *p, int algo)
 
 int bbo_create(const bbo_params *params, bbo_handle *out)
 {
-    std::lock_guard<std::mutex> lock(g_create_mutex);
-    if (!params || !out) {
-        g_create_error = "bbo_create: NULL argument";
-        return BBO_ERR_ARG;
-    }
-    *out = nullptr;
-    try {
+    return created("bbo_create", params && out, [&] {
+        *out = nullptr;
         std::unique_ptr<bbo_handle_s> h(new bbo_handle_s());
         h->algo = params->algo;
         const bbo_params own = own_copy(params);
-        params = &own;
-        switch (params->algo) {
-        case BBO_ALGO_CMAES:
-        case BBO_ALGO_ACTIVE_CMAES:
-        case BBO_ALGO_SEP_CMAES:
-        case BBO_ALGO_CHOLESKY_CMAES:
-            h->opt.reset(new bbo::CmaEngine(*params));
-            break;
-        case BBO_ALGO_SHADE:
-        case BBO_ALGO_JADE:
-        case BBO_ALGO_SANSDE:
-            h->opt.reset(bbo::make_de_engine(*params));
-            break;
-        case BBO_ALGO_APSO:
-            h->opt.reset(bbo::make_pso_engine(*params));
-            break;
-        case BBO_ALGO_CSO:
-            h->opt.reset(bbo::make_cso_engine(*params));
-            break;
-        case BBO_ALGO_CCPSO:
-            h->opt.reset(bbo::make_ccpso_engine(*params));
-            break;
-        case BBO_ALGO_JAYA:
-            h->opt.reset(bbo::make_jaya_engine(*params));
-            break;
-        case BBO_ALGO_DSA:
-            h->opt.reset(bbo::make_dsa_engine(*params));
-            break;
-        case BBO_ALGO_HEES:
-            h->opt.reset(bbo::make_hees_engine(*params));
-            break;
-        case BBO_ALGO_SPIRAL:
-            h->opt.reset(bbo::make_spiral_engine(*params));
-            break;
-        case BBO_ALGO_NSHS:
-            h->opt.reset(bbo::make_nshs_engine(*params));
-            break;
-        case BBO_ALGO_LM_CMAES:
-            h->opt.reset(bbo::make_lm_engine(*params));
-            break;
-        case BBO_ALGO_XNES:
-            h->opt.reset(bbo::make_xnes_engine(*params));
-            break;
-        case BBO_ALGO_AMALGAM:
-            h->opt.reset(bbo::make_amalgam_engine(*params));
-            break;
-        case BBO_ALGO_SLPSO:
-            h->opt.reset(bbo::make_slpso_engine(*params));
-            break;
-        case BBO_ALGO_CRS:
-            h->opt.reset(bbo::make_crs_engine(*params));
-            break;
-        case BBO_ALGO_SSDE:
-            h->opt.reset(bbo::make_ssde_engine(*params));
-            break;
-        case BBO_ALGO_ACD:
-            h->opt.reset(bbo::make_acd_engine(*params));
-            break;
-        default:
-            throw bbo::Error(BBO_ERR_ARG,
-                    "bbo_create: unknown algo (restart drivers use bbo_create_restart)");
-        }
-        *out = h.release();
-        return BBO_OK;
-    } catch (const bbo::Error &e) {
-        g_create_error = e.what();
-        return e.status;
-    } catch (const std::exception &e) {
-        g_create_error = e.what();
-        return BBO_ERR_HIP;
-    }
+        for (const auto &f : FACTORIES)
+            if (f.algo == own.algo) {
+                h->opt.reset(f.make(own));
+                *out = h.release();
+                return;
+            }
+        throw bbo::Error(BBO_ERR_ARG, "bbo_create: unknown algo (restart drivers use bbo_create_restart)");
+    });
 }
 
 int bbo_create_restart(const bbo_params *params, bbo_handle base, bbo_handle *out)
 {
-    std::lock_guard<std::mutex> lock(g_create_mutex);
-    if (!params || !out || !base || !base->opt) {
-        g_create_error = "bbo_create_restart: NULL argument";
-        return BBO_ERR_ARG;
-    }
-    *out = nullptr;
-    try {
+    return created("bbo_create_restart", params && out && base && base->opt, [&] {
+        *out = nullptr;
         if (params->algo != BBO_ALGO_IPOP_CMAES && params->algo != BBO_ALGO_BIPOP_CMAES)
             throw bbo::Error(BBO_ERR_ARG, "bbo_create_restart: algo must be IPOP or BIPOP");
         if (base->algo != BBO_ALGO_CMAES && base->algo != BBO_ALGO_ACTIVE_CMAES
@@ -302,39 +301,20 @@ int bbo_create_restart(const bbo_params *params, bbo_handle base, bbo_handle *ou
         const bbo_params own = own_copy(params);
         h->opt.reset(bbo::make_restart_driver(own, base->opt.get()));
         *out = h.release();
-        return BBO_OK;
-    } catch (const bbo::Error &e) {
-        g_create_error = e.what();
-        return e.status;
-    } catch (const std::exception &e) {
-        g_create_error = e.what();
-        return BBO_ERR_HIP;
-    }
+    });
 }
 
 int bbo_program_create(const char *source, const char *arch, const double *data, int data_count,
         bbo_program *out)
 {
-    std::lock_guard<std::mutex> lock(g_create_mutex);
-    if (!out) {
-        g_create_error = "bbo_program_create: NULL argument";
-        return BBO_ERR_ARG;
-    }
-    *out = nullptr;
-    try {
+    return created("bbo_program_create", out != nullptr, [&] {
+        *out = nullptr;
         std::unique_ptr<bbo_program_s> p(new bbo_program_s());
         p->prog = bbo::Program::compile(source, arch, data, data_count);
         std::lock_guard<std::mutex> reg(g_programs_mutex);
         g_programs.insert(p.get());
         *out = p.release();
-        return BBO_OK;
-    } catch (const bbo::Error &e) {
-        g_create_error = e.what();
-        return e.status;
-    } catch (const std::exception &e) {
-        g_create_error = e.what();
-        return BBO_ERR_HIP;
-    }
+    });
 }
 
 int bbo_program_destroy(bbo_program p)
@@ -404,55 +384,30 @@ int bbo_run(bbo_handle h, int max_generations, int *generations_done)
 
 int bbo_get(bbo_handle h, const char *key, int population, double *out, int cap)
 {
-    if (!h || !h->opt || !key) return BBO_ERR_ARG;
-    try {
-        return h->opt->get(key, population, out, cap);
-    } catch (const bbo::Error &e) {
-        h->error = e.what();
-        return e.status;
-    } catch (const std::exception &e) {
-        h->error = e.what();
-        return BBO_ERR_HIP;
-    }
+    if (!key) return BBO_ERR_ARG;
+    return guarded_value(h, [&] { return h->opt->get(key, population, out, cap); });
 }
 
 int bbo_set(bbo_handle h, const char *key, int population, const double *in, int count)
 {
-    if (!h || !h->opt || !key || !in) return BBO_ERR_ARG;
-    try {
-        return h->opt->set(key, population, in, count);
-    } catch (const bbo::Error &e) {
-        h->error = e.what();
-        return e.status;
-    } catch (const std::exception &e) {
-        h->error = e.what();
-        return BBO_ERR_HIP;
-    }
+    if (!key || !in) return BBO_ERR_ARG;
+    return guarded_value(h, [&] { return h->opt->set(key, population, in, count); });
 }
 
 int bbo_cma_phase_run(bbo_handle h, int phase)
 {
-    return guarded(h, [&] {
-        auto *cma = dynamic_cast<bbo::CmaEngine*>(h->opt.get());
-        if (!cma) throw bbo::Error(BBO_ERR_ARG, "not a CMA-ES handle");
-        cma->phase(phase);
-    });
+    return guarded(h, [&] { engine_of<bbo::CmaEngine>(h)->phase(phase); });
 }
 
 int bbo_cma_inject_normals(bbo_handle h, const double *z, int count)
 {
-    return guarded(h, [&] {
-        auto *cma = dynamic_cast<bbo::CmaEngine*>(h->opt.get());
-        if (!cma) throw bbo::Error(BBO_ERR_ARG, "not a CMA-ES handle");
-        cma->inject_normals(z, count);
-    });
+    return guarded(h, [&] { engine_of<bbo::CmaEngine>(h)->inject_normals(z, count); });
 }
 
 int bbo_cma_set_params(bbo_handle h, int np, double sigma0, int mfev)
 {
     return guarded(h, [&] {
-        auto *cma = dynamic_cast<bbo::CmaEngine*>(h->opt.get());
-        if (!cma) throw bbo::Error(BBO_ERR_ARG, "not a CMA-ES handle");
+        auto *cma = engine_of<bbo::CmaEngine>(h);
         if (np < 4) throw bbo::Error(BBO_ERR_ARG, "CMA-ES needs np >= 4");
         cma->set_params(np, sigma0, mfev);
     });
@@ -460,36 +415,22 @@ int bbo_cma_set_params(bbo_handle h, int np, double sigma0, int mfev)
 
 int bbo_cma_set_seed(bbo_handle h, uint64_t seed)
 {
-    return guarded(h, [&] {
-        auto *cma = dynamic_cast<bbo::CmaEngine*>(h->opt.get());
-        if (!cma) throw bbo::Error(BBO_ERR_ARG, "not a CMA-ES handle");
-        cma->set_seed(seed);
-    });
+    return guarded(h, [&] { engine_of<bbo::CmaEngine>(h)->set_seed(seed); });
 }
 
 int bbo_cma_evaluate(bbo_handle h, const double *x, double *f_out)
 {
     return guarded(h, [&] {
-        auto *cma = dynamic_cast<bbo::CmaEngine*>(h->opt.get());
-        if (!cma) throw bbo::Error(BBO_ERR_ARG, "not a CMA-ES handle");
+        auto *cma = engine_of<bbo::CmaEngine>(h);
         if (!x || !f_out) throw bbo::Error(BBO_ERR_ARG, "NULL argument");
         if (cma->dimension() <= 0) throw bbo::Error(BBO_ERR_STATE, "evaluate before initialize()");
         *f_out = cma->evaluate_point(x);
     });
 }
 
-namespace {
-bbo::CcpsoEngine* as_ccpso(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::CcpsoEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a CCPSO handle");
-    return e;
-}
-}
-
 int bbo_ccpso_set_shard(bbo_handle h, int rank, int world)
 {
-    return guarded(h, [&] { as_ccpso(h)->set_shard(rank, world); });
+    return guarded(h, [&] { engine_of<bbo::CcpsoEngine>(h)->set_shard(rank, world); });
 }
 
 int bbo_ccpso_set_local(bbo_handle h, bbo_handle local, int localfreq)
@@ -497,31 +438,25 @@ int bbo_ccpso_set_local(bbo_handle h, bbo_handle local, int localfreq)
     return guarded(h, [&] {
         if (local && !local->opt) throw bbo::Error(BBO_ERR_ARG, "bbo_ccpso_set_local: dead local handle");
         if (local == h) throw bbo::Error(BBO_ERR_ARG, "bbo_ccpso_set_local: local must be another optimizer");
-        as_ccpso(h)->set_local(local ? local->opt.get() : nullptr, localfreq);
+        engine_of<bbo::CcpsoEngine>(h)->set_local(local ? local->opt.get() : nullptr, localfreq);
     });
 }
 
 int bbo_ccpso_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_ccpso(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::CcpsoEngine>(h)->phase(phase); });
 }
 
 int bbo_ccpso_table_record(bbo_handle h)
 {
-    if (!h || !h->opt) return BBO_ERR_ARG;
-    try {
-        return as_ccpso(h)->table_record();
-    } catch (const bbo::Error &e) {
-        h->error = e.what();
-        return e.status;
-    }
+    return guarded_value(h, [&] { return engine_of<bbo::CcpsoEngine>(h)->table_record(); });
 }
 
 int bbo_ccpso_export_tables(bbo_handle h, double *dst, int device_memory)
 {
     return guarded(h, [&] {
         if (!dst) throw bbo::Error(BBO_ERR_ARG, "NULL destination");
-        as_ccpso(h)->export_tables(dst, device_memory != 0);
+        engine_of<bbo::CcpsoEngine>(h)->export_tables(dst, device_memory != 0);
     });
 }
 
@@ -529,7 +464,7 @@ int bbo_ccpso_merge_tables(bbo_handle h, const double *gathered, int world, int 
 {
     return guarded(h, [&] {
         if (!gathered) throw bbo::Error(BBO_ERR_ARG, "NULL source");
-        as_ccpso(h)->merge_tables(gathered, world, device_memory != 0);
+        engine_of<bbo::CcpsoEngine>(h)->merge_tables(gathered, world, device_memory != 0);
     });
 }
 
@@ -548,12 +483,7 @@ void bbo_jaya_params_default(bbo_jaya_params *p)
 
 int bbo_jaya_configure(bbo_handle h, const bbo_jaya_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_jaya_configure: NULL parameters");
-        auto *e = dynamic_cast<bbo::JayaEngine*>(h->opt.get());
-        if (!e) throw bbo::Error(BBO_ERR_ARG, "not a JAYA handle");
-        e->configure(*p);
-    });
+    return configure_of<bbo::JayaEngine>(h, p, "bbo_jaya_configure");
 }
 
 void bbo_dsa_params_default(bbo_dsa_params *p)
@@ -566,12 +496,7 @@ void bbo_dsa_params_default(bbo_dsa_params *p)
 
 int bbo_dsa_configure(bbo_handle h, const bbo_dsa_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_dsa_configure: NULL parameters");
-        auto *e = dynamic_cast<bbo::DsaEngine*>(h->opt.get());
-        if (!e) throw bbo::Error(BBO_ERR_ARG, "not a DSA handle");
-        e->configure(*p);
-    });
+    return configure_of<bbo::DsaEngine>(h, p, "bbo_dsa_configure");
 }
 
 void bbo_hees_params_default(bbo_hees_params *p)
@@ -582,31 +507,19 @@ void bbo_hees_params_default(bbo_hees_params *p)
     p->print = 0;
 }
 
-namespace {
-bbo::HeesEngine* as_hees(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::HeesEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a HEES handle");
-    return e;
-}
-}
-
 int bbo_hees_configure(bbo_handle h, const bbo_hees_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_hees_configure: NULL parameters");
-        as_hees(h)->configure(*p);
-    });
+    return configure_of<bbo::HeesEngine>(h, p, "bbo_hees_configure");
 }
 
 int bbo_hees_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_hees(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::HeesEngine>(h)->phase(phase); });
 }
 
 int bbo_hees_inject_normals(bbo_handle h, const double *z, int count)
 {
-    return guarded(h, [&] { as_hees(h)->inject_normals(z, count); });
+    return guarded(h, [&] { engine_of<bbo::HeesEngine>(h)->inject_normals(z, count); });
 }
 
 void bbo_spiral_params_default(bbo_spiral_params *p)
@@ -623,31 +536,19 @@ void bbo_spiral_params_default(bbo_spiral_params *p)
     p->thetahigh = 6.28318530718;
 }
 
-namespace {
-bbo::SpiralEngine* as_spiral(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::SpiralEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a SpiralSearch handle");
-    return e;
-}
-}
-
 int bbo_spiral_configure(bbo_handle h, const bbo_spiral_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_spiral_configure: NULL parameters");
-        as_spiral(h)->configure(*p);
-    });
+    return configure_of<bbo::SpiralEngine>(h, p, "bbo_spiral_configure");
 }
 
 int bbo_spiral_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_spiral(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::SpiralEngine>(h)->phase(phase); });
 }
 
 int bbo_spiral_inject_uniforms(bbo_handle h, const double *u, int count)
 {
-    return guarded(h, [&] { as_spiral(h)->inject_uniforms(u, count); });
+    return guarded(h, [&] { engine_of<bbo::SpiralEngine>(h)->inject_uniforms(u, count); });
 }
 
 void bbo_nshs_params_default(bbo_nshs_params *p)
@@ -656,31 +557,19 @@ void bbo_nshs_params_default(bbo_nshs_params *p)
     p->fstdmin = 0.0001;        // py/multivariate_py.cpp:204
 }
 
-namespace {
-bbo::NshsEngine* as_nshs(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::NshsEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an NSHS handle");
-    return e;
-}
-}
-
 int bbo_nshs_configure(bbo_handle h, const bbo_nshs_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_nshs_configure: NULL parameters");
-        as_nshs(h)->configure(*p);
-    });
+    return configure_of<bbo::NshsEngine>(h, p, "bbo_nshs_configure");
 }
 
 int bbo_nshs_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_nshs(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::NshsEngine>(h)->phase(phase); });
 }
 
 int bbo_nshs_inject_uniforms(bbo_handle h, const double *u, int count)
 {
-    return guarded(h, [&] { as_nshs(h)->inject_uniforms(u, count); });
+    return guarded(h, [&] { engine_of<bbo::NshsEngine>(h)->inject_uniforms(u, count); });
 }
 
 void bbo_lm_params_default(bbo_lm_params *p)
@@ -692,31 +581,19 @@ void bbo_lm_params_default(bbo_lm_params *p)
     p->usenew = 1;
 }
 
-namespace {
-bbo::LmEngine* as_lm(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::LmEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an LmCMAES handle");
-    return e;
-}
-}
-
 int bbo_lm_configure(bbo_handle h, const bbo_lm_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_lm_configure: NULL parameters");
-        as_lm(h)->configure(*p);
-    });
+    return configure_of<bbo::LmEngine>(h, p, "bbo_lm_configure");
 }
 
 int bbo_lm_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_lm(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::LmEngine>(h)->phase(phase); });
 }
 
 int bbo_lm_inject_draws(bbo_handle h, const double *table, int count)
 {
-    return guarded(h, [&] { as_lm(h)->inject_draws(table, count); });
+    return guarded(h, [&] { engine_of<bbo::LmEngine>(h)->inject_draws(table, count); });
 }
 
 void bbo_xnes_params_default(bbo_xnes_params *p)
@@ -728,31 +605,19 @@ void bbo_xnes_params_default(bbo_xnes_params *p)
     p->from_guess = 0;
 }
 
-namespace {
-bbo::XnesEngine* as_xnes(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::XnesEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an xNES handle");
-    return e;
-}
-}
-
 int bbo_xnes_configure(bbo_handle h, const bbo_xnes_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_xnes_configure: NULL parameters");
-        as_xnes(h)->configure(*p);
-    });
+    return configure_of<bbo::XnesEngine>(h, p, "bbo_xnes_configure");
 }
 
 int bbo_xnes_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_xnes(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::XnesEngine>(h)->phase(phase); });
 }
 
 int bbo_xnes_inject_normals(bbo_handle h, const double *z, int count)
 {
-    return guarded(h, [&] { as_xnes(h)->inject_normals(z, count); });
+    return guarded(h, [&] { engine_of<bbo::XnesEngine>(h)->inject_normals(z, count); });
 }
 
 void bbo_amalgam_params_default(bbo_amalgam_params *p)
@@ -767,36 +632,24 @@ void bbo_amalgam_params_default(bbo_amalgam_params *p)
     p->substream = 0;
 }
 
-namespace {
-bbo::AmalgamEngine* as_amalgam(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::AmalgamEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an AMALGAM handle");
-    return e;
-}
-}
-
 int bbo_amalgam_configure(bbo_handle h, const bbo_amalgam_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_amalgam_configure: NULL parameters");
-        as_amalgam(h)->configure(*p);
-    });
+    return configure_of<bbo::AmalgamEngine>(h, p, "bbo_amalgam_configure");
 }
 
 int bbo_amalgam_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_amalgam(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::AmalgamEngine>(h)->phase(phase); });
 }
 
 int bbo_amalgam_inject_draws(bbo_handle h, const double *z, int zcount, const int *rows, int rcount)
 {
-    return guarded(h, [&] { as_amalgam(h)->inject_draws(z, zcount, rows, rcount); });
+    return guarded(h, [&] { engine_of<bbo::AmalgamEngine>(h)->inject_draws(z, zcount, rows, rcount); });
 }
 
 int bbo_amalgam_inject_points(bbo_handle h, const double *x, int count)
 {
-    return guarded(h, [&] { as_amalgam(h)->inject_points(x, count); });
+    return guarded(h, [&] { engine_of<bbo::AmalgamEngine>(h)->inject_points(x, count); });
 }
 
 void bbo_slpso_params_default(bbo_slpso_params *p)
@@ -811,31 +664,19 @@ void bbo_slpso_params_default(bbo_slpso_params *p)
     p->Ufmax = 10.;
 }
 
-namespace {
-bbo::SlpsoEngine* as_slpso(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::SlpsoEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an SLPSO handle");
-    return e;
-}
-}
-
 int bbo_slpso_configure(bbo_handle h, const bbo_slpso_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_slpso_configure: NULL parameters");
-        as_slpso(h)->configure(*p);
-    });
+    return configure_of<bbo::SlpsoEngine>(h, p, "bbo_slpso_configure");
 }
 
 int bbo_slpso_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_slpso(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::SlpsoEngine>(h)->phase(phase); });
 }
 
 int bbo_slpso_inject_draws(bbo_handle h, const double *table, int count)
 {
-    return guarded(h, [&] { as_slpso(h)->inject_draws(table, count); });
+    return guarded(h, [&] { engine_of<bbo::SlpsoEngine>(h)->inject_draws(table, count); });
 }
 
 void bbo_crs_params_default(bbo_crs_params *p)
@@ -845,31 +686,19 @@ void bbo_crs_params_default(bbo_crs_params *p)
     p->repair = 0;
 }
 
-namespace {
-bbo::CrsEngine* as_crs(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::CrsEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not a CRS handle");
-    return e;
-}
-}
-
 int bbo_crs_configure(bbo_handle h, const bbo_crs_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_crs_configure: NULL parameters");
-        as_crs(h)->configure(*p);
-    });
+    return configure_of<bbo::CrsEngine>(h, p, "bbo_crs_configure");
 }
 
 int bbo_crs_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_crs(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::CrsEngine>(h)->phase(phase); });
 }
 
 int bbo_crs_inject_draws(bbo_handle h, const double *table, int count)
 {
-    return guarded(h, [&] { as_crs(h)->inject_draws(table, count); });
+    return guarded(h, [&] { engine_of<bbo::CrsEngine>(h)->inject_draws(table, count); });
 }
 
 void bbo_ssde_params_default(bbo_ssde_params *p)
@@ -884,31 +713,19 @@ void bbo_ssde_params_default(bbo_ssde_params *p)
     p->repaircr = 1;
 }
 
-namespace {
-bbo::SsdeEngine* as_ssde(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::SsdeEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an SSDE handle");
-    return e;
-}
-}
-
 int bbo_ssde_configure(bbo_handle h, const bbo_ssde_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_ssde_configure: NULL parameters");
-        as_ssde(h)->configure(*p);
-    });
+    return configure_of<bbo::SsdeEngine>(h, p, "bbo_ssde_configure");
 }
 
 int bbo_ssde_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_ssde(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::SsdeEngine>(h)->phase(phase); });
 }
 
 int bbo_ssde_inject_draws(bbo_handle h, const double *table, int count)
 {
-    return guarded(h, [&] { as_ssde(h)->inject_draws(table, count); });
+    return guarded(h, [&] { engine_of<bbo::SsdeEngine>(h)->inject_draws(table, count); });
 }
 
 void bbo_acd_params_default(bbo_acd_params *p)
@@ -920,26 +737,14 @@ void bbo_acd_params_default(bbo_acd_params *p)
     p->speculate = 0;
 }
 
-namespace {
-bbo::AcdEngine* as_acd(bbo_handle h)
-{
-    auto *e = dynamic_cast<bbo::AcdEngine*>(h->opt.get());
-    if (!e) throw bbo::Error(BBO_ERR_ARG, "not an ACD handle");
-    return e;
-}
-}
-
 int bbo_acd_configure(bbo_handle h, const bbo_acd_params *p)
 {
-    return guarded(h, [&] {
-        if (!p) throw bbo::Error(BBO_ERR_ARG, "bbo_acd_configure: NULL parameters");
-        as_acd(h)->configure(*p);
-    });
+    return configure_of<bbo::AcdEngine>(h, p, "bbo_acd_configure");
 }
 
 int bbo_acd_phase(bbo_handle h, int phase)
 {
-    return guarded(h, [&] { as_acd(h)->phase(phase); });
+    return guarded(h, [&] { engine_of<bbo::AcdEngine>(h)->phase(phase); });
 }
 
 const char* bbo_last_error(bbo_handle h)

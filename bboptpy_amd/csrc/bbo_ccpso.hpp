@@ -43,6 +43,7 @@ struct CcpDev {
 
 class CcpsoEngine: public Engine<CcpScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a CCPSO handle";
     explicit CcpsoEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

@@ -210,6 +210,7 @@ struct UpdateRoute {
 
 class CmaEngine: public Engine<CmaScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a CMA-ES handle";
     explicit CmaEngine(const bbo_params &p);
     ~CmaEngine() override;
 

@@ -14,7 +14,7 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:crs_init", "bbo:crs_rank", "b
 }
 
 CrsEngine::CrsEngine(const bbo_params &p) :
-        Engine(checked(p))
+        WalkEngine(checked(p), "bbo_crs_phase", true)
 {
     bbo_crs_params_default(&cp_);
 }
@@ -75,7 +75,7 @@ void CrsEngine::init(int n, const double *lower, const double *upper, const doub
     c.stack_words = (cp_.max_depth + 31) / 32;
     c.tol = params_.tol;
     c.seed = params_.seed;
-    mid_iteration_ = false;
+    mid_generation_ = false;
 
     const size_t rows = (size_t) P * np;
     X_.alloc(rows * c.ld);
@@ -136,20 +136,18 @@ void CrsEngine::host_evaluate_pool(int p0, int pcount)
 
 void CrsEngine::launch_init(int p0, int pcount, int mode)
 {
-    timer_.begin(stream_, K_INIT);
-    hipLaunchKernelGGL(crs_init, dim3(pcount, (c_.np + CRS_INIT_ROWS - 1) / CRS_INIT_ROWS), dim3(256), 0, stream_,
-            d_, c_, p0, mode);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_INIT, [&] {
+        hipLaunchKernelGGL(crs_init, dim3(pcount, (c_.np + CRS_INIT_ROWS - 1) / CRS_INIT_ROWS), dim3(256), 0, stream_,
+                d_, c_, p0, mode);
+    });
 }
 
 void CrsEngine::launch_rank(int p0, int pcount)
 {
-    timer_.begin(stream_, K_RANK);
-    hipLaunchKernelGGL(crs_rank, dim3(pcount, (c_.np + CRS_RANK_CANDS - 1) / CRS_RANK_CANDS), dim3(256), 0, stream_,
-            d_, c_, p0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] {
+        hipLaunchKernelGGL(crs_rank, dim3(pcount, (c_.np + CRS_RANK_CANDS - 1) / CRS_RANK_CANDS), dim3(256), 0, stream_,
+                d_, c_, p0);
+    });
 }
 
 void CrsEngine::launch_body(int mode, int k, bool begin)
@@ -157,51 +155,18 @@ void CrsEngine::launch_body(int mode, int k, bool begin)
     const int b = begin ? 1 : 0;
     const size_t bytes = (size_t) 4 * c_.ld * sizeof(double) + (size_t) round_up(c_.n, 4) * sizeof(int);
     c_.launch_evals = launch_evals(k);
-    timer_.begin(stream_, K_STEPS);
-    switch (workgroup()) {
-    case 64: hipLaunchKernelGGL((crs_steps<64>), dim3(c_.npop), dim3(64), bytes, stream_, d_, c_, mode, k, b); break;
-    case 128: hipLaunchKernelGGL((crs_steps<128>), dim3(c_.npop), dim3(128), bytes, stream_, d_, c_, mode, k, b); break;
-    default: hipLaunchKernelGGL((crs_steps<256>), dim3(c_.npop), dim3(256), bytes, stream_, d_, c_, mode, k, b); break;
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_STEPS, [&] {
+        switch (workgroup()) {
+        case 64: hipLaunchKernelGGL((crs_steps<64>), dim3(c_.npop), dim3(64), bytes, stream_, d_, c_, mode, k, b); break;
+        case 128: hipLaunchKernelGGL((crs_steps<128>), dim3(c_.npop), dim3(128), bytes, stream_, d_, c_, mode, k, b); break;
+        default: hipLaunchKernelGGL((crs_steps<256>), dim3(c_.npop), dim3(256), bytes, stream_, d_, c_, mode, k, b); break;
+        }
+    });
 }
 
-// the value of every population's pending point
-void CrsEngine::launch_eval()
+void CrsEngine::launch_eval_device()
 {
-    if (!obj_.needs_host()) {
-        timer_.begin(stream_, K_EVAL);
-        hipLaunchKernelGGL(crs_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-        return;
-    }
-    // one row per population that has one pending, in population order: the callable is called
-    // exactly fev times
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int P = c_.npop;
-    std::vector<CrsScal> sc(P);
-    scal_.download(sc.data(), P);
-    std::vector<double> xh(c_.ld);
-    for (int p = 0; p < P; p++) {
-        if (!sc[p].pending || (c_.honor_stop && sc[p].stop)) continue;
-        (sc[p].stage == CRS_WAIT_MUT ? cand2_ : cand_).download(xh.data(), c_.ld, (size_t) p * c_.ld);
-        double f = 0.;
-        obj_.eval_host(xh.data(), 1, c_.n, c_.ld, &f);
-        nan_to_inf(&f, 1);
-        value_.upload(&f, 1, p);
-    }
-}
-
-bool CrsEngine::any_pending()
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<CrsScal> sc(c_.npop);
-    scal_.download(sc.data(), sc.size());
-    for (const auto &s : sc)
-        if (s.pending && !(c_.honor_stop && s.stop)) return true;
-    return false;
+    timed(K_EVAL, [&] { hipLaunchKernelGGL(crs_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 // k iterations of every population with a device objective: launches of bounded length until no
@@ -218,22 +183,11 @@ void CrsEngine::fused(int k)
     }
 }
 
-// one iterate() of every population; with a host objective the same body from evaluation to evaluation,
-// every round one row per population that still has one
-void CrsEngine::generation(bool honor_stop)
+// one iteration of every population (CRS_FUSED), or the same body from evaluation to evaluation
+void CrsEngine::launch_walk(int mode, bool begin)
 {
-    c_.honor_stop = honor_stop ? 1 : 0;
-    if (!obj_.needs_host()) {
-        fused(1);
-        mid_iteration_ = false;
-        return;
-    }
-    launch_body(CRS_ADVANCE, 1, !mid_iteration_);
-    while (any_pending()) {
-        launch_eval();
-        launch_body(CRS_ABSORB, 1, false);
-    }
-    mid_iteration_ = false;
+    if (mode == CRS_FUSED) fused(1);
+    else launch_body(mode, 1, begin);
 }
 
 // bbo_run: `gens` whole iterations per population
@@ -245,7 +199,7 @@ void CrsEngine::launch_chunk(int gens)
     }
     c_.honor_stop = 1;
     fused(gens);
-    mid_iteration_ = false;
+    mid_generation_ = false;
 }
 
 // bbo_run cannot wait for a table: an exhausted one ends it
@@ -253,26 +207,6 @@ void CrsEngine::inspect(const std::vector<CrsScal> &sc)
 {
     for (const auto &s : sc)
         if (s.starved) throw Error(BBO_ERR_STATE, "bbo_run: the injected draws are exhausted (bbo_crs_inject_draws)");
-}
-
-void CrsEngine::phase(int which)
-{
-    enter("bbo_crs_phase");
-    BBO_REQUIRE(which >= 0 && which <= 2, "bbo_crs_phase: 0 advance, 1 evaluate, 2 absorb");
-    c_.honor_stop = 0;
-    if (which == 0) {
-        // the first advance of an iteration starts it in every population; the later ones leave a
-        // population that has completed it alone until none has a point pending
-        launch_body(CRS_ADVANCE, 1, !mid_iteration_);
-        mid_iteration_ = any_pending();
-    } else if (which == 1) {
-        launch_eval();
-    } else {
-        launch_body(CRS_ABSORB, 1, false);
-        mid_iteration_ = any_pending();
-    }
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
 }
 
 void CrsEngine::inject_draws(const double *table, int count)
@@ -324,7 +258,7 @@ void CrsEngine::reset_walk(int p)
     s.starved = 0;
     s.conv = std::fabs(s.fbest - s.fworst) < c_.tol ? 1 : 0;
     scal_.upload(&s, 1, p);
-    if (c_.npop == 1) mid_iteration_ = false;
+    if (c_.npop == 1) mid_generation_ = false;
 }
 
 void CrsEngine::solution(int population, double *x_out, int *n_evals, int *converged)

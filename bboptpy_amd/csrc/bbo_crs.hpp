@@ -52,9 +52,8 @@ enum CrsStage {
 
 // what a launch of the body does
 enum CrsMode {
-    CRS_FUSED = 0,           // whole iterations, the evaluations inside
-    CRS_ADVANCE,             // up to the next pending evaluation (phase 0)
-    CRS_ABSORB               // take the value of the pending evaluation, then advance (phase 2)
+    CRS_FUSED = WALK_FUSED, CRS_ADVANCE = WALK_ADVANCE,
+    CRS_ABSORB = WALK_ABSORB // take the value of the pending evaluation, then advance (phase 2)
 };
 
 struct CrsScal {
@@ -100,8 +99,9 @@ struct CrsDev {
     CrsScal *scal;
 };
 
-class CrsEngine: public Engine<CrsScal> {
+class CrsEngine: public WalkEngine<CrsScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a CRS handle";
     explicit CrsEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
@@ -111,25 +111,28 @@ public:
     int dimension() const override { return c_.n; }
 
     void configure(const bbo_crs_params &cp);
-    // bbo_crs_phase: 0 advance to the next pending evaluation, 1 evaluate, 2 absorb
-    void phase(int which);
     // bbo_crs_inject_draws: [P][records][2 n] (n row indices, n uniforms)
     void inject_draws(const double *table, int count);
 
 private:
     static const bbo_params &checked(const bbo_params &p);
-    void generation(bool honor_stop) override;
+    void launch_walk(int mode, bool begin) override;
+    void launch_eval_device() override;
+    // the point of stage 2 (the mutation) waits in cand2
+    PendingPoints pending_points(int p, const CrsScal &s) override
+    {
+        return { s.stage == CRS_WAIT_MUT ? &cand2_ : &cand_, (size_t) p * c_.ld, 1, c_.ld, &value_ };
+    }
+    int &honor_stop() override { return c_.honor_stop; }
     void launch_chunk(int gens) override;
     void inspect(const std::vector<CrsScal> &sc) override;
     int default_poll() const override { return CRS_DEFAULT_CHUNK; }
     void launch_init(int p0, int pcount, int mode);
     void launch_rank(int p0, int pcount);
     void launch_body(int mode, int k, bool begin);
-    void launch_eval();
     void fused(int k);
     void host_evaluate_pool(int p0, int pcount);
     void reset_walk(int p);
-    bool any_pending();
     int workgroup() const;
     int launch_evals(int k) const;
 
@@ -140,7 +143,6 @@ private:
     DevBuf<int> order_, more_;
     DevBuf<uint32_t> stack_;
     int launch_evals_ = 0;           // bbo_set "launch_evals": 0 = CRS_LAUNCH_STEPS_PER_ITERATION per iteration
-    bool mid_iteration_ = false;     // bbo_crs_phase: some population has a point pending
 };
 
 } // namespace bbo

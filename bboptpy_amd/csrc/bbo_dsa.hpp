@@ -67,6 +67,7 @@ struct DsaDev {
 
 class DsaEngine: public Engine<DsaScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a DSA handle";
     explicit DsaEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

@@ -2,7 +2,8 @@
 // box and the objective's table in HBM, the guards of the entry points, and iterate() / run() /
 // optimize() as template methods over a handful of hooks.  An engine derives from Engine<its
 // per-population scalars>, writes init / generation / solution / get / set around its kernels and
-// overrides a hook only where its reference's loop differs (host side).
+// overrides a hook only where its reference's loop differs (host side).  The engines whose
+// generation is a walk from evaluation to evaluation derive from WalkEngine, below.
 #pragma once
 
 #include "bbo_common.hpp"
@@ -140,7 +141,59 @@ inline void require_record(bool record, const std::string &k)
     if (!record) throw Error(BBO_ERR_STATE, "'" + k + "' needs record_draws");
 }
 
-// Scal: the engine's per-population scalars; the base reads its `stop`, `fev` and `conv`.
+// set() of a permutation of 0 .. count - 1 that arrives as doubles; `what` is the caller's message
+inline std::vector<int> permutation_of(const double *in, int count, const char *what)
+{
+    std::vector<int> perm(count);
+    std::vector<char> seen(count, 0);
+    for (int q = 0; q < count; q++) {
+        BBO_REQUIRE(in[q] >= 0. && in[q] < count && in[q] == std::floor(in[q]) && !seen[(int) in[q]], what);
+        seen[(int) in[q]] = 1;
+        perm[q] = (int) in[q];
+    }
+    return perm;
+}
+
+// The two tables of an engine whose draws can be replayed: the one the caller injects instead of the
+// generator and the one the kernels record into.  Both have the engine's one table length.
+struct DrawTables {
+    DevBuf<double> inject, draws;
+
+    void clear()
+    {
+        inject.alloc(0);
+        draws.alloc(0);
+    }
+    // the caller's table (checked by the engine) in HBM; returns what the kernels read
+    const double *load(const double *table, size_t want)
+    {
+        if (!inject.p) inject.alloc(want);
+        inject.upload(table, want);
+        return inject.p;
+    }
+    // set("record_draws"): where the kernels record, null when off
+    double *record(bool on, size_t len)
+    {
+        if (on && !draws.p) {
+            draws.alloc(len);
+            std::vector<double> z(len, 0.);
+            draws.upload(z.data(), len);
+        }
+        return on ? draws.p : nullptr;
+    }
+};
+
+// What a population has pending for a host objective: `count` points, rows of ld doubles from
+// cand[off] on, whose values go to value[p * count ...].
+struct PendingPoints {
+    const DevBuf<double> *cand;
+    size_t off;
+    int count, ld;
+    DevBuf<double> *value;
+};
+
+// Scal: the engine's per-population scalars; the base reads its `stop`, `fev` and `conv` (and
+// `pending`, in the engines that call host_evaluate_pending).
 template<class Scal>
 class Engine: public Optimizer {
 public:
@@ -347,6 +400,40 @@ protected:
         }
     }
 
+    // A host objective over the points the populations have pending (Scal::pending), in population
+    // order, each point one call of eval_host: the callable is called exactly `fev` times.  `points`
+    // (p, scalars of p) names them; a stopped population is left out under honor_stop.
+    template<class Points>
+    void host_evaluate_pending(bool honor_stop, Points points)
+    {
+        BBO_HIP(hipStreamSynchronize(stream_));
+        const int P = params_.populations, n = dimension();
+        std::vector<Scal> sc(P);
+        scal_.download(sc.data(), P);
+        std::vector<double> xh, fh;
+        for (int p = 0; p < P; p++) {
+            if (!sc[p].pending || (honor_stop && sc[p].stop)) continue;
+            const PendingPoints pt = points(p, sc[p]);
+            xh.resize((size_t) pt.count * pt.ld);
+            fh.assign(pt.count, 0.);
+            pt.cand->download(xh.data(), xh.size(), pt.off);
+            for (int i = 0; i < pt.count; i++)
+                obj_.eval_host(xh.data() + (size_t) i * pt.ld, 1, n, pt.ld, &fh[i]);
+            nan_to_inf(fh.data(), pt.count);
+            pt.value->upload(fh.data(), pt.count, (size_t) p * pt.count);
+        }
+    }
+
+    // one kernel launch in its slot of get("profile"): `launch` holds the hipLaunchKernelGGL
+    template<class Launch>
+    void timed(int slot, Launch launch)
+    {
+        timer_.begin(stream_, slot);
+        launch();
+        timer_.end(stream_);
+        BBO_HIP(hipGetLastError());
+    }
+
     bool all_stopped()
     {
         std::vector<Scal> sc(params_.populations);
@@ -377,6 +464,98 @@ protected:
     std::vector<double> lower_h_, upper_h_, aux_h_;
     DevBuf<double> lower_, upper_, aux_;
     DevBuf<Scal> scal_;
+};
+
+// the modes of a walk kernel (the engines' own enums name the same values for their kernels)
+enum WalkMode {
+    WALK_FUSED = 0,          // a whole generation, the evaluations inside
+    WALK_ADVANCE,            // up to the next pending evaluation (phase 0)
+    WALK_ABSORB              // take the value of the pending evaluation (phase 2)
+};
+
+// The engines whose generation is one workgroup's walk per population (SLPSO, CRS, SSDE): with a
+// device objective one fused launch, with a host objective the same walk entered and left at its
+// evaluations, every round one point per population that still has one pending.  The layer owns that
+// loop, the same steps one at a time (phase) and the flag that says a generation is under way.
+template<class Scal>
+class WalkEngine: public Engine<Scal> {
+public:
+    // bbo_<engine>_phase: 0 advance to the next pending evaluation, 1 evaluate, 2 absorb
+    void phase(int which)
+    {
+        this->enter(phase_fn_);
+        BBO_REQUIRE(which >= 0 && which <= 2, std::string(phase_fn_) + ": 0 advance, 1 evaluate, 2 absorb");
+        honor_stop() = 0;
+        if (which == 0) {
+            // the first advance of a generation starts it in every population; the later ones leave a
+            // population that has completed it alone until none has a point pending
+            launch_walk(WALK_ADVANCE, !mid_generation_);
+            mid_generation_ = any_pending();
+        } else if (which == 1) {
+            launch_eval();
+        } else {
+            launch_walk(WALK_ABSORB, false);
+            if (absorb_advances_) mid_generation_ = any_pending();
+        }
+        BBO_HIP(hipStreamSynchronize(this->stream_));
+        this->timer_.collect();
+    }
+
+protected:
+    // absorb_advances: the kernel's WALK_ABSORB walks on to the next pending point itself (CRS)
+    WalkEngine(const bbo_params &p, const char *phase_fn, bool absorb_advances) :
+            Engine<Scal>(p), phase_fn_(phase_fn), absorb_advances_(absorb_advances)
+    {
+    }
+
+    // ---- the hooks ----------------------------------------------------------------------------
+    // one launch of the walk in every population (WALK_FUSED: whole, whatever launches that takes);
+    // `begin`: an idle population starts its next generation
+    virtual void launch_walk(int mode, bool begin) = 0;
+    // the device objective at every population's pending point
+    virtual void launch_eval_device() = 0;
+    virtual PendingPoints pending_points(int p, const Scal &s) = 0;
+    // the kernels' copy of the flag: a stopped population takes no further generation
+    virtual int &honor_stop() = 0;
+
+    void generation(bool honor) override
+    {
+        honor_stop() = honor ? 1 : 0;
+        if (!this->obj_.needs_host()) {
+            launch_walk(WALK_FUSED, true);
+        } else {
+            launch_walk(WALK_ADVANCE, !mid_generation_);
+            while (any_pending()) {
+                launch_eval();
+                launch_walk(WALK_ABSORB, false);
+                if (!absorb_advances_) launch_walk(WALK_ADVANCE, false);
+            }
+        }
+        mid_generation_ = false;
+    }
+
+    bool mid_generation_ = false;    // phase(): some population has a point pending
+
+private:
+    // the value of every population's pending point
+    void launch_eval()
+    {
+        if (!this->obj_.needs_host()) launch_eval_device();
+        else this->host_evaluate_pending(honor_stop() != 0, [this](int p, const Scal &s) { return pending_points(p, s); });
+    }
+
+    bool any_pending()
+    {
+        BBO_HIP(hipStreamSynchronize(this->stream_));
+        std::vector<Scal> sc(this->params_.populations);
+        this->scal_.download(sc.data(), sc.size());
+        for (const auto &s : sc)
+            if (s.pending && !(honor_stop() && s.stop)) return true;
+        return false;
+    }
+
+    const char *phase_fn_;
+    const bool absorb_advances_;
 };
 
 } // namespace bbo

@@ -74,6 +74,7 @@ struct HeesDev {
 
 class HeesEngine: public Engine<HeesScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a HEES handle";
     explicit HeesEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

@@ -62,6 +62,7 @@ struct JayaDev {
 
 class JayaEngine: public Engine<JayaScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a JAYA handle";
     explicit JayaEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

@@ -69,6 +69,7 @@ struct LmDev {
 
 class LmEngine: public Engine<LmScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an LmCMAES handle";
     explicit LmEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

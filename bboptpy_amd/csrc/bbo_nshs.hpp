@@ -71,6 +71,7 @@ struct NshsDev {
 
 class NshsEngine: public Engine<NshsScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an NSHS handle";
     explicit NshsEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

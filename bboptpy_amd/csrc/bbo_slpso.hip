@@ -14,7 +14,7 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:slpso_init", "bbo:slpso_gener
 }
 
 SlpsoEngine::SlpsoEngine(const bbo_params &p) :
-        Engine(checked(p))
+        WalkEngine(checked(p), "bbo_slpso_phase", false)
 {
     bbo_slpso_params_default(&sp_);
 }
@@ -85,8 +85,7 @@ void SlpsoEngine::init(int n, const double *lower, const double *upper, const do
     m_.alloc(rows); CF_.alloc(rows); PF_.alloc(rows); perm_.alloc(rows);
     abest_.alloc((size_t) P * c.ld); vdavg_.alloc((size_t) P * c.ld); cand_.alloc((size_t) P * c.ld);
     fcand_.alloc(P);
-    draws_.alloc(0);
-    inject_.alloc(0);
+    tables_.clear();
     scal_.alloc(P);
     upload_box(n, c.ld, lower, upper, obj);
     {
@@ -149,100 +148,27 @@ void SlpsoEngine::host_evaluate_swarm(int p0, int pcount)
 
 void SlpsoEngine::launch_init(int p0, int pcount, int mode)
 {
-    timer_.begin(stream_, K_INIT);
-    hipLaunchKernelGGL(slpso_init, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, mode);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_INIT, [&] { hipLaunchKernelGGL(slpso_init, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, mode); });
 }
 
-void SlpsoEngine::launch_body(int mode, bool begin)
+// one iterate() of every population (SLPSO_FUSED), or the same body from evaluation to evaluation
+void SlpsoEngine::launch_walk(int mode, bool begin)
 {
     const int b = begin ? 1 : 0;
     const int T = workgroup(), W = T / 64;
     const size_t bytes = (size_t) (5 + (W > 1 ? W : 0)) * c_.ld * sizeof(double) + (size_t) c_.ld * sizeof(int);
-    timer_.begin(stream_, K_GENERATION);
-    switch (T) {
-    case 64: hipLaunchKernelGGL((slpso_generation<64>), dim3(c_.npop), dim3(64), bytes, stream_, d_, c_, mode, b); break;
-    case 128: hipLaunchKernelGGL((slpso_generation<128>), dim3(c_.npop), dim3(128), bytes, stream_, d_, c_, mode, b); break;
-    default: hipLaunchKernelGGL((slpso_generation<256>), dim3(c_.npop), dim3(256), bytes, stream_, d_, c_, mode, b); break;
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_GENERATION, [&] {
+        switch (T) {
+        case 64: hipLaunchKernelGGL((slpso_generation<64>), dim3(c_.npop), dim3(64), bytes, stream_, d_, c_, mode, b); break;
+        case 128: hipLaunchKernelGGL((slpso_generation<128>), dim3(c_.npop), dim3(128), bytes, stream_, d_, c_, mode, b); break;
+        default: hipLaunchKernelGGL((slpso_generation<256>), dim3(c_.npop), dim3(256), bytes, stream_, d_, c_, mode, b); break;
+        }
+    });
 }
 
-// the value of every population's pending point
-void SlpsoEngine::launch_eval()
+void SlpsoEngine::launch_eval_device()
 {
-    if (!obj_.needs_host()) {
-        timer_.begin(stream_, K_EVAL);
-        hipLaunchKernelGGL(slpso_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-        return;
-    }
-    // one row per population that has one pending, in population order: the callable is called
-    // exactly fev times
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int P = c_.npop;
-    std::vector<SlpsoScal> sc(P);
-    scal_.download(sc.data(), P);
-    std::vector<double> xh(c_.ld);
-    for (int p = 0; p < P; p++) {
-        if (!sc[p].pending || (c_.honor_stop && sc[p].stop)) continue;
-        cand_.download(xh.data(), c_.ld, (size_t) p * c_.ld);
-        double f = 0.;
-        obj_.eval_host(xh.data(), 1, c_.n, c_.ld, &f);
-        nan_to_inf(&f, 1);
-        fcand_.upload(&f, 1, p);
-    }
-}
-
-bool SlpsoEngine::any_pending()
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<SlpsoScal> sc(c_.npop);
-    scal_.download(sc.data(), sc.size());
-    for (const auto &s : sc)
-        if (s.pending && !(c_.honor_stop && s.stop)) return true;
-    return false;
-}
-
-// one iterate() of every population: one launch with a device objective; with a host objective the
-// same body from evaluation to evaluation, every round one row per population that still has one
-void SlpsoEngine::generation(bool honor_stop)
-{
-    c_.honor_stop = honor_stop ? 1 : 0;
-    if (!obj_.needs_host()) {
-        launch_body(SLPSO_FUSED);
-        mid_generation_ = false;
-        return;
-    }
-    for (bool begin = !mid_generation_;; begin = false) {
-        launch_body(SLPSO_ADVANCE, begin);
-        if (!any_pending()) break;
-        launch_eval();
-        launch_body(SLPSO_ABSORB);
-    }
-    mid_generation_ = false;
-}
-
-void SlpsoEngine::phase(int which)
-{
-    enter("bbo_slpso_phase");
-    BBO_REQUIRE(which >= 0 && which <= 2, "bbo_slpso_phase: 0 advance, 1 evaluate, 2 absorb");
-    c_.honor_stop = 0;
-    if (which == 0) {
-        // the first advance of a generation starts it in every population; the later ones leave a
-        // population that has completed it alone until none has a point pending
-        launch_body(SLPSO_ADVANCE, !mid_generation_);
-        mid_generation_ = any_pending();
-    } else if (which == 1) {
-        launch_eval();
-    } else {
-        launch_body(SLPSO_ABSORB);
-    }
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    timed(K_EVAL, [&] { hipLaunchKernelGGL(slpso_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 void SlpsoEngine::inject_draws(const double *table, int count)
@@ -258,17 +184,10 @@ void SlpsoEngine::inject_draws(const double *table, int count)
     BBO_REQUIRE(count >= 0 && (size_t) count == want,
             "bbo_slpso_inject_draws: populations * (1 + np + np * (3 + 4 n)) values");
     auto unit = [](double u) { return u >= 0. && u < 1.; };
-    std::vector<char> seen(np);
     for (int p = 0; p < c_.npop; p++) {
         const double *t = table + (size_t) p * len;
         BBO_REQUIRE(unit(t[0]), "bbo_slpso_inject_draws: uniforms lie in [0, 1)");
-        std::fill(seen.begin(), seen.end(), 0);
-        for (int q = 0; q < np; q++) {
-            const double v = t[1 + q];
-            BBO_REQUIRE(v >= 0. && v < np && v == std::floor(v) && !seen[(int) v],
-                    "bbo_slpso_inject_draws: perm is a permutation of 0 .. np - 1");
-            seen[(int) v] = 1;
-        }
+        permutation_of(t + 1, np, "bbo_slpso_inject_draws: perm is a permutation of 0 .. np - 1");
         for (int k = 0; k < np; k++) {
             const double *st = t + 1 + np + (size_t) k * (3 + 4 * (size_t) n);
             BBO_REQUIRE(unit(st[0]) && unit(st[1]) && unit(st[2]), "bbo_slpso_inject_draws: uniforms lie in [0, 1)");
@@ -279,9 +198,7 @@ void SlpsoEngine::inject_draws(const double *table, int count)
             }
         }
     }
-    if (!inject_.p) inject_.alloc(want);
-    inject_.upload(table, want);
-    d_.inject = inject_.p;
+    d_.inject = tables_.load(table, want);
 }
 
 void SlpsoEngine::solution(int population, double *x_out, int *n_evals, int *converged)
@@ -323,7 +240,7 @@ int SlpsoEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "fcand") return o.vec(fcand_, p, 1);
     if (k == "draws") {
         require_record(c.record, k);
-        return o.vec(draws_, (size_t) p * table_len(), (int) table_len());
+        return o.vec(tables_.draws, (size_t) p * table_len(), (int) table_len());
     }
     if (k == "fabest") return o.one(s.fabest);
     if (k == "alpha") return o.one(s.alpha);
@@ -357,12 +274,7 @@ int SlpsoEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "record_draws") {      // (the whole handle: every population)
         BBO_REQUIRE(count == 1, "record_draws: one value");
         c_.record = in[0] != 0. ? 1 : 0;
-        if (c_.record && !draws_.p) {
-            draws_.alloc((size_t) c.npop * table_len());
-            std::vector<double> z((size_t) c.npop * table_len(), 0.);
-            draws_.upload(z.data(), z.size());
-        }
-        d_.draws = c_.record ? draws_.p : nullptr;
+        d_.draws = tables_.record(c_.record, (size_t) c.npop * table_len());
         return 1;
     }
     if (k == "dbg") {
@@ -400,15 +312,7 @@ int SlpsoEngine::set(const std::string &k, int p, const double *in, int count)
     }
     if (k == "perm") {          // Uf and Pl follow
         BBO_REQUIRE(count == c.np, "perm: np values");
-        std::vector<int> perm(c.np);
-        std::vector<char> seen(c.np, 0);
-        for (int q = 0; q < c.np; q++) {
-            BBO_REQUIRE(in[q] >= 0. && in[q] < c.np && in[q] == std::floor(in[q]) && !seen[(int) in[q]],
-                    "perm: a permutation of 0 .. np - 1");
-            seen[(int) in[q]] = 1;
-            perm[q] = (int) in[q];
-        }
-        perm_.upload(perm.data(), c.np, pr);
+        perm_.upload(permutation_of(in, c.np, "perm: a permutation of 0 .. np - 1").data(), c.np, pr);
         launch_init(p, 1, SLPSO_INIT_PAR);
         BBO_HIP(hipStreamSynchronize(stream_));
         return count;

@@ -33,9 +33,7 @@ enum SlpsoStage {
 
 // what a launch of the body does
 enum SlpsoMode {
-    SLPSO_FUSED = 0,         // a whole generation, the evaluations inside
-    SLPSO_ADVANCE,           // up to the next pending evaluation (phase 0)
-    SLPSO_ABSORB             // take the value of the pending evaluation (phase 2)
+    SLPSO_FUSED = WALK_FUSED, SLPSO_ADVANCE = WALK_ADVANCE, SLPSO_ABSORB = WALK_ABSORB
 };
 
 struct SlpsoScal {
@@ -74,8 +72,9 @@ struct SlpsoDev {
     SlpsoScal *scal;
 };
 
-class SlpsoEngine: public Engine<SlpsoScal> {
+class SlpsoEngine: public WalkEngine<SlpsoScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an SLPSO handle";
     explicit SlpsoEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
@@ -85,28 +84,25 @@ public:
     int dimension() const override { return c_.n; }
 
     void configure(const bbo_slpso_params &sp);
-    // bbo_slpso_phase: 0 advance to the next pending evaluation, 1 evaluate, 2 absorb
-    void phase(int which);
     void inject_draws(const double *table, int count);
 
 private:
     static const bbo_params &checked(const bbo_params &p);
-    void generation(bool honor_stop) override;
+    void launch_walk(int mode, bool begin) override;
+    void launch_eval_device() override;
+    PendingPoints pending_points(int p, const SlpsoScal&) override { return { &cand_, (size_t) p * c_.ld, 1, c_.ld, &fcand_ }; }
+    int &honor_stop() override { return c_.honor_stop; }
     void launch_init(int p0, int pcount, int mode);
-    void launch_body(int mode, bool begin = true);
-    void launch_eval();
     void host_evaluate_swarm(int p0, int pcount);
-    bool any_pending();
     int workgroup() const;
     size_t table_len() const { return 1 + (size_t) c_.np + (size_t) c_.np * (3 + 4 * (size_t) c_.n); }
 
     bbo_slpso_params sp_ {};
     SlpsoConst c_ {};
     SlpsoDev d_ {};
-    DevBuf<double> x_, v_, pb_, fx_, fpb_, fp_, Uf_, Pl_, s_, p_, abest_, vdavg_, cand_, fcand_, radius_, draws_,
-            inject_, Uf_tab_, Pl_tab_;
+    DevBuf<double> x_, v_, pb_, fx_, fpb_, fp_, Uf_, Pl_, s_, p_, abest_, vdavg_, cand_, fcand_, radius_, Uf_tab_, Pl_tab_;
     DevBuf<int> g_, G_, m_, CF_, PF_, perm_;
-    bool mid_generation_ = false;    // bbo_slpso_phase: some population has a point pending
+    DrawTables tables_;
 };
 
 } // namespace bbo

@@ -64,6 +64,7 @@ struct SpiralDev {
 
 class SpiralEngine: public Engine<SpiralScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not a SpiralSearch handle";
     explicit SpiralEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

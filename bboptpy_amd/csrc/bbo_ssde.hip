@@ -14,7 +14,7 @@ static const char *const K_NAMES[K_COUNT] = { "bbo:ssde_init", "bbo:ssde_generat
 }
 
 SsdeEngine::SsdeEngine(const bbo_params &p) :
-        Engine(checked(p))
+        WalkEngine(checked(p), "bbo_ssde_phase", false)
 {
     bbo_ssde_params_default(&sp_);
 }
@@ -89,8 +89,7 @@ void SsdeEngine::init(int n, const double *lower, const double *upper, const dou
     SR_.alloc(mem); SC_.alloc(mem); w_.alloc(mem); SCR_.alloc(mem); wCR_.alloc(mem); radius_.alloc(mem);
     perm_.alloc((size_t) P * c.ld); cand_.alloc((size_t) P * c.ld);
     fcand_.alloc(P);
-    draws_.alloc(0);
-    inject_.alloc(0);
+    tables_.clear();
     scal_.alloc(P);
     upload_box(n, c.ld, lower, upper, obj);
     {
@@ -143,100 +142,26 @@ void SsdeEngine::host_evaluate_rows_of(int p0, int pcount, int r0, int r1)
 
 void SsdeEngine::launch_init(int p0, int pcount, int mode, int r0, int r1)
 {
-    timer_.begin(stream_, K_INIT);
-    hipLaunchKernelGGL(ssde_init, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, mode, r0, r1);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_INIT, [&] { hipLaunchKernelGGL(ssde_init, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, mode, r0, r1); });
 }
 
-void SsdeEngine::launch_body(int mode, bool begin)
+// one iterate() of every population (SSDE_FUSED), or the same body from evaluation to evaluation
+void SsdeEngine::launch_walk(int mode, bool begin)
 {
     const int b = begin ? 1 : 0;
-    const int T = workgroup();
     const size_t bytes = (size_t) 5 * c_.ld * sizeof(double) + (size_t) 2 * c_.ld * sizeof(int);
-    timer_.begin(stream_, K_GENERATION);
-    switch (T) {
-    case 64: hipLaunchKernelGGL((ssde_generation<64>), dim3(c_.npop), dim3(64), bytes, stream_, d_, c_, mode, b); break;
-    case 128: hipLaunchKernelGGL((ssde_generation<128>), dim3(c_.npop), dim3(128), bytes, stream_, d_, c_, mode, b); break;
-    default: hipLaunchKernelGGL((ssde_generation<256>), dim3(c_.npop), dim3(256), bytes, stream_, d_, c_, mode, b); break;
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_GENERATION, [&] {
+        switch (workgroup()) {
+        case 64: hipLaunchKernelGGL((ssde_generation<64>), dim3(c_.npop), dim3(64), bytes, stream_, d_, c_, mode, b); break;
+        case 128: hipLaunchKernelGGL((ssde_generation<128>), dim3(c_.npop), dim3(128), bytes, stream_, d_, c_, mode, b); break;
+        default: hipLaunchKernelGGL((ssde_generation<256>), dim3(c_.npop), dim3(256), bytes, stream_, d_, c_, mode, b); break;
+        }
+    });
 }
 
-// the value of every population's pending point
-void SsdeEngine::launch_eval()
+void SsdeEngine::launch_eval_device()
 {
-    if (!obj_.needs_host()) {
-        timer_.begin(stream_, K_EVAL);
-        hipLaunchKernelGGL(ssde_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
-        return;
-    }
-    // one row per population that has one pending, in population order: the callable is called
-    // exactly fev times
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int P = c_.npop;
-    std::vector<SsdeScal> sc(P);
-    scal_.download(sc.data(), P);
-    std::vector<double> xh(c_.ld);
-    for (int p = 0; p < P; p++) {
-        if (!sc[p].pending || (c_.honor_stop && sc[p].stop)) continue;
-        cand_.download(xh.data(), c_.ld, (size_t) p * c_.ld);
-        double f = 0.;
-        obj_.eval_host(xh.data(), 1, c_.n, c_.ld, &f);
-        nan_to_inf(&f, 1);
-        fcand_.upload(&f, 1, p);
-    }
-}
-
-bool SsdeEngine::any_pending()
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<SsdeScal> sc(c_.npop);
-    scal_.download(sc.data(), sc.size());
-    for (const auto &s : sc)
-        if (s.pending && !(c_.honor_stop && s.stop)) return true;
-    return false;
-}
-
-// one iterate() of every population: one launch with a device objective; with a host objective the
-// same body from evaluation to evaluation, every round one row per population that still has one
-void SsdeEngine::generation(bool honor_stop)
-{
-    c_.honor_stop = honor_stop ? 1 : 0;
-    if (!obj_.needs_host()) {
-        launch_body(SSDE_FUSED);
-        mid_generation_ = false;
-        return;
-    }
-    for (bool begin = !mid_generation_;; begin = false) {
-        launch_body(SSDE_ADVANCE, begin);
-        if (!any_pending()) break;
-        launch_eval();
-        launch_body(SSDE_ABSORB);
-    }
-    mid_generation_ = false;
-}
-
-void SsdeEngine::phase(int which)
-{
-    enter("bbo_ssde_phase");
-    BBO_REQUIRE(which >= 0 && which <= 2, "bbo_ssde_phase: 0 advance, 1 evaluate, 2 absorb");
-    c_.honor_stop = 0;
-    if (which == 0) {
-        // the first advance of a generation starts it in every population; the later ones leave a
-        // population that has completed it alone until none has a point pending
-        launch_body(SSDE_ADVANCE, !mid_generation_);
-        mid_generation_ = any_pending();
-    } else if (which == 1) {
-        launch_eval();
-    } else {
-        launch_body(SSDE_ABSORB);
-    }
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    timed(K_EVAL, [&] { hipLaunchKernelGGL(ssde_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 void SsdeEngine::inject_draws(const double *table, int count)
@@ -253,14 +178,9 @@ void SsdeEngine::inject_draws(const double *table, int count)
             "bbo_ssde_inject_draws: populations * (n + npinit * (9 + 3 n)) values");
     auto unit = [](double u) { return u >= 0. && u < 1.; };
     auto index = [](double v, int below) { return v >= 0. && v < below && v == std::floor(v); };
-    std::vector<char> seen(n);
     for (int p = 0; p < c_.npop; p++) {
         const double *t = table + (size_t) p * len;
-        std::fill(seen.begin(), seen.end(), 0);
-        for (int q = 0; q < n; q++) {
-            BBO_REQUIRE(index(t[q], n) && !seen[(int) t[q]], "bbo_ssde_inject_draws: perm is a permutation of 0 .. n - 1");
-            seen[(int) t[q]] = 1;
-        }
+        permutation_of(t, n, "bbo_ssde_inject_draws: perm is a permutation of 0 .. n - 1");
         for (int i = 0; i < npinit; i++) {
             const double *m = t + n + (size_t) i * rec;
             BBO_REQUIRE(index(m[0], c_.H), "bbo_ssde_inject_draws: iL lies in [0, h)");
@@ -273,9 +193,7 @@ void SsdeEngine::inject_draws(const double *table, int count)
                 BBO_REQUIRE(unit(m[j]), "bbo_ssde_inject_draws: uniforms lie in [0, 1)");
         }
     }
-    if (!inject_.p) inject_.alloc(want);
-    inject_.upload(table, want);
-    d_.inject = inject_.p;
+    d_.inject = tables_.load(table, want);
 }
 
 void SsdeEngine::solution(int population, double *x_out, int *n_evals, int *converged)
@@ -308,7 +226,7 @@ int SsdeEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "fcand") return o.vec(fcand_, p, 1);
     if (k == "draws") {
         require_record(c.record, k);
-        return o.vec(draws_, (size_t) p * table_len(), (int) table_len());
+        return o.vec(tables_.draws, (size_t) p * table_len(), (int) table_len());
     }
     if (k == "k") return o.one(s.k);
     if (k == "kCR") return o.one(s.kCR);
@@ -348,12 +266,7 @@ int SsdeEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "record_draws") {      // (the whole handle: every population)
         BBO_REQUIRE(count == 1, "record_draws: one value");
         c_.record = in[0] != 0. ? 1 : 0;
-        if (c_.record && !draws_.p) {
-            draws_.alloc((size_t) c.npop * table_len());
-            std::vector<double> z((size_t) c.npop * table_len(), 0.);
-            draws_.upload(z.data(), z.size());
-        }
-        d_.draws = c_.record ? draws_.p : nullptr;
+        d_.draws = tables_.record(c_.record, (size_t) c.npop * table_len());
         return 1;
     }
     if (k == "substream") {     // the sub-stream of population 0; the pool is drawn again from it
@@ -387,15 +300,7 @@ int SsdeEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "LCR") return set_memory(LCR_, p, in, count, "LCR"), count;
     if (k == "perm") {          // the next generation keeps it
         BBO_REQUIRE(count == c.n, "perm: n values");
-        std::vector<int> perm(c.n);
-        std::vector<char> seen(c.n, 0);
-        for (int q = 0; q < c.n; q++) {
-            BBO_REQUIRE(in[q] >= 0. && in[q] < c.n && in[q] == std::floor(in[q]) && !seen[(int) in[q]],
-                    "perm: a permutation of 0 .. n - 1");
-            seen[(int) in[q]] = 1;
-            perm[q] = (int) in[q];
-        }
-        perm_.upload(perm.data(), c.n, (size_t) p * c.ld);
+        perm_.upload(permutation_of(in, c.n, "perm: a permutation of 0 .. n - 1").data(), c.n, (size_t) p * c.ld);
         SsdeScal s;
         scal_.download(&s, 1, p);
         s.keep_perm = 1;

@@ -36,9 +36,7 @@ enum SsdeStage {
 
 // what a launch of the body does
 enum SsdeMode {
-    SSDE_FUSED = 0,          // a whole generation, the evaluations inside
-    SSDE_ADVANCE,            // up to the next pending evaluation (phase 0)
-    SSDE_ABSORB              // take the value of the pending evaluation (phase 2)
+    SSDE_FUSED = WALK_FUSED, SSDE_ADVANCE = WALK_ADVANCE, SSDE_ABSORB = WALK_ABSORB
 };
 
 struct SsdeScal {
@@ -84,8 +82,9 @@ struct SsdeDev {
     SsdeScal *scal;
 };
 
-class SsdeEngine: public Engine<SsdeScal> {
+class SsdeEngine: public WalkEngine<SsdeScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an SSDE handle";
     explicit SsdeEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;
@@ -95,19 +94,17 @@ public:
     int dimension() const override { return c_.n; }
 
     void configure(const bbo_ssde_params &sp);
-    // bbo_ssde_phase: 0 advance to the next pending evaluation, 1 evaluate, 2 absorb
-    void phase(int which);
     void inject_draws(const double *table, int count);
 
 private:
     static const bbo_params &checked(const bbo_params &p);
-    void generation(bool honor_stop) override;
+    void launch_walk(int mode, bool begin) override;
+    void launch_eval_device() override;
+    PendingPoints pending_points(int p, const SsdeScal&) override { return { &cand_, (size_t) p * c_.ld, 1, c_.ld, &fcand_ }; }
+    int &honor_stop() override { return c_.honor_stop; }
     void seed_pool(int p0, int pcount);
     void launch_init(int p0, int pcount, int mode, int r0, int r1);
-    void launch_body(int mode, bool begin = true);
-    void launch_eval();
     void host_evaluate_rows_of(int p0, int pcount, int r0, int r1);
-    bool any_pending();
     int workgroup() const;
     size_t table_len() const { return (size_t) c_.n + (size_t) c_.npinit * (SSDE_REC_HEAD + 3 * (size_t) c_.n); }
     void set_memory(DevBuf<double> &b, int p, const double *in, int count, const char *what);
@@ -115,9 +112,9 @@ private:
     bbo_ssde_params sp_ {};
     SsdeConst c_ {};
     SsdeDev d_ {};
-    DevBuf<double> x_, f_, L1_, L2_, LCR_, SR_, SC_, w_, SCR_, wCR_, radius_, cand_, fcand_, draws_, inject_;
+    DevBuf<double> x_, f_, L1_, L2_, LCR_, SR_, SC_, w_, SCR_, wCR_, radius_, cand_, fcand_;
     DevBuf<int> order_, order2_, perm_;
-    bool mid_generation_ = false;    // bbo_ssde_phase: some population has a point pending
+    DrawTables tables_;
 };
 
 } // namespace bbo

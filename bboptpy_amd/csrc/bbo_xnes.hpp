@@ -70,6 +70,7 @@ struct XnesDev {
 
 class XnesEngine: public Engine<XnesScal> {
 public:
+    static constexpr const char *HANDLE_NAME = "not an xNES handle";
     explicit XnesEngine(const bbo_params &p);
     void init(int n, const double *lower, const double *upper, const double *guess,
             const ObjectiveSpec &obj) override;

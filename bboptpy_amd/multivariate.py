@@ -131,6 +131,9 @@ class MultivariateSearch:
 
     _algo = None
     _accepts_program = False     # DeviceObjective: the CMA-ES and DE families
+    # the engine's prefix in the C ABI where it has an extension struct: the struct is self._<prefix>, handed
+    # to bbo_<prefix>_configure when the handle is made; bbo_<prefix>_phase is what _phase() calls
+    _extension = None
 
     def __init__(self, *, seed=None, device=0, populations=1, poll_every=None):
         _ffi.lib()   # fail loudly at construction when the HIP library is missing
@@ -145,11 +148,20 @@ class MultivariateSearch:
         self._handle = None
         self._binding = None
         self._n = None
+        self._record_draws = False      # (extension of some engines) set_state("record_draws") at initialize()
 
     # -- handle management --------------------------------------------------------
     def _create(self):
+        L = _ffi.lib()
         h = C.c_void_p()
-        _ffi.check(_ffi.lib().bbo_create(C.byref(self._params), C.byref(h)))
+        _ffi.check(L.bbo_create(C.byref(self._params), C.byref(h)))
+        if self._extension is not None:
+            configure = getattr(L, "bbo_%s_configure" % self._extension)
+            status = configure(h, C.byref(getattr(self, "_" + self._extension)))
+            if status < 0:
+                msg = L.bbo_last_error(h)
+                L.bbo_destroy(h)
+                raise _ffi.BboError(status, msg.decode() if msg else "")
         return h
 
     def _ensure_handle(self):
@@ -214,6 +226,8 @@ class MultivariateSearch:
         h = self._ensure_handle()
         self._check(_ffi.lib().bbo_init(h, n, lower, upper, guess,
                                         C.byref(self._binding.struct)))
+        if self._record_draws:
+            self.set_state("record_draws", [1.])
 
     def iterate(self):
         if self._handle is None:
@@ -254,6 +268,28 @@ class MultivariateSearch:
         v = _np.ascontiguousarray(_np.asarray(value, dtype=_np.float64)).ravel()
         self._check(_ffi.lib().bbo_set(self._handle, key.encode(), population, v, v.size))
 
+    # -- what the engines' extension methods are made of ---------------------------------
+    def _phase(self, which):
+        self._check(getattr(_ffi.lib(), "bbo_%s_phase" % self._extension)(self._handle, int(which)))
+
+    def _inject(self, fn_name, table):
+        """a table of draws for the generations that follow; None: the device draws"""
+        fn = getattr(_ffi.lib(), fn_name)
+        if table is None:
+            self._check(fn(self._handle, None, 0))
+            return
+        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
+        self._check(fn(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+
+    def _pending(self):
+        """the populations that have a point waiting for its value"""
+        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+
+    @staticmethod
+    def _require_finite_box(n, lower, upper, what):
+        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
+            raise ValueError("%s: the bounds must be finite" % what)
+
 
 class BaseCMAES(MultivariateSearch):
     """BaseCmaes, multivariate_py.cpp:99-101 (abstract in the reference)"""
@@ -292,12 +328,7 @@ class BaseCMAES(MultivariateSearch):
         return out.value
 
     def inject_normals(self, z):
-        if z is None:
-            self._check(_ffi.lib().bbo_cma_inject_normals(self._handle, None, 0))
-            return
-        z = _np.ascontiguousarray(_np.asarray(z, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_cma_inject_normals(
-            self._handle, z.ctypes.data_as(C.c_void_p), z.size))
+        self._inject("bbo_cma_inject_normals", z)
 
 
 class CMAES(BaseCMAES):
@@ -359,6 +390,7 @@ class LmCMAES(BaseCMAES):
     adds for the restart drivers (set_params, set_seed, evaluate) and inject_normals raise
     NotImplementedError; the draws are injected with inject_draws."""
     _algo = _ffi.ALGO_LM_CMAES
+    _extension = "lm"
     _accepts_program = False
 
     def __init__(self, mfev, tol, np, memory=0, sigma0=2., bound=False, rademacher=True, usenew=True, **ext):
@@ -369,29 +401,16 @@ class LmCMAES(BaseCMAES):
         s = self._lm = _ffi.LmParams()
         s.memory, s.rademacher, s.usenew = int(memory), int(bool(rademacher)), int(bool(usenew))
 
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_lm_configure(h, C.byref(self._lm))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
     def phase(self, which):
         """one part of a generation: 0 sample, 1 evaluate, 2 rank, 3 update of mean / pc / memory /
         sigma, 4 history + counters + stop test"""
-        self._check(_ffi.lib().bbo_lm_phase(self._handle, int(which)))
+        self._phase(which)
 
     def inject_draws(self, table):
         """the draws of the following G generations, [G][populations][ceil(np / 2)][n + 1]: per "+"
         candidate its z (normals, or +-1) and the normal of the subset selection (ignored where the
         reference draws none); None: the device draws"""
-        if table is None:
-            self._check(_ffi.lib().bbo_lm_inject_draws(self._handle, None, 0))
-            return
-        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_lm_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+        self._inject("bbo_lm_inject_draws", table)
 
     def _not_here(self, what):
         raise NotImplementedError("LmCMAES has no %s: it runs on an engine of its own, outside the "
@@ -734,6 +753,7 @@ class JAYA(MultivariateSearch):
     with Levy-flight and chaotic mutations, Rao 2016, Rao & Saroj 2017; jaya.cpp).  `guess` is
     ignored, as in the reference; `kcheb` is stored and unused, as in the reference."""
     _algo = _ffi.ALGO_JAYA
+    _extension = "jaya"
 
     class JAYA_Mutation(enum.IntEnum):
         """JayaSearch::jaya_mutation_method, bound with export_values (:214-219)"""
@@ -754,21 +774,13 @@ class JAYA(MultivariateSearch):
         j.adapt, j.k0, j.mutation = int(bool(adapt)), int(k0), int(self.JAYA_Mutation(mutation))
         j.kcheb, j.scale, j.beta, j.temper = int(kcheb), float(scale), float(beta), float(temper)
 
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_jaya_configure(h, C.byref(self._jaya))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
 
 class DSA(MultivariateSearch):
     """DSA(mfev, tol, stol, np, adapt=True, nbatch=100) -- :189-191 (Differential Search,
     Civicioglu 2012, with the reference's Rexp3 bandit over the four direction methods; ds.cpp).
     `guess` is ignored, as in the reference."""
     _algo = _ffi.ALGO_DSA
+    _extension = "dsa"
 
     def __init__(self, mfev, tol, stol, np, adapt=True, nbatch=100, **ext):
         super().__init__(**ext)
@@ -776,15 +788,6 @@ class DSA(MultivariateSearch):
         p.mfev, p.tol, p.stol, p.np = int(mfev), float(tol), float(stol), int(np)
         d = self._dsa = _ffi.DsaParams()
         d.adapt, d.nbatch = int(bool(adapt)), int(nbatch)
-
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_dsa_configure(h, C.byref(self._dsa))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
 
 
 class HEES(MultivariateSearch):
@@ -794,6 +797,7 @@ class HEES(MultivariateSearch):
     mres > 1 restarts with doubled np from uniform points of the box (a finite box, populations=1);
     initialize / iterate / run ignore mres, as in the reference.  The bounds never clamp."""
     _algo = _ffi.ALGO_HEES
+    _extension = "hees"
 
     def __init__(self, mfev, tol, mres=1, print=False, np=0, sigma0=2., **ext):
         super().__init__(**ext)
@@ -804,15 +808,6 @@ class HEES(MultivariateSearch):
         if h.mres > 1 and p.populations != 1:
             raise ValueError("HEES: restarts (mres > 1) work on populations=1 only")
 
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_hees_configure(h, C.byref(self._hees))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
     def optimize(self, f, lower, upper, guess):
         if self._hees.print:
             sys.stdout.flush()      # the table is written by the library
@@ -820,17 +815,12 @@ class HEES(MultivariateSearch):
 
     def phase(self, which):
         """one part of a generation: 0 sample + evaluate, 1 rank, 2 update, 3 finish"""
-        self._check(_ffi.lib().bbo_hees_phase(self._handle, int(which)))
+        self._phase(which)
 
     def inject_normals(self, z):
         """the normals of the following generations: per population the reference's (B n) x n
         table, B = ceil(mu / n), of which the first mu rows are used; None: the device draws"""
-        if z is None:
-            self._check(_ffi.lib().bbo_hees_inject_normals(self._handle, None, 0))
-            return
-        z = _np.ascontiguousarray(_np.asarray(z, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_hees_inject_normals(
-            self._handle, z.ctypes.data_as(C.c_void_p), z.size))
+        self._inject("bbo_hees_inject_normals", z)
 
 
 class xNES(MultivariateSearch):
@@ -840,6 +830,7 @@ class xNES(MultivariateSearch):
     extension, keyword-only) starts the mean at `guess`.  solution() is the best point of the last
     generation; get_state("xbest") / ("fbest") hold the best ever seen.  n is at most 512."""
     _algo = _ffi.ALGO_XNES
+    _extension = "xnes"
 
     def __init__(self, mfev, tol, a0=1., etamu=1., *, from_guess=False, **ext):
         super().__init__(**ext)
@@ -848,28 +839,14 @@ class xNES(MultivariateSearch):
         x = self._xnes = _ffi.XnesParams()
         x.a0, x.etamu, x.from_guess = float(a0), float(etamu), int(bool(from_guess))
 
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_xnes_configure(h, C.byref(self._xnes))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
     def phase(self, which):
         """one part of a generation: 0 sample + evaluate, 1 rank, 2 small step, 3 adapt"""
-        self._check(_ffi.lib().bbo_xnes_phase(self._handle, int(which)))
+        self._phase(which)
 
     def inject_normals(self, z):
         """the normals of the following G generations, [G][populations][np][n] in sampling order;
         None: the device draws"""
-        if z is None:
-            self._check(_ffi.lib().bbo_xnes_inject_normals(self._handle, None, 0))
-            return
-        z = _np.ascontiguousarray(_np.asarray(z, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_xnes_inject_normals(
-            self._handle, z.ctypes.data_as(C.c_void_p), z.size))
+        self._inject("bbo_xnes_inject_normals", z)
 
 
 class AMALGAM(MultivariateSearch):
@@ -884,6 +861,7 @@ class AMALGAM(MultivariateSearch):
     (concurrent=True) or one after another (concurrent=False) with the same results; it needs
     populations=1 and print=True writes the reference's table.  n is at most 512, np in [3, 65536]."""
     _algo = _ffi.ALGO_AMALGAM
+    _extension = "amalgam"
     _accepts_program = False
 
     def __init__(self, mfev, tol, stol, np=0, iamalgam=True, noparam=True, print=True, *,
@@ -898,15 +876,6 @@ class AMALGAM(MultivariateSearch):
         if a.noparam and p.populations != 1:
             raise ValueError("AMALGAM: the parameter-free mode (noparam=True) works on populations=1 only")
         self._points = None
-
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_amalgam_configure(h, C.byref(self._amalgam))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
 
     def _flush(self):
         if self._amalgam.print and self._amalgam.noparam:
@@ -931,7 +900,7 @@ class AMALGAM(MultivariateSearch):
 
     def phase(self, which):
         """one part of a generation: 0 distribution, 1 sample + evaluate, 2 adapt + stop"""
-        self._check(_ffi.lib().bbo_amalgam_phase(self._handle, int(which)))
+        self._phase(which)
 
     def inject_points(self, x):
         """the initial points of the next initialize() / optimize(), [populations][np][n]"""
@@ -958,6 +927,7 @@ class SpiralSearch(MultivariateSearch):
     ignored, as in the reference; the box seeds the points and never clamps them; `converged` is
     always False."""
     _algo = _ffi.ALGO_SPIRAL
+    _extension = "spiral"
 
     def __init__(self, mfev, tol, np=20, r=0.95, theta=1.57079632679, taur=0.0, tautheta=0.1,
                  rlow=0.9, rhigh=1.0, thetalow=0.0, thetahigh=6.28318530718, **ext):
@@ -968,28 +938,14 @@ class SpiralSearch(MultivariateSearch):
         s.r, s.theta, s.taur, s.tautheta = float(r), float(theta), float(taur), float(tautheta)
         s.rlow, s.rhigh, s.thetalow, s.thetahigh = float(rlow), float(rhigh), float(thetalow), float(thetahigh)
 
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_spiral_configure(h, C.byref(self._spiral))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
     def phase(self, which):
         """one part of a generation: 0 draw, 1 rotate, 2 evaluate, 3 best"""
-        self._check(_ffi.lib().bbo_spiral_phase(self._handle, int(which)))
+        self._phase(which)
 
     def inject_uniforms(self, u):
         """the raw uniforms of the following generations, [populations][np][4] in [0, 1): per point
         the coin of r, the value of r, the coin of theta, the value of theta; None: the device draws"""
-        if u is None:
-            self._check(_ffi.lib().bbo_spiral_inject_uniforms(self._handle, None, 0))
-            return
-        u = _np.ascontiguousarray(_np.asarray(u, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_spiral_inject_uniforms(
-            self._handle, u.ctypes.data_as(C.c_void_p), u.size))
+        self._inject("bbo_spiral_inject_uniforms", u)
 
 
 class NSHS(MultivariateSearch):
@@ -1000,6 +956,7 @@ class NSHS(MultivariateSearch):
     Extension `record_draws=True` keeps the four raw uniforms of every coordinate of the last
     iteration (get_state("draws"))."""
     _algo = _ffi.ALGO_NSHS
+    _extension = "nshs"
     _accepts_program = False
 
     def __init__(self, mfev, hms, fstdmin=0.0001, **ext):
@@ -1011,34 +968,15 @@ class NSHS(MultivariateSearch):
         s.fstdmin = float(fstdmin)
         self._record_draws = bool(record_draws)
 
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_nshs_configure(h, C.byref(self._nshs))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
-    def initialize(self, f, lower, upper, guess):
-        super().initialize(f, lower, upper, guess)
-        if self._record_draws:
-            self.set_state("record_draws", [1.])
-
     def phase(self, which):
         """one part of an iteration: 0 generate, 1 evaluate, 2 replace"""
-        self._check(_ffi.lib().bbo_nshs_phase(self._handle, int(which)))
+        self._phase(which)
 
     def inject_uniforms(self, u):
         """the raw uniforms of the following iterations, [populations][n][4] in [0, 1): per
         coordinate the coin, the row (row j as (j + 0.5) / hms), the fresh value, the adjustment;
         None: the device draws"""
-        if u is None:
-            self._check(_ffi.lib().bbo_nshs_inject_uniforms(self._handle, None, 0))
-            return
-        u = _np.ascontiguousarray(_np.asarray(u, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_nshs_inject_uniforms(
-            self._handle, u.ctypes.data_as(C.c_void_p), u.size))
+        self._inject("bbo_nshs_inject_uniforms", u)
 
 
 class SLPSO(MultivariateSearch):
@@ -1050,6 +988,7 @@ class SLPSO(MultivariateSearch):
     Extension `record_draws=True` keeps the draws of the last generation in the layout of
     inject_draws (get_state("draws"))."""
     _algo = _ffi.ALGO_SLPSO
+    _extension = "slpso"
     _accepts_program = False
     MAX_N, MAX_NP = 512, 4096
 
@@ -1070,23 +1009,8 @@ class SLPSO(MultivariateSearch):
             raise ValueError("SLPSO: np must be in [2, %d]" % self.MAX_NP)
         if not 1 <= n <= self.MAX_N:
             raise ValueError("SLPSO: dimension must be in [1, %d]" % self.MAX_N)
-        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
-            raise ValueError("SLPSO draws its swarm from [lower, upper]: the bounds must be finite")
+        self._require_finite_box(n, lower, upper, "SLPSO draws its swarm from [lower, upper]")
         return n, lower, upper, guess
-
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_slpso_configure(h, C.byref(self._slpso))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
-    def initialize(self, f, lower, upper, guess):
-        super().initialize(f, lower, upper, guess)
-        if self._record_draws:
-            self.set_state("record_draws", [1.])
 
     def table_len(self):
         """doubles per population of the table of inject_draws and of get_state("draws")"""
@@ -1097,21 +1021,17 @@ class SLPSO(MultivariateSearch):
         """the generation one evaluation at a time: 0 advance to the next pending point ("cand"), 1
         evaluate it, 2 absorb the value.  Phase 0 returns the number of populations that have a point
         pending: 0 when the generation is complete."""
-        self._check(_ffi.lib().bbo_slpso_phase(self._handle, int(which)))
+        self._phase(which)
         if int(which) != 0:
             return None
-        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+        return self._pending()
 
     def inject_draws(self, table):
         """the draws of the following generations, [populations][1 + np + np (3 + 4 n)]: alpha, the
         permutation after its shuffle, then per particle step the forcing coin, the roulette uniform, the
         partner j as (j + 0.5) / np and per coordinate r, the normal of operator 1, the redraw of eq. 11
         and the coin of Algorithm 2; None: the device draws"""
-        if table is None:
-            self._check(_ffi.lib().bbo_slpso_inject_draws(self._handle, None, 0))
-            return
-        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_slpso_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+        self._inject("bbo_slpso_inject_draws", table)
 
 
 class CRS(MultivariateSearch):
@@ -1127,6 +1047,7 @@ class CRS(MultivariateSearch):
     overflows its stack); `record_draws=True` keeps the draws of the last iteration in the layout of
     inject_draws (get_state("draws"))."""
     _algo = _ffi.ALGO_CRS
+    _extension = "crs"
     _accepts_program = False
     MAX_N, MAX_NP = 512, 65536
 
@@ -1147,42 +1068,23 @@ class CRS(MultivariateSearch):
             raise ValueError("CRS: np must be in [2, %d]" % self.MAX_NP)
         if not 1 <= n <= self.MAX_N:
             raise ValueError("CRS: dimension must be in [1, %d]" % self.MAX_N)
-        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
-            raise ValueError("CRS draws its pool from [lower, upper]: the bounds must be finite")
+        self._require_finite_box(n, lower, upper, "CRS draws its pool from [lower, upper]")
         return n, lower, upper, guess
-
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_crs_configure(h, C.byref(self._crs))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
-    def initialize(self, f, lower, upper, guess):
-        super().initialize(f, lower, upper, guess)
-        if self._record_draws:
-            self.set_state("record_draws", [1.])
 
     def phase(self, which):
         """the iteration one evaluation at a time: 0 advance to the next pending point ("cand" in stage
         1, "cand2" in stage 2), 1 evaluate it ("value"), 2 absorb the value and advance again.  Phases 0
         and 2 return the number of populations that have a point pending: 0 when the iteration is
         complete."""
-        self._check(_ffi.lib().bbo_crs_phase(self._handle, int(which)))
+        self._phase(which)
         if int(which) == 1:
             return None
-        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+        return self._pending()
 
     def inject_draws(self, table):
         """the draws of the following trials, [populations][records][2 n]: per record the n row indices
         of a trial (-1 where none is drawn) and the n uniforms of a mutation; None: the device draws"""
-        if table is None:
-            self._check(_ffi.lib().bbo_crs_inject_draws(self._handle, None, 0))
-            return
-        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_crs_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+        self._inject("bbo_crs_inject_draws", table)
 
 
 class SSDE(MultivariateSearch):
@@ -1195,6 +1097,7 @@ class SSDE(MultivariateSearch):
     and ptop must lie in (0, 1).  `record_draws=True` (an extension) keeps the draws of the last
     generation in the layout of inject_draws (get_state("draws"))."""
     _algo = _ffi.ALGO_SSDE
+    _extension = "ssde"
     _accepts_program = False
     MAX_N, MIN_NP, MAX_NP = 512, 4, 4096
 
@@ -1215,42 +1118,23 @@ class SSDE(MultivariateSearch):
             raise ValueError("SSDE: npinit must be in [4, %d]" % self.MAX_NP)
         if not 1 <= n <= self.MAX_N:
             raise ValueError("SSDE: dimension must be in [1, %d]" % self.MAX_N)
-        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
-            raise ValueError("SSDE draws its pool from [lower, upper]: the bounds must be finite")
+        self._require_finite_box(n, lower, upper, "SSDE draws its pool from [lower, upper]")
         return n, lower, upper, guess
-
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_ssde_configure(h, C.byref(self._ssde))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
-
-    def initialize(self, f, lower, upper, guess):
-        super().initialize(f, lower, upper, guess)
-        if self._record_draws:
-            self.set_state("record_draws", [1.])
 
     def phase(self, which):
         """the generation one evaluation at a time: 0 advance to the next pending point ("cand"), 1
         evaluate it ("fcand"), 2 absorb the value.  Phases 0 and 2 return the number of populations that
         have a point pending: 0 when the generation is complete."""
-        self._check(_ffi.lib().bbo_ssde_phase(self._handle, int(which)))
+        self._phase(which)
         if int(which) == 1:
             return None
-        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+        return self._pending()
 
     def inject_draws(self, table):
         """the draws of the following generations, [populations][n + npinit * (9 + 3 n)]: the permutation,
         then per member iL, the normal of prank, p, q, r, pbest, ci, the normal of CRi, j0 and the n
         uniforms each of b, the crossover and the redraw; None: the device draws"""
-        if table is None:
-            self._check(_ffi.lib().bbo_ssde_inject_draws(self._handle, None, 0))
-            return
-        t = _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
-        self._check(_ffi.lib().bbo_ssde_inject_draws(self._handle, t.ctypes.data_as(C.c_void_p), t.size))
+        self._inject("bbo_ssde_inject_draws", table)
 
 
 class ACD(MultivariateSearch):
@@ -1267,6 +1151,7 @@ class ACD(MultivariateSearch):
     speculative sweep over the next pending coordinates) was built, measured slower at 4096 populations
     and dropped: only False is accepted."""
     _algo = _ffi.ALGO_ACD
+    _extension = "acd"
     _accepts_program = False
     MAX_N = 128
 
@@ -1285,27 +1170,17 @@ class ACD(MultivariateSearch):
         n, lower, upper, guess = super()._problem(f, lower, upper, guess)
         if not 1 <= n <= self.MAX_N:
             raise ValueError("ACD: dimension must be in [1, %d]" % self.MAX_N)
-        if not (_np.isfinite(lower[:n]).all() and _np.isfinite(upper[:n]).all()):
-            raise ValueError("ACD draws x_best from [lower, upper]: the bounds must be finite")
+        self._require_finite_box(n, lower, upper, "ACD draws x_best from [lower, upper]")
         return n, lower, upper, guess
-
-    def _create(self):
-        h = super()._create()
-        status = _ffi.lib().bbo_acd_configure(h, C.byref(self._acd))
-        if status < 0:
-            msg = _ffi.lib().bbo_last_error(h)
-            _ffi.lib().bbo_destroy(h)
-            raise _ffi.BboError(status, msg.decode() if msg else "")
-        return h
 
     def phase(self, which):
         """a coordinate step one part at a time: 0 form x1 and x2 ("cand", 2 x n), 1 evaluate them
         ("value"), 2 absorb the values, finish the step and, where due, update the encoding.  Phase 0
         returns the number of populations that have a pair pending."""
-        self._check(_ffi.lib().bbo_acd_phase(self._handle, int(which)))
+        self._phase(which)
         if int(which) != 0:
             return None
-        return sum(int(self.get_state("pending", p)[0]) for p in range(self._params.populations))
+        return self._pending()
 
 
 class APSO(MultivariateSearch):
