@@ -10,8 +10,8 @@ from .objectives import vectorized, DeviceObjective
 from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, CMAES,
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
                            SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES,
-                           SpiralSearch, NSHS, LmCMAES, xNES, AMALGAM, SLPSO, CRS, SSDE, ACD)
+                           SpiralSearch, NSHS, LmCMAES, xNES, AMALGAM, SLPSO, CRS, SSDE, ACD, Mayfly)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "objectives",
            "vectorized", "DeviceObjective"]

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
     ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
-    ALGO_CRS, ALGO_SSDE, ALGO_ACD = range(24)
+    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY = range(25)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -143,6 +143,13 @@ class AcdParams(C.Structure):
                 ("speculate", C.c_int)]
 
 
+class MayflyParams(C.Structure):
+    """bbo_mayfly_params: the arguments of Mayfly that bbo_params has no field for"""
+    _fields_ = [(k, C.c_double) for k in ("a1", "a2", "a3", "beta", "dance", "ddamp", "fl", "fldamp", "gmin",
+                                          "gmax", "vdamp", "sigma", "pmutdim", "pmutnp", "l")] \
+        + [("pgb", C.c_int), ("repair", C.c_int), ("substream", C.c_int)]
+
+
 class Objective(C.Structure):
     _fields_ = [("kind", C.c_int), ("builtin", C.c_int), ("scalar", SCALAR_FN),
                 ("batch", BATCH_FN), ("user", C.c_void_p)]
@@ -209,6 +216,7 @@ EXTENSIONS = {
     "crs": (CrsParams, True, {"draws": _TABLE}),
     "ssde": (SsdeParams, True, {"draws": _TABLE}),
     "acd": (AcdParams, True, {}),
+    "mayfly": (MayflyParams, False, {"draws": _TABLE}),
 }
 
 

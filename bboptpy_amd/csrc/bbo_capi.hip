@@ -15,6 +15,7 @@
 #include "bbo_crs.hpp"
 #include "bbo_ssde.hpp"
 #include "bbo_acd.hpp"
+#include "bbo_mayfly.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -38,6 +39,7 @@ Optimizer* make_slpso_engine(const bbo_params &p);    // bbo_slpso.hip
 Optimizer* make_crs_engine(const bbo_params &p);      // bbo_crs.hip
 Optimizer* make_ssde_engine(const bbo_params &p);     // bbo_ssde.hip
 Optimizer* make_acd_engine(const bbo_params &p);      // bbo_acd.hip
+Optimizer* make_mayfly_engine(const bbo_params &p);   // bbo_mayfly.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 }
 
@@ -147,6 +149,7 @@ const struct {
     { BBO_ALGO_XNES, bbo::make_xnes_engine }, { BBO_ALGO_AMALGAM, bbo::make_amalgam_engine },
     { BBO_ALGO_SLPSO, bbo::make_slpso_engine }, { BBO_ALGO_CRS, bbo::make_crs_engine },
     { BBO_ALGO_SSDE, bbo::make_ssde_engine }, { BBO_ALGO_ACD, bbo::make_acd_engine },
+    { BBO_ALGO_MAYFLY, bbo::make_mayfly_engine },
 };
 
 bbo::ObjectiveSpec to_spec(const bbo_objective *o)
@@ -745,6 +748,40 @@ int bbo_acd_configure(bbo_handle h, const bbo_acd_params *p)
 int bbo_acd_phase(bbo_handle h, int phase)
 {
     return guarded(h, [&] { engine_of<bbo::AcdEngine>(h)->phase(phase); });
+}
+
+void bbo_mayfly_params_default(bbo_mayfly_params *p)
+{
+    if (!p) return;
+    /* py/multivariate_py.cpp:236-246 (commented away there), mayfly.h:64-68 */
+    p->a1 = 1.;
+    p->a2 = 1.5;
+    p->a3 = 1.5;
+    p->beta = 2.;
+    p->dance = 5.;
+    p->ddamp = 0.8;
+    p->fl = 1.;
+    p->fldamp = 0.99;
+    p->gmin = 0.8;
+    p->gmax = 0.8;
+    p->vdamp = 0.1;
+    p->sigma = 0.1;
+    p->pmutdim = 0.01;
+    p->pmutnp = 0.05;
+    p->l = 0.95;
+    p->pgb = 0;
+    p->repair = 0;
+    p->substream = 0;
+}
+
+int bbo_mayfly_configure(bbo_handle h, const bbo_mayfly_params *p)
+{
+    return configure_of<bbo::MayflyEngine>(h, p, "bbo_mayfly_configure");
+}
+
+int bbo_mayfly_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { engine_of<bbo::MayflyEngine>(h)->inject_draws(table, count); });
 }
 
 const char* bbo_last_error(bbo_handle h)

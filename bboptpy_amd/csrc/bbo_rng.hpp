@@ -54,7 +54,11 @@ enum Stream : uint32_t {
     STREAM_SSDE_CTRL = 35,
     STREAM_SSDE_R = 36,
     STREAM_SSDE_PERM = 37,
-    STREAM_ACD_INIT = 38
+    STREAM_ACD_INIT = 38,
+    STREAM_MAYFLY_INIT = 39,
+    STREAM_MAYFLY_R = 40,
+    STREAM_MAYFLY_PERM = 41,
+    STREAM_MAYFLY_Z = 42
 };
 
 struct u32x4 {

@@ -1183,6 +1183,71 @@ class ACD(MultivariateSearch):
         return self._pending()
 
 
+class Mayfly(MultivariateSearch):
+    """Mayfly(np, mfev, a1=1., a2=1.5, a3=1.5, beta=2., dance=5., ddamp=0.8, fl=1., fldamp=0.99, gmin=0.8,
+    gmax=0.8, vdamp=0.1, sigma=0.1, pmutdim=0.01, pmutnp=0.05, l=0.95, pgb=False) -- the binding the reference
+    writes out at :236-246 and leaves commented away (the mayfly optimizer of Zervoudakis & Tsafarakis 2020
+    with the PGB-IMA switch; mayfly.cpp).  A generation moves np females and np males, mates the sorted
+    swarms into np offspring, mutates nmut of them and selects: 3 np + nmut evaluations, all of them parallel
+    across the individuals but the male loop, which runs as rounds of `window` males.  `guess` is ignored, as
+    in the reference, and a finite box is mandatory.  np must be even (the reference leaves the last
+    offspring of an odd swarm unwritten, a zero vector of value 0 that wins the selection) and mfev must
+    exceed 2 np (the initial swarms; else the reference divides 0 by 0).  The budget is tested between
+    generations: n_evals passes mfev by less than one generation; converged is always False.  The default
+    reproduces the reference's in-place selection, which leaves about half of each swarm an exact duplicate.
+    The reference also builds its flies with x and v exchanged, so every fly starts at the origin with the
+    point it drew as its velocity; that is reproduced too.
+    Extensions, keyword-only: `repair=True` selects from untouched copies and starts every fly at the point it
+    drew, as the paper does; `substream=s` lets population p draw from sub-stream s + p;
+    `record_draws=True` keeps the draws of the last generation in the layout of inject_draws
+    (get_state("draws"))."""
+    _algo = _ffi.ALGO_MAYFLY
+    _extension = "mayfly"
+    _accepts_program = False
+    MAX_N, MAX_NP = 512, 4096
+
+    def __init__(self, np, mfev, a1=1., a2=1.5, a3=1.5, beta=2., dance=5., ddamp=0.8, fl=1., fldamp=0.99,
+                 gmin=0.8, gmax=0.8, vdamp=0.1, sigma=0.1, pmutdim=0.01, pmutnp=0.05, l=0.95, pgb=False, *,
+                 repair=False, record_draws=False, substream=0, **ext):
+        super().__init__(**ext)
+        p = self._params
+        p.np, p.mfev = int(np), int(mfev)
+        m = self._mayfly = _ffi.MayflyParams()
+        for k, v in (("a1", a1), ("a2", a2), ("a3", a3), ("beta", beta), ("dance", dance), ("ddamp", ddamp),
+                     ("fl", fl), ("fldamp", fldamp), ("gmin", gmin), ("gmax", gmax), ("vdamp", vdamp),
+                     ("sigma", sigma), ("pmutdim", pmutdim), ("pmutnp", pmutnp), ("l", l)):
+            setattr(m, k, float(v))
+        m.pgb, m.repair, m.substream = int(bool(pgb)), int(bool(repair)), int(substream)
+        self._record_draws = bool(record_draws)
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        np_, mfev = self._params.np, self._params.mfev
+        if np_ < 2 or np_ > self.MAX_NP:
+            raise ValueError("Mayfly: np must be in [2, %d]" % self.MAX_NP)
+        if np_ % 2:
+            raise ValueError("Mayfly: np must be even: the reference leaves the last offspring of an odd swarm "
+                             "unwritten, a zero vector of value 0 that enters the selection")
+        if mfev <= 2 * np_:
+            raise ValueError("Mayfly: mfev must exceed 2 np, the evaluations of the initial swarms "
+                             "(itmax would be <= 0 and g = 0/0)")
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("Mayfly: dimension must be in [1, %d]" % self.MAX_N)
+        self._require_finite_box(n, lower, upper, "Mayfly draws its swarms from [lower, upper]")
+        return n, lower, upper, guess
+
+    def table_len(self):
+        """the length of one population's table of inject_draws"""
+        return int(self.get_state("table_len")[0])
+
+    def inject_draws(self, table):
+        """the draws of the following generations, [populations][2 np n + np + nmut + 2 nmut nmd]: the
+        canonical uniforms of the females' random flights and of the males' dances (-1 where a fly takes the
+        attraction form), the shuffles of the offspring and of the mutated flies as permutations, and per
+        mutated fly its nmd displaced genes and their normals; None: the device draws"""
+        self._inject("bbo_mayfly_inject_draws", table)
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

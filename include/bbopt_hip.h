@@ -65,7 +65,8 @@ typedef enum {
     BBO_ALGO_SLPSO = 20,       /* SLPSOSearch  src/multivariate/pso/slpso.h           */
     BBO_ALGO_CRS = 21,         /* CrsSearch    src/multivariate/crs/crs.h             */
     BBO_ALGO_SSDE = 22,        /* SSDESearch   src/multivariate/de/ssde.h             */
-    BBO_ALGO_ACD = 23          /* ACD          src/multivariate/acd/acd.h             */
+    BBO_ALGO_ACD = 23,         /* ACD          src/multivariate/acd/acd.h             */
+    BBO_ALGO_MAYFLY = 24       /* MayflySearch src/multivariate/mayfly/mayfly.h       */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -679,6 +680,54 @@ typedef struct { double ksucc, kunsucc; int from_guess; int speculate; } bbo_acd
 void bbo_acd_params_default(bbo_acd_params *p);   /* 2., 0.5, 0, 0 */
 int bbo_acd_configure(bbo_handle h, const bbo_acd_params *p);
 int bbo_acd_phase(bbo_handle h, int phase);
+
+/* ---- Mayfly (BBO_ALGO_MAYFLY): Mayfly(np,mfev,a1=1.,a2=1.5,a3=1.5,beta=2.,dance=5.,ddamp=0.8,fl=1.,
+ * fldamp=0.99,gmin=0.8,gmax=0.8,vdamp=0.1,sigma=0.1,pmutdim=0.01,pmutnp=0.05,l=0.95,pgb=false), the mayfly
+ * optimizer of Zervoudakis & Tsafarakis 2020 with the PGB-IMA switch (mayfly.cpp; the reference writes the
+ * binding out at py/multivariate_py.cpp:236-246 but leaves it commented away).  np and mfev travel in
+ * bbo_params, the rest here.  Both swarms start uniform in the box (fev = 2 np): a finite box is mandatory,
+ * `guess` is not read.  Limits: n in [1, 512], np even in [2, 4096], mfev > 2 np.  bbo_create refuses an odd
+ * np (the reference leaves the last offspring of an odd swarm unwritten: a zero vector of value 0 that wins
+ * the selection), np < 2 and mfev <= 2 np (itmax <= 0: g = 0/0); bbo_init refuses a box that is not finite, n
+ * outside the limits and an objective program (BBO_ERR_ARG).  No restart base, not sharded over devices.
+ * bbo_mayfly_configure is legal between bbo_create and bbo_init.
+ * One bbo_iterate is one iterate() of the reference: the females (each against the male of its slot), the
+ * males (male j + 1 reads the best that male j wrote: run as rounds of "window" males that are committed up
+ * to the first that improves fbest, the rest formed again with the same draws), both swarms sorted (stable
+ * on ties), np offspring, nmut mutated flies, the two selections and the schedule.  The reference's selection
+ * copies into the swarm in place while its sorted list still points at slots already overwritten, which
+ * leaves about half of each swarm an exact duplicate; that is reproduced (repair = 0) by resolving for every
+ * slot the record that lands in it.  repair = 1 (an extension) selects from untouched copies, as the paper
+ * does, and starts every fly at the point it drew with no velocity (the reference builds its flies with x and v
+ * exchanged: every fly starts at the origin, the drawn point is its velocity and, for a male, its own best).
+ * substream (an extension): population p draws from Philox sub-stream substream + p, so a batch can be
+ * checked against single runs.  The budget is tested between generations, so fev passes mfev by less than one generation (3 np +
+ * nmut evaluations); there is no convergence test ("flag" 2 = budget).
+ * bbo_mayfly_inject_draws: populations * table_len doubles that replace the generator in every following
+ * generation ("table_len" = 2 np n + np + nmut + 2 nmut nmd, nmd = ceil(pmutdim n)): the canonical uniforms
+ * in [0, 1) of the females' random flights [np][n] and of the males' dances [np][n] (-1 where the fly takes
+ * the attraction form), the shuffle of the offspring and of the mutated flies as permutations (shuffled
+ * place -> index), and per mutated fly its nmd displaced genes and their nmd normals.  NULL returns to the
+ * device generator (Philox keyed by generation, swarm, individual and coordinate).  "record_draws" keeps
+ * the same table of the last generation ("draws").
+ * Keys: "males_x" "males_v" "males_bx" "males_f" "males_bf" "females_x" "females_v" "females_f" (slot
+ * order), "xbest" "fbest" "g" "dance" "fl" "it" "itmax" "fev" (all writable: a whole state can be set, nothing
+ * is evaluated), "nmut" "nmd" "flag" "conv"; of the last generation: "moved_males_x" "moved_males_v"
+ * "moved_males_f" "moved_females_x" "moved_females_v" "moved_females_f" (the swarms after their moves, before
+ * the selection), "off_x" "off_f" "mut_x" "mut_f", "rank_m" "rank_f" (rank -> slot), "sel_m" "sel_f" (rank ->
+ * record of the selection: t < np the swarm's fly of rank t, then np / 2 shuffled offspring, then nmut / 2
+ * shuffled mutated flies), "src_m" "src_f" (the record that landed in each slot), "branch_m" "branch_f"
+ * (1: attraction, 0: the random form), "perm_o" "perm_u", "took" (the evaluation that took fbest last:
+ * females from 0, males from np, offspring from 2 np, mutated flies from 3 np; -1 none), "dropped" "rounds"
+ * (male evaluations discarded and rounds run so far).  "window" (writable): the males of a round, 0 = all
+ * remaining, default 4; the state does not depend on it.  A NaN value counts as +inf. */
+typedef struct {
+    double a1, a2, a3, beta, dance, ddamp, fl, fldamp, gmin, gmax, vdamp, sigma, pmutdim, pmutnp, l;
+    int pgb, repair, substream;
+} bbo_mayfly_params;
+void bbo_mayfly_params_default(bbo_mayfly_params *p);   /* 1, 1.5, 1.5, 2, 5, 0.8, 1, 0.99, 0.8, 0.8, 0.1, 0.1, 0.01, 0.05, 0.95, 0, 0, 0 */
+int bbo_mayfly_configure(bbo_handle h, const bbo_mayfly_params *p);
+int bbo_mayfly_inject_draws(bbo_handle h, const double *table, int count);
 
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
