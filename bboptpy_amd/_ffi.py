@@ -195,6 +195,7 @@ CORE = {
     "bbo_ccpso_merge_tables": ([_h, C.c_void_p, _i, _i], _i),
     "bbo_program_create": ([C.c_char_p, C.c_char_p, C.c_void_p, _i, C.POINTER(_h)], _i),
     "bbo_program_destroy": ([_h], _i),
+    "bbo_probe_objective": ([_i, _i, _i, _i, _dp, _dp], _i),
     "bbo_last_error": ([_h], C.c_char_p),
     "bbo_version": (None, C.c_char_p),
     "bbo_device_count": (None, _i),
@@ -260,6 +261,16 @@ def check(status, handle=None):
         msg = lib().bbo_last_error(handle)
         raise BboError(status, msg.decode() if msg else "")
     return status
+
+
+def probe_objective(objective, form, X):
+    """diagnostics (bbo_probe_objective): built-in `objective` (a name or an id) at the rows of
+    X[rows, n] through device form `form`; the raw values, one per row"""
+    X = np.ascontiguousarray(np.atleast_2d(np.asarray(X, dtype=np.float64)))
+    f = np.empty(X.shape[0])
+    check(lib().bbo_probe_objective(BUILTIN_IDS.get(objective, objective), int(form), X.shape[1],
+                                    X.shape[0], X, f))
+    return f
 
 
 def default_params(algo):

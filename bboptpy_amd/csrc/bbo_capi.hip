@@ -41,6 +41,7 @@ Optimizer* make_ssde_engine(const bbo_params &p);     // bbo_ssde.hip
 Optimizer* make_acd_engine(const bbo_params &p);      // bbo_acd.hip
 Optimizer* make_mayfly_engine(const bbo_params &p);   // bbo_mayfly.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
+void probe_objective(int obj, int form, int n, int rows, const double *X, double *f_out);   // bbo_probe.hip
 }
 
 // the caller's share of a compiled objective program; handles initialised with it hold their own
@@ -782,6 +783,13 @@ int bbo_mayfly_configure(bbo_handle h, const bbo_mayfly_params *p)
 int bbo_mayfly_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { engine_of<bbo::MayflyEngine>(h)->inject_draws(table, count); });
+}
+
+// diagnostics: no handle, so the message is the one of bbo_last_error(NULL)
+int bbo_probe_objective(int objective, int form, int n, int rows, const double *X, double *f_out)
+{
+    return created("bbo_probe_objective", X && f_out,
+            [&] { bbo::probe_objective(objective, form, n, rows, X, f_out); });
 }
 
 const char* bbo_last_error(bbo_handle h)

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/bbopt_hip.h"
+#include "bbo_objectives.hpp"
 
 namespace bbo {
 
@@ -241,13 +242,14 @@ inline void fill_objective_aux(int obj, int n, double *aux)
     }
 }
 
-// a built-in objective at ONE point on the host: the same definition and the same per-coordinate
-// table as the device kernels (bbo_objectives.hpp).  For the few places that evaluate a single
+// a built-in objective at ONE point on the host: the same definition, the same cos_2pi and the same
+// per-coordinate table as the device kernels (bbo_objectives.hpp; std::cos(2 pi x) would round 2 pi x
+// first and lose cos altogether at large |x|).  For the few places that evaluate a single
 // point between device generations: the restart drivers' extra evaluation (bipop_cmaes.cpp:86),
 // CCPSO's local search (ccpso.cpp:371-435).
 inline double builtin_objective_host(int obj, int n, const double *x, const double *aux)
 {
-    const double two_pi = 6.283185307179586476925286766559, euler_e = 2.718281828459045235360287471352;
+    const double euler_e = EULER_E;
     double s = 0.;
     switch (obj) {
     case BBO_OBJ_SPHERE:
@@ -260,7 +262,7 @@ inline double builtin_objective_host(int obj, int n, const double *x, const doub
         }
         return s;
     case BBO_OBJ_RASTRIGIN:
-        for (int i = 0; i < n; i++) s += x[i] * x[i] - 10. * std::cos(two_pi * x[i]);
+        for (int i = 0; i < n; i++) s += x[i] * x[i] - 10. * cos_2pi(x[i]);
         return 10. * n + s;
     case BBO_OBJ_ELLIPSOID:
         for (int i = 0; i < n; i++) s += aux[i] * (x[i] * x[i]);
@@ -269,7 +271,7 @@ inline double builtin_objective_host(int obj, int n, const double *x, const doub
         double cs = 0.;
         for (int i = 0; i < n; i++) {
             s += x[i] * x[i];
-            cs += std::cos(two_pi * x[i]);
+            cs += cos_2pi(x[i]);
         }
         return -20. * std::exp(-0.2 * std::sqrt(s / n)) - std::exp(cs / n) + 20. + euler_e;
     }

@@ -38,11 +38,21 @@ constexpr double EULER_E = 2.718281828459045235360287471352;
 // cos(2 pi x) for any finite x: x is reduced to t = x - rint(x) in [-1/2, 1/2] EXACTLY, then to
 // an octant, then the fdlibm kernel polynomials on [0, pi/4] -- no Payne-Hanek path, about a
 // third of ocml's cos(2 pi x) (which first rounds 2 pi x).  |error| <= 2 ulp of 1.
-__device__ inline double cos_2pi(double x)
+// __host__ too: builtin_objective_host (bbo_common.hpp) evaluates single points with this very
+// function, so the library has ONE cosine (built with -ffp-contract=off every operation below is one
+// IEEE operation on either side: the host's value is the device's to the bit).
+__host__ __device__ inline double cos_2pi(double x)
 {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    // host: (int) of a NaN is undefined in C++ (the device's conversion saturates and the NaN comes
+    // out through the polynomials); a non-finite x gives NaN, as std::cos did
+    if (!__builtin_isfinite(x)) return x - x;
+#endif
     double t = fabs(x - rint(x));            // [0, 1/2], exact
     const double v = t * 8.;                 // [0, 4]
     int k = (int) v;                         // octant 0..4 (4 only at t = 1/2)
+    // (the clamp keeps k an octant index but decides no value: at t = 1/2, k = 3 gives f = 1, flipped
+    // to 0, and k = 4 would give f = 0 unflipped; q = 2 and the result -cos 0 = -1 either way)
     k = k > 3 ? 3 : k;
     double f = v - (double) k;               // [0, 1]
     const bool odd = (k & 1) != 0;

@@ -729,6 +729,18 @@ void bbo_mayfly_params_default(bbo_mayfly_params *p);   /* 1, 1.5, 1.5, 2, 5, 0.
 int bbo_mayfly_configure(bbo_handle h, const bbo_mayfly_params *p);
 int bbo_mayfly_inject_draws(bbo_handle h, const double *table, int count);
 
+/* ---- diagnostics -------------------------------------------------------------------------------
+ * bbo_probe_objective: built-in `objective` at `rows` points of `n` coordinates (X, rows x n, host
+ * memory) through ONE of the device forms the kernels evaluate it in; f_out takes the rows values as
+ * the form returns them (no NaN guard).  For tests of the forms at points no optimizer draws.
+ *   form 0  eval_row_group<16>, the row in LDS              1  eval_row_group<64>, the row in global
+ *        2  eval_row_group<64>, the LDS row swizzled           memory with ld = n rounded up to even
+ *        3  eval_row_group<16> unrolled by 4 (CCPSO)        4  eval_frag_rows<8>, MFMA accumulator layout
+ * Whatever lies behind a row's n coordinates holds 1e300, in every form.  n in [1, 1024], rows in [1, 65536]; form 4 takes n <= 128 and the
+ * objectives without transcendental terms (sphere, rosenbrock, ellipsoid, cigar, discus, schwefel12).
+ * BBO_ERR_ARG otherwise, with the reason in bbo_last_error(NULL). */
+int bbo_probe_objective(int objective, int form, int n, int rows, const double *X, double *f_out);
+
 const char *bbo_last_error(bbo_handle h);   /* h may be NULL: last creation error */
 const char *bbo_version(void);
 int bbo_device_count(void);

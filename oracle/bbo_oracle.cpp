@@ -1054,6 +1054,7 @@ void orc_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c
     bbo_philox(seed, c0, c1, c2, c3, out);
 }
 double orc_log_unit(double u) { return bbo_log_unit(u); }
+double orc_cos_2pi(double x) { return bbo_cos_2pi(x); }
 void orc_sincos_turn(double t, double *s, double *c) { bbo_sincos_turn(t, s, c); }
 double orc_exp_neg(double s) { return bbo_exp_neg(s); }
 void orc_normal_quad(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, double *z)

@@ -177,6 +177,9 @@ class _Lib:
                 f("sincos_turn").argtypes = [C.c_double, C.POINTER(C.c_double),
                                              C.POINTER(C.c_double)]
                 f("sincos_turn").restype = None
+            if hasattr(L, p + "cos_2pi"):
+                f("cos_2pi").argtypes = [C.c_double]
+                f("cos_2pi").restype = C.c_double
             if hasattr(L, p + "exp_neg"):
                 f("exp_neg").argtypes = [C.c_double]
                 f("exp_neg").restype = C.c_double
