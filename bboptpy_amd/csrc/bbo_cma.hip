@@ -352,6 +352,10 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
         BDp_.upload(eyeP.data(), P * ld2);
     }
     S_.alloc((size_t) P * c.mu_pad);
+    // cma_gram128s' per-row coefficients, where cma_rank_sort can write them (zeroed: no stamp is valid)
+    const bool coef_table = dense && c.ld == 128;
+    coef_tab_.alloc(coef_table ? (size_t) P * coef_tab_chunks(c.lambda_pad) * 2 * G128_CH : 0);
+    coef_stamp_.alloc(coef_table ? P : 0);
     gram_part_.alloc((size_t) P * c.splits * (dense ? ld2 : ld));   // sep: second moments, [ld]; Cholesky: unused
     mean_part_.alloc((size_t) P * c.splits * ld);
     hist_best_.alloc((size_t) P * c.hlen);
@@ -425,6 +429,7 @@ void CmaEngine::init(int n, const double *lower, const double *upper, const doub
     d.C = C_.p; d.B = B_.p; d.D = D_.p; d.isc = isc_.p; d.BDp = BDp_.p; d.ISp = ISp_.p;
     d.A = chol ? A_.p : nullptr;
     d.chol_repairs = chol ? chol_repairs_.p : nullptr;
+    d.coef_tab = coef_tab_.p; d.coef_stamp = coef_stamp_.p;
     d.S = S_.p; d.zn2 = zn2_.p; d.csep = csep_.p; d.gram_part = gram_part_.p; d.mean_part = mean_part_.p;
     d.hist_best = hist_best_.p; d.hist_kth = hist_kth_.p; d.eig_work = eig_work_.p;
     d.weights = weights_.p; d.lower = lower_.p; d.upper = upper_.p; d.aux = aux_.p;
@@ -1032,6 +1037,7 @@ void CmaEngine::inject_normals(const double *z, int count)
 {
     BBO_REQUIRE(inited_, "inject_normals before init");
     rank_wrote_norms_ = false;
+    coef_tab_forget();
     if (!z) {
         d_.zinject = nullptr;
         return;
@@ -1041,6 +1047,13 @@ void CmaEngine::inject_normals(const double *z, int count)
     if (zinject_.count != want) zinject_.alloc(want);
     zinject_.upload(z, want);
     d_.zinject = zinject_.p;
+}
+
+// The stamps of cma_rank_sort's coefficient table go back to 'never', in stream order and without a wait:
+// a ranking that went before a change of the state from outside does not vouch for an update after it.
+void CmaEngine::coef_tab_forget()
+{
+    if (coef_stamp_.p) BBO_HIP(hipMemsetAsync(coef_stamp_.p, 0, coef_stamp_.count * sizeof(int), stream_));
 }
 
 void CmaEngine::after_chunk(bool in_run)
@@ -1285,6 +1298,12 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     }
     if (k == "small_fused") return o.one(small_fused_ ? 1 : 0);           // the last generation or chunk ran in cma_small_generations
     if (k == "splits") return o.one(c.splits);                            // Gram slabs per population
+    if (k == "gram_coef_stamp") {      // it + 1 of the last generation whose cma_rank_sort left cma_gram128s its
+                                       // coefficient table: equal to "it" after a generation that took the table, 0 = never
+        int stamp = 0;
+        if (coef_stamp_.p) coef_stamp_.download(&stamp, 1, p);
+        return o.one(stamp);
+    }
     if (k == "eig_mw_reserved") return o.one((double) mw_reserved_);       // this engine's share of the device's ...
     if (k == "eig_mw_capacity") {                                        // ... budget of spread workgroups
         MwBudget &b = MwBudget::get();
@@ -1326,6 +1345,7 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
 {
     enter_population("set()", p);
     rank_wrote_norms_ = false;      // (S of a ranking before this call may not match the new state)
+    coef_tab_forget();              // (nor its coefficient table)
     const CmaConst &c = c_;
     const size_t ld = c.ld, n = c.n;
     auto vec_in = [&](DevBuf<double> &b) {          // n -> [P][ld]

@@ -96,6 +96,8 @@ enum CmaDbg : int {
     DBG_SAMPLE_4WAVES    = 268435456,  // n > 128: the four-wavefront cma_sample_eval where <1, 16> would run
     DBG_TRED_ALL_SPREAD  = 536870912,  // spread reduction: no cma_tred_tail (128 < n <= 256), no cma_tred_mw_chain
                                        // (n > 256)
+    DBG_GRAM_LOOKUP      = 1073741824, // cma_gram128s looks its coefficients up (rank, then weights and S) where it would
+                                       // take cma_rank_sort's table, and cma_rank_sort writes none
     // every bit cma_eigen / cma_eigen_r1 read inside the kernel (bbo_eig.hpp, bbo_eig_dc.hpp), and
     // DBG_EIG_ONE_WG, which asks for them.  The fixed-shape builds of n = ld = 128 read none, so any of these
     // -- and DBG_EIG_GENERIC128 -- keeps the generic kernel: a bit added to those two files belongs in this mask.
@@ -121,6 +123,10 @@ struct CmaDev {
     double *S;          // [P][mu_pad]  whitened squared norms of the worst mu
     double *csep;       // [P][ld] diagonal covariance of the separable variant (D = its sqrt)
     double *zn2;        // [P][lambda_pad] ||z||^2 of every candidate (cma_sample_eval128 only)
+    double *coef_tab;   // [P][ceil(lambda_pad / 32)][2][32] ld = 128: the Gram coefficient v and the mean weight w of
+                        // every ROW, in chunks of 32 rows (v of the 32, then w), written by cma_rank_sort for
+                        // cma_gram128s (null: no table); rows >= lambda hold zeros
+    int *coef_stamp;    // [P]          it + 1 of the generation whose ranking wrote coef_tab, 0 = never
     double *gram_part;  // [P][splits][ld][ld]
     double *mean_part;  // [P][splits][ld]
     double *hist_best, *hist_kth;     // [P][hlen]
@@ -298,7 +304,9 @@ private:
     DevBuf<double> zn2_, csep_, A_;
     DevBuf<double> X_, f_, xmean_, xold_, pc_, ps_, C_, B_, D_, isc_, BDp_, ISp_, S_,
             gram_part_, mean_part_, hist_best_, hist_kth_, eig_work_, weights_, zinject_, zrecord_;
-    DevBuf<int> rank_, order_, chol_repairs_;
+    DevBuf<double> coef_tab_;
+    DevBuf<int> rank_, order_, chol_repairs_, coef_stamp_;
+    void coef_tab_forget();         // no ranking's coefficient table is valid any more (set(), inject_normals())
     DevBuf<long long> stamps_;
     int *mw_fail_host_ = nullptr;   // pinned, device-visible: raised by a spread reduction that timed out
     long mw_reserved_ = 0;          // workgroups this engine holds of the device's MwBudget

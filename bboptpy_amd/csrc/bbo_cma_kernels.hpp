@@ -651,6 +651,10 @@ __global__ __launch_bounds__(256) void cma_rank64(CmaDev d, CmaConst c)
 // merge path for 2048 / 4096 padded keys (`merge`: two buffers, 24 m bytes of dynamic LDS), the
 // bitonic network otherwise (12 max(m, 1024) bytes): rank_sort_merges, bbo_rank.hpp.
 // grid (P), 1024 threads (256 for m <= 256)
+constexpr int G128_CH = 32;          // cma_gram128 / cma_gram128s (below): rows per chunk
+// CmaDev::coef_tab, which this kernel writes for cma_gram128s: chunks of 2 * G128_CH doubles per population
+__host__ __device__ constexpr int coef_tab_chunks(int lambda_pad) { return (lambda_pad + G128_CH - 1) / G128_CH; }
+
 static_assert((int) DBG_RANK_COUNT32 == RANK_DBG_COUNT32 && (int) DBG_RANK_COUNT_NO64 == RANK_DBG_COUNT_NO64
         && (int) DBG_RANK_BITONIC == RANK_DBG_BITONIC, "bbo_rank.hpp reads these bits of CmaDev::dbg");
 
@@ -685,6 +689,44 @@ __global__ __launch_bounds__(1024) void cma_rank_sort(CmaDev d, CmaConst c, int 
         sc->ibw[2] = idx[L - 2]; sc->ybw[2] = keys[L - 2];
         sc->ibw[3] = idx[L - 1]; sc->ybw[3] = keys[L - 1];
         sc->fev += L;   // base_cmaes.cpp:218
+    }
+    // cma_gram128s' coefficients of every ROW (rank_coefficients, the same expressions in the same order:
+    // the same bits), once per population here, where the ranking sits in LDS, instead of by every
+    // wavefront of every slab there.  Only where the whitened norms are final now (written above, or not
+    // needed): when cma_whiten* comes after this kernel the stamp stays behind and the slab looks them up.
+    // The table is written ROW by row, 256-byte runs: the rank of a row comes from the inverse of idx, built
+    // in LDS over the sorted keys, which nothing reads any more (scattered by rank through idx, as 8-byte
+    // stores to 2 lambda different lines, the same table cost 26 us of a 41 us launch at M).
+    if (d.coef_tab && !(d.dbg & DBG_GRAM_LOOKUP) && (c.variant != 1 || (c.use_zn && sc->basis_ok))) {
+        const double cmu1 = c.variant == 1 ? c.cmu + c.cneg * (1. - c.alphaold) : c.cmu;
+        const double s2 = sc->sigma * sc->sigma;
+        const double *zn2 = d.zn2 + (size_t) p * c.lambda_pad;
+        int *inv = reinterpret_cast<int*>(keys);       // [lambda] <= 2 m ints
+        __syncthreads();                               // (thread 0 has read the keys)
+        for (int r = threadIdx.x; r < c.lambda; r += blockDim.x) inv[idx[r]] = r;
+        __syncthreads();
+        // (the layout of cma_gram128s' strip: [chunk of G128_CH rows][v | w][row of the chunk])
+        const int rows = coef_tab_chunks(c.lambda_pad) * G128_CH;
+        double *tab = d.coef_tab + (size_t) p * rows * 2;
+        for (int row = threadIdx.x; row < rows; row += blockDim.x) {
+            double pv = 0., pw = 0.;                   // (the padding rows: exact zeros)
+            if (row < c.lambda) {
+                const int r = inv[row];
+                if (r < c.mu) {
+                    pw = d.weights[r];
+                    pv = cmu1 * pw;
+                } else if (c.variant == 1 && r >= c.lambda - c.mu) {
+                    const int k = c.lambda - 1 - r;         // S[k] over S[mu - 1 - k], the latter this row's own
+                    const double sk = s2 * zn2[idx[c.lambda - c.mu + k]], sm = s2 * zn2[row];
+                    const double ycoeff = sk / fmax(sm, 1e-8);
+                    pv = -c.cneg * d.weights[k] * ycoeff;
+                }
+            }
+            double *t = tab + (row / G128_CH) * 2 * G128_CH + row % G128_CH;
+            t[0] = pv;
+            t[G128_CH] = pw;
+        }
+        if (threadIdx.x == 0) d.coef_stamp[p] = sc->it + 1;
     }
 }
 
@@ -1064,7 +1106,6 @@ __global__ __launch_bounds__(256) void cma_gram(CmaDev d, CmaConst c, int ldy)
 //     wave 3: (0,0) (1,0) (1,1), lower triangle of rows 5-7 x cols 5-7
 // grid (splits, P), 256 threads, 2 workgroups per CU
 // ---------------------------------------------------------------------------
-constexpr int G128_CH = 32;          // rows per chunk
 constexpr int G128_PACE = 2;         // cma_gram128s: chunks between two pacing barriers (1, 2: 366 us; 4: 370; 8: 371; none: 374)
 constexpr int G128_LDY = 128 + 16;
 constexpr int G128_TI[4][9] = { { 5, 5, 5, 6, 6, 6, 7, 7, 7 }, { 2, 2, 2, 3, 3, 3, 4, 4, 4 },
@@ -1253,7 +1294,7 @@ __global__ __launch_bounds__(256, 2) void cma_gram128(CmaDev d, CmaConst c)
 // ---------------------------------------------------------------------------
 template<int WV>
 __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &c, int p, int s,
-        double *coef, int lane)
+        double *coef, int lane, bool use_tab)
 {
     const CmaScal *sc = d.scal + p;
     const double *Xp = d.X + (size_t) p * c.lambda_pad * 128;
@@ -1290,24 +1331,34 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
         for (int i = 0; i < 8; i++)
             if (g128_needs_y(WV, i)) ring[slot][i] = src[lane_off + 16 * i];
     };
-    // Coefficients of a chunk's 32 rows (rank_coefficients, same arithmetic): lanes 0..31 look
-    // them up, the LDS strip hands them round.  The look-up is a chain of two dependent loads; it
-    // runs TWO chunks ahead, one link per chunk, branch-free with clamped indices -- the memory
-    // counter retires in order, so a load that is consumed long after it was issued costs no wait,
-    // while one consumed at once would drain the whole prefetch ring first.
+    // Coefficients of a chunk's 32 rows, handed round by the LDS strip.  The memory counter retires
+    // in order, so a load that is consumed long after it was issued costs no wait, while one consumed
+    // at once -- by as little as a select on its result -- drains the whole prefetch ring first and
+    // adds a round trip of its own.  Hence NO instruction of the chunk loop touches a value loaded
+    // later than the ring's four k-steps: every load below is issued in one chunk's tail with clamped
+    // indices, branch-free, and its result -- together with the `exists` flag it was clamped by --
+    // is first used in the NEXT chunk's tail, behind eight k-steps of younger ring loads.
+    //   table (use_tab): cma_rank_sort has written the finished pair (v, w) of every row for this
+    //     generation (CmaDev::coef_tab, stamped) in the strip's own layout: one coalesced 512-byte
+    //     load per chunk, one chunk ahead, stored to the strip as it comes; no arithmetic at all.
+    //   look-up (no valid stamp: counting / wave rank, norms from cma_whiten*; DBG_GRAM_LOOKUP):
+    //     lanes 0..31, rank_coefficients' arithmetic; a chain of two dependent loads that runs TWO
+    //     chunks ahead, one link per chunk.
+    // The choice is uniform over the workgroup and made once (cma_gram128s); both forms share the
+    // register pair wa and the one chunk loop.
     const double cmu1 = c.variant == 1 ? c.cmu + c.cneg * (1. - c.alphaold) : c.cmu;
     const double *Sp = d.S + (size_t) p * c.mu_pad;
-    int rk = 0;                           // link 1: the rank of the row (chunk ch + 2)
+    int rk = 0;                           // link 1: the rank of the row (chunk ch + 2), as loaded ...
+    bool rk_ok = false;                   // ... and whether the row exists: applied by link 2
     int rk2 = 0;                          // ... one chunk on, while link 2 is in flight
     double wa = 0., sk = 1., sm = 1.;     // link 2: weights[.], S[k], S[mu - 1 - k] (chunk ch + 1)
     auto coef_link1 = [&](int ch) {
         const int row = row0 + ch * G128_CH + lane;
-        const bool ok = lane < G128_CH && ch < nch && row < c.lambda;
-        rk = rank[ok ? row : 0];
-        if (!ok) rk = -1;
+        rk_ok = lane < G128_CH && ch < nch && row < c.lambda;
+        rk = rank[rk_ok ? row : 0];       // (not touched here: see above)
     };
     auto coef_link2 = [&]() {             // from the rank loaded one chunk ago
-        rk2 = rk;
+        rk2 = rk_ok ? rk : -1;
         const bool pos = rk2 >= 0 && rk2 < c.mu;
         const int k = min(max(c.lambda - 1 - rk2, 0), c.mu - 1);
         wa = d.weights[pos ? rk2 : k];
@@ -1328,6 +1379,28 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
             coef[buf * 2 * G128_CH + G128_CH + lane] = pw;
         }
     };
+    // the table's form of the same: tab_load(ch) asks for chunk ch, tab_put writes what the last
+    // tab_load asked for.  The table is laid out like the strip ([chunk][v | w][row of chunk], slabs
+    // begin on chunk boundaries) and holds zeros for every row from lambda to the end of the last
+    // chunk, so there is nothing to mask; a chunk past the slab is never swept, its index is only
+    // kept inside the table.
+    const double *tabp = d.coef_tab + ((size_t) p * coef_tab_chunks(c.lambda_pad) + row0 / G128_CH) * 2 * G128_CH;
+    // (the address is a scalar base plus the lane's constant byte offset, ready in a register: formed
+    // per chunk in vector registers it took wa's own pair as scratch, which waited for the look-up's
+    // load pending there -- the ring again; the empty asm keeps the sum out of the loop's preheader,
+    // where it would be a 64-bit pointer per lane and two registers the kernel does not have)
+    // This, the order of the tail (strip writes before loads) and the choice by execution mask are
+    // answers to what ONE compiler release does with registers, not properties of the source: none of
+    // them changes a result, and tests/test_isa_gram128s.py reads the outcome off the built library.
+    // When that test fails after a compiler upgrade, read the chunk loops' tails again and expect to
+    // redo these three.
+    unsigned off = 8u * lane;
+    auto tab_load = [&](int ch) {
+        asm volatile("" : "+v"(off));     // (in place: reset from a constant, the copy would land in wa's pair)
+        const char *q = reinterpret_cast<const char*>(tabp + min(ch, nch - 1) * 2 * G128_CH);
+        wa = *reinterpret_cast<const double*>(q + off);
+    };
+    auto tab_put = [&](int buf) { coef[buf * 2 * G128_CH + lane] = wa; };
     auto sweep_step = [&](int slot, double vk, double wk) {
         double y[8], a[8];
         // (no masks: columns >= n are zero in X and in the mean alike, rows >= lambda have
@@ -1350,12 +1423,22 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
     };
 
     // prologue: coefficients of chunks 0 and 1, the first four k-steps
-    coef_link1(0);
-    coef_link2();
-    put_coef(0);
-    coef_link1(1);
-    coef_link2();                         // (chunk 1's values: written to the strip at the end of chunk 0)
-    coef_link1(2);
+    // (the lanes that look up are picked by the EXECUTION MASK, the look-up is not branched round: as
+    // one of two uniform branches its loads landed in scratch registers and were copied home where the
+    // branches join -- a use of the youngest load, the drain again)
+    const int looks = use_tab ? 0 : G128_CH;
+    if (lane < looks) {
+        coef_link1(0);
+        coef_link2();
+        put_coef(0);
+        coef_link1(1);
+        coef_link2();                     // (chunk 1's values: written to the strip at the end of chunk 0)
+        coef_link1(2);
+    } else if (use_tab) {
+        tab_load(0);
+        tab_put(0);
+        tab_load(1);                      // (written to the strip at the end of chunk 0)
+    }
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) load_step(0, ks, ks);
     wave_sync();
@@ -1380,9 +1463,15 @@ __device__ __forceinline__ void gram128_stream(const CmaDev &d, const CmaConst &
             // the scheduler would, the four slots are waited for at once and nothing is ahead)
             __builtin_amdgcn_sched_barrier(0);
         }
-        put_coef(buf ^ 1);                // chunk ch + 1, loaded during chunk ch - 1 / the prologue
-        coef_link2();                     // chunk ch + 2, from the rank loaded a chunk ago
-        coef_link1(ch + 3);
+        // (both forms write the strip before either loads: they share wa, and a read of it behind the
+        // other form's load would wait for that load -- the compiler does not tell the lanes apart)
+        if (lane < looks) put_coef(buf ^ 1);      // chunk ch + 1, loaded during chunk ch - 1 / the prologue
+        else if (use_tab) tab_put(buf ^ 1);
+        if (lane < looks) {
+            coef_link2();                 // chunk ch + 2, from the rank loaded a chunk ago
+            coef_link1(ch + 3);
+        } else if (use_tab)
+            tab_load(ch + 2);
         wave_sync();
         // Pacing, not synchronisation: the four wavefronts share no data, but they read the same
         // rows, and left alone they drift apart until a row one of them fetched has left L1 / L2
@@ -1401,11 +1490,13 @@ __global__ __launch_bounds__(256, 2) void cma_gram128s(CmaDev d, CmaConst c)
     if (pop_frozen(c, d.scal + p)) return;
     __shared__ double coef[4][2 * 2 * G128_CH];      // per wavefront: [buffer][v | w][row of chunk]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // this generation's ranking left its coefficient table (cma_rank_sort): one scalar test per workgroup
+    const bool use_tab = d.coef_tab && !(d.dbg & DBG_GRAM_LOOKUP) && d.coef_stamp[p] == d.scal[p].it + 1;
     switch (wave) {
-    case 0: gram128_stream<0>(d, c, p, s, coef[0], lane); break;
-    case 1: gram128_stream<1>(d, c, p, s, coef[1], lane); break;
-    case 2: gram128_stream<2>(d, c, p, s, coef[2], lane); break;
-    default: gram128_stream<3>(d, c, p, s, coef[3], lane); break;
+    case 0: gram128_stream<0>(d, c, p, s, coef[0], lane, use_tab); break;
+    case 1: gram128_stream<1>(d, c, p, s, coef[1], lane, use_tab); break;
+    case 2: gram128_stream<2>(d, c, p, s, coef[2], lane, use_tab); break;
+    default: gram128_stream<3>(d, c, p, s, coef[3], lane, use_tab); break;
     }
 }
 
