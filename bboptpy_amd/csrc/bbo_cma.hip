@@ -530,6 +530,9 @@ SampleRoute CmaEngine::sample_route() const
         is(c.variant == 3 && chol_tri_ ? SK_EVAL128_TRI : SK_EVAL128, (c.lambda_pad + r.rows_per_wg - 1) / r.rows_per_wg,
                 512, 128 * 1024);
         r.full = nothing_to_guard() ? 1 : 0;     // the lean build of the tile loop where nothing needs guarding (M, C3)
+        // ... and its transposed form (coordinates along the accumulators, the objective in the lane) for the
+        // objectives eval_frag_cols offers and for none on the device; Schwefel 1.2 scans across lanes: row layout
+        r.transposed = r.full && !sample128_rowlayout_ && (c.obj < 0 || frag_cols_objective_ok(c.obj)) ? 1 : 0;
     } else if (c.ld == 128 && (long) c.npop * (c.lambda_pad / 16) <= sample_wide_max_tiles_)
         // one population at a time: a 16-row tile per WORKGROUP, one column tile per wavefront (the
         // form C5's handful of candidates takes at n = 256) -- a wavefront's chain is 32 MFMAs and
@@ -569,8 +572,8 @@ void CmaEngine::launch_sample_eval()
     case SK_SEP_SUM: go(sep_sum_kernel<0>(c_.obj), 0); break;
     case SK_SEP_SUM4: go(sep_sum_kernel<4>(c_.obj), 0); break;
     case SK_SEP_64: go(sep_sample_eval<64>, 140 * 1024); break;
-    case SK_EVAL128: go(cma_sample_eval128, 128 * 1024, r.rows_per_wg, r.full); break;
-    case SK_EVAL128_TRI: go(cma_sample_eval128_tri, 128 * 1024, r.rows_per_wg, r.full); break;
+    case SK_EVAL128: go(cma_sample_eval128, 128 * 1024, r.rows_per_wg, r.full, r.transposed); break;
+    case SK_EVAL128_TRI: go(cma_sample_eval128_tri, 128 * 1024, r.rows_per_wg, r.full, r.transposed); break;
     case SK_TILE8: go(cma_sample_eval<1, 8>, 0); break;
     case SK_TILE8_TRI: go(cma_sample_eval<1, 8, true>, 0); break;
     case SK_EVAL64_1_8: go(cma_sample_eval64<1, 8>, 0); break;
@@ -1227,6 +1230,16 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
         }
         return c.mu;
     }
+    if (k == "S") {          // the whitened squared norms of the worst mu, as the last ranking or update left them
+        if (c.variant != 1) throw Error(BBO_ERR_KEY, "'S' belongs to ActiveCMAES");
+        if (out && cap >= c.mu) S_.download(out, c.mu, (size_t) p * c.mu_pad);
+        return c.mu;
+    }
+    if (k == "zn2") {        // ||z||^2 of every candidate, where the last sampler handed it down (else stale)
+        if (!zn2_.p) return 0;
+        if (out && cap >= c.lambda) zn2_.download(out, c.lambda, (size_t) p * c.lambda_pad);
+        return c.lambda;
+    }
     if (k == "zlast") {
         const size_t cnt = (size_t) c.lambda * n;
         if (!zrecord_.p) return 0;
@@ -1291,6 +1304,8 @@ int CmaEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "rank_route") return o.one(last_rank_);                      // the form of the last launch_rank: RankKernel
     if (k == "sample_route") return o.one(last_sample_.k);                // the last launch_sample_eval: SampleKernel, -1 before any
     if (k == "sample_lean") return o.one(last_sample_.full);              // ... took a lean build
+    if (k == "sample_transposed") return o.one(last_sample_.transposed);  // ... and the transposed tile loop
+    if (k == "sample128_rowlayout") return o.one(sample128_rowlayout_ ? 1 : 0);
     if (k == "update_route") {                                            // the last launch_update in launch order: UpdateKernel ids
         double ids[sizeof(last_update_.step) / sizeof(last_update_.step[0])];
         for (int i = 0; i < last_update_.count; i++) ids[i] = last_update_.step[i].k;
@@ -1440,6 +1455,10 @@ int CmaEngine::set(const std::string &k, int p, const double *in, int count)
     }
     if (k == "sample_wide_max") {  // (tuning: at most this many 16-row tiles take the tile-per-workgroup sampler)
         sample_wide_max_tiles_ = (long) in[0];
+        return 1;
+    }
+    if (k == "sample128_rowlayout") {   // 1 = cma_sample_eval128's row-layout tile loop, 0 = the transposed one (same bits)
+        sample128_rowlayout_ = in[0] != 0.;
         return 1;
     }
     if (k == "sample128_min") {    // (tuning: candidates in flight from which cma_sample_eval128 draws)

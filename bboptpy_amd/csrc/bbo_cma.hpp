@@ -191,6 +191,8 @@ struct SampleRoute {
     int full;               // the lean build (get "sample_lean"): kernel argument of those two, the template
                             // argument of sep_sample_eval<64, 512, true>, always for sep_sample_sum
     bool writes_zn;         // the kernel hands down ||z||^2 of every candidate
+    int transposed;         // cma_sample_eval128 / _tri, lean build: the transposed tile loop (get "sample_transposed"):
+                            // kernel argument
 };
 
 // The kernels of one launch_update.  get "update_route" returns the ids of the last one in launch order:
@@ -292,9 +294,11 @@ private:
     long sample_wide_max_tiles_ = 512;       // n = 128: at most this many 16-row tiles take cma_sample_eval<1, 8>
     long sample128_min_rows_ = 256 * 128;   // candidates in flight from which cma_sample_eval128 is used
     bool chol_tri_ = true;             // CholeskyCMAES, n = 128: the triangular forms of the two wide samplers
+    bool sample128_rowlayout_ = false; // cma_sample_eval128 / _tri: the row-layout tile loop where the transposed one would run
     int split_maxp_ = 32;              // 64 < n <= 128: at most this many populations take the split decomposition
     EigRoute last_route_ {};           // what the last launch_eigen did (get "eig_route", "eig_fixed128", "cov_fused")
-    SampleRoute last_sample_ { SK_NONE };   // what the last launch_sample_eval did (get "sample_route", "sample_lean")
+    SampleRoute last_sample_ { SK_NONE };   // what the last launch_sample_eval did (get "sample_route", "sample_lean",
+                                            // "sample_transposed")
     UpdateRoute last_update_ {};       // what the last launch_update did (get "update_route")
     bool small_fused_ = false;         // the last generation or chunk was a cma_small_generations launch (get "small_fused")
     int last_rank_ = -1;               // the form the last launch_rank took: RankKernel (get "rank_route"), -1 before

@@ -435,12 +435,75 @@ __device__ inline void sample128_epilogue(const CmaDev &d, const CmaConst &c, in
     }
 }
 
+// The epilogue of the TRANSPOSED tile (round 11, FULL only).  With the two MFMA operands swapped the
+// accumulators hold the transpose: lane (fr, fk) has, of candidate rowbase + fr, operand rows fk + 4 r of
+// column block t -- and the workgroup's LDS copy of the operand is permuted inside every run of 16
+// (sample128_fill) so that operand row fk + 4 r of block t is coordinate 16 t + 4 fk + r.  A lane then
+// owns four ADJACENT coordinates of ONE candidate per block: the mean is two 16-byte LDS reads, the row
+// leaves in two 16-byte stores per block from one address (16 per tile for the 32 8-byte ones of the row
+// layout and their four bases), and the objective's neighbours and sums stay in the lane
+// (eval_frag_cols).  X, f and zn2 are the row layout's byte for byte.
+__device__ inline void sample128_epilogue_tr(const CmaDev &d, const CmaConst &c, int p, int rowbase,
+        double sigma, const d4_t (&acc)[8], int lane, const double *xm)
+{
+    const int fr = lane & 15, fk = lane >> 4;
+    const size_t row = (size_t) p * c.lambda_pad + rowbase + fr;
+    double2 *Xp = reinterpret_cast<double2*>(d.X + row * 128 + 4 * fk);
+    const double2 *xm2 = reinterpret_cast<const double2*>(xm + 4 * fk);
+    double x[8][4];
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const double2 m0 = xm2[8 * t], m1 = xm2[8 * t + 1];
+        x[t][0] = m0.x + sigma * acc[t][0];
+        x[t][1] = m0.y + sigma * acc[t][1];
+        x[t][2] = m1.x + sigma * acc[t][2];
+        x[t][3] = m1.y + sigma * acc[t][3];
+        Xp[8 * t] = double2 { x[t][0], x[t][1] };
+        Xp[8 * t + 1] = double2 { x[t][2], x[t][3] };
+    }
+    if (c.obj >= 0) {
+        double fv = eval_frag_cols<8>(c.obj, x, d.aux, lane);
+        if (fk == 0) {
+            if (fv != fv) fv = BBO_INF;      // NaN -> +inf
+            d.f[row] = fv;
+        }
+    }
+}
+
+// The packed operand of a population into the workgroup's LDS (512 threads, 128 KB).  transposed: inside
+// every run of 16 doubles -- the 16 operand rows a fragment holds for one k -- position m takes source
+// position 4 (m & 3) + (m >> 2), a 4 x 4 index transpose and its own inverse.  A property of this copy
+// only: BDp in HBM and every other reader keep the fragment order.
+__device__ inline void sample128_fill(double *bd, const double *bdp, int tid, int transposed)
+{
+    const double2 *src = reinterpret_cast<const double2*>(bdp);
+    if (transposed) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int e = 2 * (tid + 512 * i), m = e & 15;       // m even: the pair goes to T(m), T(m) + 4
+            const double2 v = src[tid + 512 * i];
+            double *dst = bd + (e & ~15) + 4 * (m & 3) + (m >> 2);
+            dst[0] = v.x;
+            dst[4] = v.y;
+        }
+    } else {
+        double2 *dst = reinterpret_cast<double2*>(bd);
+#pragma unroll
+        for (int i = 0; i < 16; i++) dst[tid + 512 * i] = src[tid + 512 * i];
+    }
+}
+
 // TRI: as in cma_sample_eval -- k-step i meets column tile t only while its block i >> 2 <= t
 // (36 of the 64 block pairs)
-template<bool FULL, bool TRI = false>
+// TR (with FULL): the MFMA operands swapped -- A[l & 15][l >> 4] and B[l >> 4][l & 15] are mirror images
+// per lane, so the draw, z[32] and the fragment reads are the same registers, every accumulator element is
+// the same chain of 32 accumulations over the same four products, and the tile comes out transposed for
+// sample128_epilogue_tr.  TRI skips whole 16-blocks, which the permutation of the LDS copy preserves.
+template<bool FULL, bool TRI = false, bool TR = false>
 __device__ __forceinline__ void sample_eval128_body(const CmaDev &d, const CmaConst &c,
         int rows_per_wg, double *bd, const double2 *ntab, const double *ftab, const double *xms)
 {
+    static_assert(FULL || !TR, "the transposed tile has no masked form");
     const int p = blockIdx.y, row0 = blockIdx.x * rows_per_wg;
     const CmaScal *sc = d.scal + p;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -498,7 +561,8 @@ __device__ __forceinline__ void sample_eval128_body(const CmaDev &d, const CmaCo
                 for (int t = 0; t < 8; t++) {
                     if (TRI && (i >> 2) > t) continue;
                     const double bv = (i & 3) == 0 ? pre[t] : frag(i, t);
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[i], bv, acc[t], 0, 0, 0);
+                    acc[t] = TR ? __builtin_amdgcn_mfma_f64_16x16x4f64(bv, z[i], acc[t], 0, 0, 0)
+                                : __builtin_amdgcn_mfma_f64_16x16x4f64(z[i], bv, acc[t], 0, 0, 0);
                 }
                 if ((i & 3) == 3) {
                     if (i + 1 < 32) {
@@ -541,58 +605,51 @@ __device__ __forceinline__ void sample_eval128_body(const CmaDev &d, const CmaCo
         zz += __shfl_xor(zz, 16, 64);
         zz += __shfl_xor(zz, 32, 64);
         if (fk == 0) d.zn2[(size_t) p * c.lambda_pad + row] = zz;
-        sample128_epilogue<FULL>(d, c, p, rowbase, sigma, acc, lane, xms);
+        if (TR) sample128_epilogue_tr(d, c, p, rowbase, sigma, acc, lane, xms);
+        else sample128_epilogue<FULL>(d, c, p, rowbase, sigma, acc, lane, xms);
     }
 }
 
 __global__ __launch_bounds__(512, 1) void cma_sample_eval128(CmaDev d, CmaConst c, int rows_per_wg,
-        int full)
+        int full, int transposed)
 {
     const int p = blockIdx.y;
     const CmaScal *sc = d.scal + p;
     if (pop_frozen(c, sc)) return;
     extern __shared__ __attribute__((aligned(16))) double bd[];
     const int tid = threadIdx.x;
-    {
-        const double2 *src = reinterpret_cast<const double2*>(d.BDp + (size_t) p * 128 * 128);
-        double2 *dst = reinterpret_cast<double2*>(bd);
-#pragma unroll
-        for (int i = 0; i < 16; i++) dst[tid + 512 * i] = src[tid + 512 * i];
-    }
+    sample128_fill(bd, d.BDp + (size_t) p * 128 * 128, tid, transposed);
     __shared__ double2 ntab[NORMAL_TABLE_N];
     __shared__ double ftab[NORMAL_FTABLE_N];
-    __shared__ double xms[128];
+    __shared__ __attribute__((aligned(16))) double xms[128];
     normal_table_fill(ntab, tid, 512);
     normal_ftable_fill(ftab, tid, 512);
     if (tid < 128) xms[tid] = d.xmean[(size_t) p * 128 + tid];
     __syncthreads();
-    if (full) sample_eval128_body<true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
+    if (transposed) sample_eval128_body<true, false, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
+    else if (full) sample_eval128_body<true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
     else sample_eval128_body<false>(d, c, rows_per_wg, bd, ntab, ftab, xms);
 }
 
 // the same kernel over a lower-triangular operand (CholeskyCMAES' factor)
 __global__ __launch_bounds__(512, 1) void cma_sample_eval128_tri(CmaDev d, CmaConst c, int rows_per_wg,
-        int full)
+        int full, int transposed)
 {
     const int p = blockIdx.y;
     const CmaScal *sc = d.scal + p;
     if (pop_frozen(c, sc)) return;
     extern __shared__ __attribute__((aligned(16))) double bd[];
     const int tid = threadIdx.x;
-    {
-        const double2 *src = reinterpret_cast<const double2*>(d.BDp + (size_t) p * 128 * 128);
-        double2 *dst = reinterpret_cast<double2*>(bd);
-#pragma unroll
-        for (int i = 0; i < 16; i++) dst[tid + 512 * i] = src[tid + 512 * i];
-    }
+    sample128_fill(bd, d.BDp + (size_t) p * 128 * 128, tid, transposed);
     __shared__ double2 ntab[NORMAL_TABLE_N];
     __shared__ double ftab[NORMAL_FTABLE_N];
-    __shared__ double xms[128];
+    __shared__ __attribute__((aligned(16))) double xms[128];
     normal_table_fill(ntab, tid, 512);
     normal_ftable_fill(ftab, tid, 512);
     if (tid < 128) xms[tid] = d.xmean[(size_t) p * 128 + tid];
     __syncthreads();
-    if (full) sample_eval128_body<true, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
+    if (transposed) sample_eval128_body<true, true, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
+    else if (full) sample_eval128_body<true, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
     else sample_eval128_body<false, true>(d, c, rows_per_wg, bd, ntab, ftab, xms);
 }
 

@@ -286,4 +286,92 @@ __device__ inline void eval_frag_rows(int obj, int n, const double (&x)[NT][4], 
     }
 }
 
+// ---------------------------------------------------------------------------
+// The same objectives on the TRANSPOSED accumulator tile (the MFMA operands swapped and the operand's
+// rows permuted, sample_eval128_body): x[t][r] is coordinate 16 t + 4 fk + r of candidate lane & 15,
+// fk = lane >> 4 -- four adjacent coordinates per lane and tile, the dimension exactly 16 NT.  The lane
+// sums class c = 4 fk + r (the coordinates c mod 16) in a[r], ascending in t: the partial sums a_c of
+// eval_frag_rows.  row16_sum pairs them, up to the order of the two terms of a sum, as
+//     F = (Q0 + Q2) + (Q1 + Q3),   Q_c = (a_c + a_{c+8}) + (a_{c+4} + a_{c+12}),
+// so one exchange with the lanes 32 away forms the inner pairs, one with the lanes 16 away forms Q_r in
+// every lane, and three additions in the lane form F: eval_frag_rows' bits (tests/test_sample_transposed.py
+// restates both).  The lanes of group 0 return their candidate's f (the other groups too, except for cigar
+// and discus, which take x0 from the lane).  The objective is one branch per tile.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline bool frag_cols_objective_ok(int obj)
+{
+    return obj == OBJ_SPHERE || obj == OBJ_ROSENBROCK || obj == OBJ_ELLIPSOID || obj == OBJ_CIGAR
+            || obj == OBJ_DISCUS;
+}
+
+template<int NT>
+__device__ inline double eval_frag_cols(int obj, const double (&x)[NT][4], const double *aux, int lane)
+{
+    const int fk = lane >> 4;
+    double a[4] = { 0., 0., 0., 0. };
+    switch (obj) {
+    case OBJ_SPHERE:
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) a[r] += x[t][r] * x[t][r];
+        break;
+    case OBJ_ROSENBROCK: {
+        // the right-hand neighbour sits in the lane for r < 3; coordinate 16 t + 4 fk + 4 is the first of
+        // the lanes 16 higher, and beyond group 3 the first of group 0's NEXT tile, so group 0 -- nobody
+        // reads its own-tile first value -- offers that one (eval_frag_rows' trick): one move per tile
+        const int up = ((lane + 16) & 63) << 2;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            const double xn3 = lane_read64(fk == 0 ? x[t + 1 < NT ? t + 1 : t][0] : x[t][0], up);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const double xj = x[t][r];
+                const double xn = r < 3 ? x[t][r < 3 ? r + 1 : r] : xn3;
+                const double tt = xn - xj * xj;
+                const double u = 1. - xj;
+                const double term = 100. * (tt * tt) + u * u;
+                // (the last coordinate has no neighbour: it adds 0., as in eval_frag_rows)
+                a[r] += (t == NT - 1 && r == 3 && fk == 3) ? 0. : term;
+            }
+        }
+        break;
+    }
+    case OBJ_ELLIPSOID: {
+        const double *w = aux + 4 * fk;
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) a[r] += w[16 * t + r] * (x[t][r] * x[t][r]);
+        break;
+    }
+    case OBJ_CIGAR:
+    case OBJ_DISCUS:
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const double sq = x[t][r] * x[t][r];
+                a[r] += (t == 0 && r == 0 && fk == 0) ? 0. : sq;
+            }
+        break;
+    default:
+        return 0.;
+    }
+    double q[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const double s = a[r] + __shfl_xor(a[r], 32, 64);
+        q[r] = s + __shfl_xor(s, 16, 64);
+    }
+    const double f = (q[0] + q[2]) + (q[1] + q[3]);
+    if (obj == OBJ_CIGAR || obj == OBJ_DISCUS) {
+        // x0: group 0's first value (the lanes that store f); eval_frag_rows' row sum of (x0, 0, .., 0) is
+        // x0 up to the sign of a zero, and it is squared
+        const double x0 = x[0][0];
+        return obj == OBJ_CIGAR ? x0 * x0 + 1.0e6 * f : 1.0e6 * (x0 * x0) + f;
+    }
+    return f;
+}
+
 } // namespace bbo

@@ -46,6 +46,15 @@ __device__ inline double dpp_mov(double v)
     return __hiloint2double(hi, lo);
 }
 
+// an fp64 value of another lane of the wavefront through the LDS crossbar (ds_bpermute: not an
+// instruction of the vector pipe); byte = 4 * the source lane, computed once by the caller
+__device__ inline double lane_read64(double v, int byte)
+{
+    const int lo = __builtin_amdgcn_ds_bpermute(byte, __double2loint(v));
+    const int hi = __builtin_amdgcn_ds_bpermute(byte, __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
 // xor butterfly over G lanes (a power of two, <= 64, contiguous in one wavefront): every lane of
 // the group returns the total
 template<int G>
