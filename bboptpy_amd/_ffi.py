@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
     ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
-    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY = range(25)
+    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA = range(26)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -150,6 +150,12 @@ class MayflyParams(C.Structure):
         + [("pgb", C.c_int), ("repair", C.c_int), ("substream", C.c_int)]
 
 
+class PikaiaParams(C.Structure):
+    """bbo_pikaia_params: the arguments of PIKAIA that bbo_params has no field for"""
+    _fields_ = [(k, C.c_double) for k in ("pcross", "pmut", "pmutmn", "pmutmx", "fdif")] \
+        + [(k, C.c_int) for k in ("imut", "irep", "ielite", "repair", "raw", "substream")]
+
+
 class Objective(C.Structure):
     _fields_ = [("kind", C.c_int), ("builtin", C.c_int), ("scalar", SCALAR_FN),
                 ("batch", BATCH_FN), ("user", C.c_void_p)]
@@ -218,6 +224,7 @@ EXTENSIONS = {
     "ssde": (SsdeParams, True, {"draws": _TABLE}),
     "acd": (AcdParams, True, {}),
     "mayfly": (MayflyParams, False, {"draws": _TABLE}),
+    "pikaia": (PikaiaParams, False, {"draws": _TABLE}),
 }
 
 

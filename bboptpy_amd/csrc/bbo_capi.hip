@@ -16,6 +16,7 @@
 #include "bbo_ssde.hpp"
 #include "bbo_acd.hpp"
 #include "bbo_mayfly.hpp"
+#include "bbo_pikaia.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -40,6 +41,7 @@ Optimizer* make_crs_engine(const bbo_params &p);      // bbo_crs.hip
 Optimizer* make_ssde_engine(const bbo_params &p);     // bbo_ssde.hip
 Optimizer* make_acd_engine(const bbo_params &p);      // bbo_acd.hip
 Optimizer* make_mayfly_engine(const bbo_params &p);   // bbo_mayfly.hip
+Optimizer* make_pikaia_engine(const bbo_params &p);   // bbo_pikaia.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 void probe_objective(int obj, int form, int n, int rows, const double *X, double *f_out);   // bbo_probe.hip
 }
@@ -150,7 +152,7 @@ const struct {
     { BBO_ALGO_XNES, bbo::make_xnes_engine }, { BBO_ALGO_AMALGAM, bbo::make_amalgam_engine },
     { BBO_ALGO_SLPSO, bbo::make_slpso_engine }, { BBO_ALGO_CRS, bbo::make_crs_engine },
     { BBO_ALGO_SSDE, bbo::make_ssde_engine }, { BBO_ALGO_ACD, bbo::make_acd_engine },
-    { BBO_ALGO_MAYFLY, bbo::make_mayfly_engine },
+    { BBO_ALGO_MAYFLY, bbo::make_mayfly_engine }, { BBO_ALGO_PIKAIA, bbo::make_pikaia_engine },
 };
 
 bbo::ObjectiveSpec to_spec(const bbo_objective *o)
@@ -783,6 +785,33 @@ int bbo_mayfly_configure(bbo_handle h, const bbo_mayfly_params *p)
 int bbo_mayfly_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { engine_of<bbo::MayflyEngine>(h)->inject_draws(table, count); });
+}
+
+void bbo_pikaia_params_default(bbo_pikaia_params *p)
+{
+    if (!p) return;
+    /* pikaia.h:25-27 */
+    p->pcross = 0.85;
+    p->pmut = 0.005;
+    p->pmutmn = 0.0005;
+    p->pmutmx = 0.25;
+    p->fdif = 1.;
+    p->imut = 2;
+    p->irep = 1;
+    p->ielite = 0;
+    p->repair = 0;
+    p->raw = 0;
+    p->substream = 0;
+}
+
+int bbo_pikaia_configure(bbo_handle h, const bbo_pikaia_params *p)
+{
+    return configure_of<bbo::PikaiaEngine>(h, p, "bbo_pikaia_configure");
+}
+
+int bbo_pikaia_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { engine_of<bbo::PikaiaEngine>(h)->inject_draws(table, count); });
 }
 
 // diagnostics: no handle, so the message is the one of bbo_last_error(NULL)

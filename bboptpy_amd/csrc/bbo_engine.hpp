@@ -305,7 +305,7 @@ protected:
         if (obj.is_program())
             throw Error(BBO_ERR_ARG, std::string(who) + ": objective programs are supported by the CMA-ES family "
                     "(CMAES, ActiveCMAES, SepCMAES, CholeskyCMAES, IPOP / BIPOP over them) and the DE family "
-                    "(JADE, SHADE, SANSDE)");
+                    "(JADE, SHADE, SANSDE), and by PIKAIA");
     }
 
     // get / set of the keys every program-capable engine shares; < 0: not one of them

@@ -58,7 +58,10 @@ enum Stream : uint32_t {
     STREAM_MAYFLY_INIT = 39,
     STREAM_MAYFLY_R = 40,
     STREAM_MAYFLY_PERM = 41,
-    STREAM_MAYFLY_Z = 42
+    STREAM_MAYFLY_Z = 42,
+    STREAM_PIKAIA_INIT = 43,
+    STREAM_PIKAIA_MATE = 44,
+    STREAM_PIKAIA_LOCUS = 45
 };
 
 struct u32x4 {

@@ -123,7 +123,7 @@ class _ObjectiveBinding:
 
 
 PROGRAM_FAMILIES = ("CMAES, ActiveCMAES, SepCMAES, CholeskyCMAES (and IPopCMAES / BiPopCMAES over them), "
-                    "JADE, SHADE, SANSDE")
+                    "JADE, SHADE, SANSDE, PIKAIA")
 
 
 class MultivariateSearch:
@@ -1246,6 +1246,96 @@ class Mayfly(MultivariateSearch):
         attraction form), the shuffles of the offspring and of the mutated flies as permutations, and per
         mutated fly its nmd displaced genes and their normals; None: the device draws"""
         self._inject("bbo_mayfly_inject_draws", table)
+
+
+class PIKAIA(MultivariateSearch):
+    """PIKAIA(np, ngen, nd, pcross=0.85, imut=2, pmut=0.005, pmutmn=0.0005, pmutmx=0.25, fdif=1., irep=1,
+    ielite=0) -- the constructor of the reference's PikaiaSearch (pikaia.h:25-27), which it binds to no Python
+    class (the genetic algorithm of Charbonneau & Knapp, a translation of the HAO Fortran 77 code; pikaia.cpp).
+    A generation is np / 2 matings: two parents by a rank roulette, every coordinate of a phenotype in [0, 1)
+    encoded as nd decimal digits, one- or two-point crossover of the digit string with probability pcross, per
+    locus with probability pmut a fresh digit (imut 1-3) or, for imut 4-6 after a coin, +-1 with the carry into
+    the same gene (creep); then np evaluations, the ranking and, for imut 2, 3, 5, 6, the adjustment of pmut.
+    The default MINIMISES f over the box like every class here: the objective is handed
+    x = lower + u * (upper - lower) and the GA's fitness is -f(x), which is the reference run on that wrapped
+    function; a finite box is mandatory and `guess` is not read.  The only stop is ngen generations, and
+    converged is then True, as the reference reports.  n_evals is the reference's counter: np + ngen (np + 1),
+    whatever ielite is.  The reference's init stores the value of the last row only, so the first generation
+    selects on tied zeros; that is reproduced.  So is the signed denominator of imut 2 / 5: on a non-negative
+    objective (fitness <= 0) pmut only ever rises, reaches pmutmx in about ten generations and the run stalls;
+    use repair=True or imut 3 / 6 there.  irep 2 and 3 (steady state) are refused: they are a sequential walk
+    with the evaluations inside it and are not built.  np must be even (the reference leaves the last row of an
+    odd new population a zero vector), nd at most 9.  A callable is called np + ielite times per generation,
+    new row 1 first when ielite = 1; a NaN ranks worst.  Takes a DeviceObjective (whose NaN is stored as +inf: under
+    raw=True a +inf from a program ranks worst as well).
+    Extensions, keyword-only: `raw=True` is the literal reference (the objective sees u in the unit cube, the
+    box is ignored, +f is maximised); `repair=True` stores every initial value, counts np evaluations per
+    generation, keeps the stored value of the elite row and divides by |f_best + f_median| in imut 2 / 5;
+    `substream=s` lets population p draw from sub-stream s + p; `record_draws=True` keeps the draws of the
+    last generation in the layout of inject_draws (get_state("draws"))."""
+    _algo = _ffi.ALGO_PIKAIA
+    _extension = "pikaia"
+    _accepts_program = True
+    MAX_N, MAX_NP, MAX_ND = 512, 4096, 9
+
+    def __init__(self, np, ngen, nd, pcross=0.85, imut=2, pmut=0.005, pmutmn=0.0005, pmutmx=0.25, fdif=1., irep=1,
+                 ielite=0, *, repair=False, raw=False, record_draws=False, substream=0, **ext):
+        super().__init__(**ext)
+        np_, ngen, nd, imut, irep, ielite = int(np), int(ngen), int(nd), int(imut), int(irep), int(ielite)
+        if irep != 1:
+            raise ValueError("PIKAIA: irep must be 1 (full generational replacement): the steady-state plans "
+                             "irep = 2, 3 insert every child at once and the next select reads the ranks that "
+                             "insertion left, a sequential walk with the evaluations inside it that is not built")
+        if np_ < 2 or np_ > self.MAX_NP:
+            raise ValueError("PIKAIA: np must be in [2, %d]" % self.MAX_NP)
+        if np_ % 2:
+            raise ValueError("PIKAIA: np must be even: the reference leaves the last row of an odd new "
+                             "population unwritten, a zero vector")
+        if not 1 <= nd <= self.MAX_ND:
+            raise ValueError("PIKAIA: nd must be in [1, 9]: int(ph * 10**nd) overflows an int from nd = 10")
+        if not 1 <= imut <= 6:
+            raise ValueError("PIKAIA: imut must be in [1, 6]")
+        if ielite not in (0, 1):
+            raise ValueError("PIKAIA: ielite is 0 or 1")
+        for name, v in (("pcross", pcross), ("pmut", pmut), ("pmutmn", pmutmn), ("pmutmx", pmutmx)):
+            if not 0. <= float(v) <= 1.:
+                raise ValueError("PIKAIA: %s is a probability and must lie in [0, 1]" % name)
+        if float(pmutmn) > float(pmutmx):
+            raise ValueError("PIKAIA: pmutmn must not exceed pmutmx")
+        if not 0. <= float(fdif) <= 1.:
+            raise ValueError("PIKAIA: fdif must lie in [0, 1]: beyond 1 the weights of select turn negative")
+        if ngen < 1:
+            raise ValueError("PIKAIA: ngen must be >= 1")
+        if np_ + ngen * (np_ + 1) > 2 ** 31 - 1:
+            raise ValueError("PIKAIA: np + ngen (np + 1) evaluations must fit the int counter (INT_MAX)")
+        p = self._params
+        p.np, p.mfev, p.h = np_, ngen, nd       # (ngen and nd travel in `mfev` and `h`, include/bbopt_hip.h)
+        g = self._pikaia = _ffi.PikaiaParams()
+        g.pcross, g.pmut, g.pmutmn, g.pmutmx, g.fdif = float(pcross), float(pmut), float(pmutmn), float(pmutmx), float(fdif)
+        g.imut, g.irep, g.ielite = imut, irep, ielite
+        g.repair, g.raw, g.substream = int(bool(repair)), int(bool(raw)), int(substream)
+        self._record_draws = bool(record_draws)
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("PIKAIA: dimension must be in [1, %d]" % self.MAX_N)
+        if not self._pikaia.raw:
+            self._require_finite_box(n, lower, upper, "PIKAIA maps its phenotypes from the unit cube onto "
+                                     "[lower, upper] (raw=True hands the objective the unit cube itself)")
+        return n, lower, upper, guess
+
+    def table_len(self):
+        """the length of one population's table of inject_draws"""
+        return int(self.get_state("table_len")[0])
+
+    def inject_draws(self, table):
+        """the draws of the following generations, [populations][np / 2][69 + 2 (1 + 2 n nd)]: per mating the
+        uniform of the first parent, 64 slots for the attempts at the second, the crossover's coin, ispl, the
+        coin one- / two-point and ispl2, then per child the coin creep / uniform, n nd locus uniforms and n nd
+        value uniforms (new digit int(10 u), or creep step round(u) 2 - 1); -1 wherever the reference draws
+        nothing; None: the device draws"""
+        self._inject("bbo_pikaia_inject_draws", table)
 
 
 class APSO(MultivariateSearch):

@@ -66,7 +66,8 @@ typedef enum {
     BBO_ALGO_CRS = 21,         /* CrsSearch    src/multivariate/crs/crs.h             */
     BBO_ALGO_SSDE = 22,        /* SSDESearch   src/multivariate/de/ssde.h             */
     BBO_ALGO_ACD = 23,         /* ACD          src/multivariate/acd/acd.h             */
-    BBO_ALGO_MAYFLY = 24       /* MayflySearch src/multivariate/mayfly/mayfly.h       */
+    BBO_ALGO_MAYFLY = 24,      /* MayflySearch src/multivariate/mayfly/mayfly.h       */
+    BBO_ALGO_PIKAIA = 25       /* PikaiaSearch src/multivariate/pikaia/pikaia.h       */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -728,6 +729,60 @@ typedef struct {
 void bbo_mayfly_params_default(bbo_mayfly_params *p);   /* 1, 1.5, 1.5, 2, 5, 0.8, 1, 0.99, 0.8, 0.8, 0.1, 0.1, 0.01, 0.05, 0.95, 0, 0, 0 */
 int bbo_mayfly_configure(bbo_handle h, const bbo_mayfly_params *p);
 int bbo_mayfly_inject_draws(bbo_handle h, const double *table, int count);
+
+/* ---- PIKAIA (BBO_ALGO_PIKAIA): PIKAIA(np,ngen,nd,pcross=0.85,imut=2,pmut=0.005,pmutmn=0.0005,pmutmx=0.25,
+ * fdif=1.,irep=1,ielite=0), the genetic algorithm of Charbonneau & Knapp (pikaia.cpp, a translation of the HAO
+ * Fortran 77 code; the reference binds it to no Python class, the constructor at pikaia.h:25-27 is the
+ * signature).  In bbo_params travel np, ngen (as `mfev`: this engine's budget is generations) and nd (as `h`),
+ * the rest here.  Limits: n in [1, 512], np even in [2, 4096], nd in [1, 9], ngen >= 1 with np + ngen (np + 1)
+ * <= INT_MAX.  bbo_create refuses an odd np (the reference leaves the last row of the new population a zero
+ * vector), nd > 9 (int(ph 10^nd) overflows); bbo_pikaia_configure, legal between bbo_create and bbo_init,
+ * refuses irep = 2, 3 (the steady-state plans are a sequential walk with the evaluations inside it: not
+ * built), imut outside [1, 6], ielite outside {0, 1}, a probability outside [0, 1], pmutmn > pmutmx and fdif
+ * outside [0, 1]; bbo_init refuses a box that is not finite unless raw (BBO_ERR_ARG each, with the reason).
+ * The GA's state is the phenotype u in [0, 1)^n.  raw = 0 (the default): the objective is handed
+ * x = lower + u (upper - lower), one multiply and one add, and the fitness the GA maximises is -f(x): the
+ * reference run on that wrapped function.  raw = 1 is the literal reference: the objective sees u, the box is
+ * not read, the fitness is +f.  `guess` is not read.  Reproduced with repair = 0: init stores the value of the
+ * last row only, in the last slot, so the first generation selects on np - 1 tied zeros; a generation counts
+ * np + 1 evaluations; the relative fitness difference of imut 2 / 5 has a signed denominator, so on a
+ * non-negative objective (fitness <= 0) pmut only ever rises to pmutmx.  repair = 1 stores every initial value,
+ * counts np per generation, keeps the stored value of the elite row and divides by |f_best + f_median|.
+ * Ranking is the library's stable order (fitness ascending, ties by row), not the reference's quicksort: where
+ * values tie (after init, repair = 0) runs agree with the reference as distributions, not draw for draw.
+ * select's running sums are formed left to right once per generation and looked up by bisection; if rounding
+ * leaves the last sum under the dice the device takes the last row (np counting from 1 as the reference does,
+ * np - 1 in the 0-based keys; the reference would keep the index of the previous call).  The second parent is drawn at most 64 times and is then the next row cyclically.
+ * One bbo_iterate is one iterate() of the reference; the only stop is ig > ngen ("flag" 1, converged, as the
+ * reference reports).  bbo_solution returns the mapped best row of the population as it stands.  A host
+ * objective is called in the reference's order: new row 1 first when ielite = 1, then rows 1 .. np (np + ielite
+ * calls per generation; np under repair).  A NaN value ranks worst.  Objective programs are taken; a program's NaN is stored as +inf
+ * ("new_f"), so under raw = 1 a +inf from a program ranks worst as well.
+ * substream (an extension): population p draws from Philox sub-stream substream + p.
+ * bbo_pikaia_inject_draws: populations * table_len doubles that replace the generator in every following
+ * generation.  Per mating ("table_len" = (np / 2) (69 + 2 (1 + 2 n nd))): [0] the uniform of the first parent,
+ * [1, 65) those of the second, one per attempt, [65, 69) the crossover's coin, ispl, the coin one- / two-point,
+ * ispl2, then per child the coin creep / uniform, n nd locus uniforms and n nd value uniforms (the new digit
+ * int(10 u) or the creep step round(u) 2 - 1); -1 wherever the reference draws nothing.  The doubles are
+ * compared as the reference compares them.  A table is refused (BBO_ERR_ARG) unless every slot the next
+ * generation reads holds a draw: both parents' first slots, the crossover's coin and what it calls for, the
+ * coin of every child for imut >= 4, every locus uniform, and the value of every locus whose uniform is below
+ * pmut as it stands at the call.  NULL returns to the device generator (Philox keyed by generation,
+ * mating, child, purpose and locus; one 32-bit word per locus test).  "record_draws" keeps the same table of
+ * the last generation ("draws").
+ * Keys: "ph" (phenotypes, row order; writing them writes "x" too) "fitns" "order" (rank -> row, ascending;
+ * writable as a permutation, the ranks and the running sums follow) "pmut" "ig" "fev" "fbest" "xbest" (best
+ * ever, the objective's scale) -- all writable, nothing is evaluated -- "x" "rank" "cum" "flag" "conv" "rdif"
+ * "table_len" "z" "zinv"; of the last generation "parents" (np / 2 x 2 rows) "cross" (np / 2 x 2: ispl, ispl2,
+ * 1-based, or -1) "mode" (per child: 1 creep, 0 uniform) "new_ph" "new_x" "new_f" (objective values) "elite". */
+typedef struct {
+    double pcross, pmut, pmutmn, pmutmx, fdif;
+    int imut, irep, ielite;
+    int repair, raw, substream;
+} bbo_pikaia_params;
+void bbo_pikaia_params_default(bbo_pikaia_params *p);   /* 0.85, 0.005, 0.0005, 0.25, 1., 2, 1, 0, 0, 0, 0 */
+int bbo_pikaia_configure(bbo_handle h, const bbo_pikaia_params *p);
+int bbo_pikaia_inject_draws(bbo_handle h, const double *table, int count);
 
 /* ---- diagnostics -------------------------------------------------------------------------------
  * bbo_probe_objective: built-in `objective` at `rows` points of `n` coordinates (X, rows x n, host
