@@ -218,6 +218,8 @@ int CsoEngine::get(const std::string &k, int p, double *out, int cap)
     }
     if (k == "f") return o.vec_by_slot(f_, occ_, pb, c.np, c.np);
     if (k == "home") return o.ints(occ_, pb, c.np);
+    // (read-only) the slots as the last generation's shuffle left them, before the sort inside the groups
+    if (k == "shuffled") return o.ints(occ2_, pb, c.np);
     if (k == "xbest") return o.vec(X_, (pb + s.ibest) * c.ld, c.n);
     if (k == "mean") return o.vec(mean_, (size_t) p * c.ld, c.n);
     if (k == "meanw") return o.vec(meanw_, (size_t) p * c.ld, c.n);

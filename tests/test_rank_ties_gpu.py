@@ -14,57 +14,15 @@ The two tests without the `gpu` mark check the tables themselves on the host."""
 import numpy as np
 import pytest
 
+# the key families and the reference, shared with test_select_ties_gpu.py
+from _tie_families import FAMILIES, EDGES, family, groups, bits, reference
+
 gpu = pytest.mark.gpu
 
 # enum RankKernel (bbo_rank.hpp), in its order: the contract of the key `rank_route`
 ROUTES = ("wave", "sort_bitonic256", "sort_bitonic_e1", "sort_bitonic_e2", "sort_bitonic_e4", "sort_bitonic_e8",
           "sort_merge2", "sort_merge4", "count8", "count32", "count64")
 DBG_RANK_COUNT32, DBG_RANK_COUNT_NO64, DBG_RANK_BITONIC, DBG_NO_SMALL_FUSED = 128, 4096, 262144, 64
-
-# ---- the key families: functions of the length, a seeded generator, and nothing else ------------------------
-FAMILIES = ("constant", "parity", "halves", "few", "descending", "edges", "distinct")
-EDGES = np.array([-np.inf, -1.797e308, -0.0, 0.0, 5e-324, 1.797e308, np.inf])
-
-
-def family(k, L):
-    """family k at length L >= 4"""
-    name, rng = FAMILIES[k], np.random.default_rng([k, L])
-    i = np.arange(L)
-    if name == "constant":
-        return np.full(L, 3.25)
-    if name == "parity":
-        return (i % 2).astype(np.float64)
-    if name == "halves":
-        return np.where(i < L // 2, 1., 0.)
-    if name == "few":                       # long runs of ties across every seam; the ends tie whatever was drawn
-        f = rng.integers(0, 8, L).astype(np.float64)
-        f[L - 1] = f[0]
-        return f
-    if name == "descending":
-        return (L - i).astype(np.float64)
-    if name == "edges":                     # +inf in about a third of the entries: real +inf ties the padding key
-        f = EDGES[rng.choice(7, size=L, p=[1 / 9.] * 6 + [1 / 3.])]
-        f[0], f[1], f[2], f[L - 1] = np.inf, -0.0, 0.0, np.inf
-        return f
-    return rng.standard_normal(L)           # the control
-
-
-def groups(P):
-    """the seven families over handles of P populations (population p of a handle gets the p-th of its group;
-    the last group wraps round to fill its handle)"""
-    return [[(i + k) % 7 for k in range(P)] for i in range(0, 7, P)]
-
-
-def bits(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.uint64)
-
-
-def reference(f):
-    order = np.argsort(f, kind="stable")
-    rank = np.empty_like(order)
-    rank[order] = np.arange(f.size)
-    return order, rank
-
 
 # ---- the case tables -------------------------------------------------------------------------------------
 # CMA: (expected route, populations, lambda, dbg)
