@@ -220,19 +220,17 @@ void AcdEngine::launch_chunk(int gens)
 
 void AcdEngine::phase(int which)
 {
-    enter("bbo_acd_phase");
-    BBO_REQUIRE(which >= 0 && which <= 2, "bbo_acd_phase: 0 form x1 and x2, 1 evaluate, 2 absorb");
-    c_.honor_stop = 0;
-    if (which == 0) {
-        launch_sweep(ACD_ADVANCE, 1, true);
-    } else if (which == 1) {
-        launch_eval();
-    } else {
-        launch_sweep(ACD_ABSORB, 1, false);
-        launch_update();
-    }
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("bbo_acd_phase", which, 3, "bbo_acd_phase: 0 form x1 and x2, 1 evaluate, 2 absorb", [&] {
+        c_.honor_stop = 0;
+        if (which == 0) {
+            launch_sweep(ACD_ADVANCE, 1, true);
+        } else if (which == 1) {
+            launch_eval();
+        } else {
+            launch_sweep(ACD_ABSORB, 1, false);
+            launch_update();
+        }
+    });
 }
 
 // converged() (:204-228) of population p as it stands, on the host: solution() asks again, and before

@@ -160,10 +160,9 @@ void AmalgamEngine::init(int n, const double *lower, const double *upper, const 
 
 void AmalgamEngine::launch_rank()
 {
-    timer_.begin(stream_, K_RANK);
-    hipLaunchKernelGGL(amalgam_rank, dim3((c_.np + 31) / 32, c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] {
+        hipLaunchKernelGGL(amalgam_rank, dim3((c_.np + 31) / 32, c_.npop), dim3(256), 0, stream_, d_, c_);
+    });
 }
 
 // updateDistribution, :358-416 (the sort is the ranking the previous phase left)
@@ -171,17 +170,15 @@ void AmalgamEngine::part_distribution()
 {
     const AmalgamConst &c = c_;
     const int P = c.npop, T = (c.n + 15) / 16, tiles = T * (T + 1) / 2;
-    timer_.begin(stream_, K_MOMENTS);
-    hipLaunchKernelGGL(amalgam_mean, dim3(P), dim3(256), 0, stream_, d_, c_);
-    hipLaunchKernelGGL(amalgam_gram, dim3((tiles + 3) / 4, c.slabs, P), dim3(256), 0, stream_, d_, c_);
-    hipLaunchKernelGGL(amalgam_cov, dim3((c.n * c.n + 255) / 256, P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_FACTOR);
-    hipLaunchKernelGGL(amalgam_factor, dim3(P), dim3(1024),
-            c.lds_factor ? (size_t) c.ld * c.ld * sizeof(double) : (size_t) 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_MOMENTS, [&] {
+        hipLaunchKernelGGL(amalgam_mean, dim3(P), dim3(256), 0, stream_, d_, c_);
+        hipLaunchKernelGGL(amalgam_gram, dim3((tiles + 3) / 4, c.slabs, P), dim3(256), 0, stream_, d_, c_);
+        hipLaunchKernelGGL(amalgam_cov, dim3((c.n * c.n + 255) / 256, P), dim3(256), 0, stream_, d_, c_);
+    });
+    timed(K_FACTOR, [&] {
+        hipLaunchKernelGGL(amalgam_factor, dim3(P), dim3(1024),
+                c.lds_factor ? (size_t) c.ld * c.ld * sizeof(double) : (size_t) 0, stream_, d_, c_);
+    });
 }
 
 // samplePopulation, :418-453
@@ -193,28 +190,24 @@ void AmalgamEngine::part_sample()
     if (zin_gens_ > 0 && zin_pos_ >= zin_gens_)
         throw Error(BBO_ERR_STATE, "AMALGAM: the injected draws are used up (inject more, or NULL for the "
                 "device's draws)");
-    timer_.begin(stream_, K_DRAW);
-    if (zin_gens_ > 0) {
-        d_.zin = zin_.p + (size_t) zin_pos_ * P * c.np * c.ld;
-        d_.shin = shin_.p + (size_t) zin_pos_ * P * c.np;
-        zin_pos_++;
-        hipLaunchKernelGGL(amalgam_take, rows, dim3(256), 0, stream_, d_, c_);
-    } else {
-        d_.zin = nullptr;
-        d_.shin = nullptr;
-        hipLaunchKernelGGL(amalgam_draw, rows, dim3(256), 0, stream_, d_, c_);
-        hipLaunchKernelGGL(amalgam_settle, rows, dim3(256), 0, stream_, d_, c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_POINTS);
-    hipLaunchKernelGGL(amalgam_points, dim3((c.np + 15) / 16, P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_EVAL);
-    hipLaunchKernelGGL(amalgam_eval, rows, dim3(256), (size_t) 4 * c.ld * sizeof(double), stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    const bool take = zin_gens_ > 0;    // the next generation of the injected table
+    d_.zin = take ? zin_.p + (size_t) zin_pos_ * P * c.np * c.ld : nullptr;
+    d_.shin = take ? shin_.p + (size_t) zin_pos_ * P * c.np : nullptr;
+    if (take) zin_pos_++;
+    timed(K_DRAW, [&] {
+        if (take) {
+            hipLaunchKernelGGL(amalgam_take, rows, dim3(256), 0, stream_, d_, c_);
+        } else {
+            hipLaunchKernelGGL(amalgam_draw, rows, dim3(256), 0, stream_, d_, c_);
+            hipLaunchKernelGGL(amalgam_settle, rows, dim3(256), 0, stream_, d_, c_);
+        }
+    });
+    timed(K_POINTS, [&] {
+        hipLaunchKernelGGL(amalgam_points, dim3((c.np + 15) / 16, P), dim3(256), 0, stream_, d_, c_);
+    });
+    timed(K_EVAL, [&] {
+        hipLaunchKernelGGL(amalgam_eval, rows, dim3(256), (size_t) 4 * c.ld * sizeof(double), stream_, d_, c_);
+    });
     if (obj_.needs_host()) {
         // rows 1 .. in sampling order; row 0 keeps the value amalgam_eval gave it
         if (ident_.count != (size_t) P * c.np) {
@@ -230,10 +223,7 @@ void AmalgamEngine::part_sample()
 // the multiplier rules and the stop tests (:213-233, :290-328), then the ranking of the new values
 void AmalgamEngine::part_adapt()
 {
-    timer_.begin(stream_, K_ADAPT);
-    hipLaunchKernelGGL(amalgam_adapt, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_ADAPT, [&] { hipLaunchKernelGGL(amalgam_adapt, dim3(c_.npop), dim3(256), 0, stream_, d_, c_); });
     launch_rank();
 }
 
@@ -247,15 +237,14 @@ void AmalgamEngine::generation(bool honor_stop)
 
 void AmalgamEngine::phase(int which)
 {
-    enter("phase()");
+    enter("phase()");       // (here too: the refusal comes behind it and before the range check)
     if (driver()) throw Error(BBO_ERR_STATE, "AMALGAM phase: not in the parameter-free mode (noparam)");
-    BBO_REQUIRE(which >= 0 && which <= 2, "AMALGAM phase: 0 distribution, 1 sample + evaluate, 2 adapt + stop");
-    c_.honor_stop = 0;
-    if (which == 0) part_distribution();
-    else if (which == 1) part_sample();
-    else part_adapt();
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("phase()", which, 3, "AMALGAM phase: 0 distribution, 1 sample + evaluate, 2 adapt + stop", [&] {
+        c_.honor_stop = 0;
+        if (which == 0) part_distribution();
+        else if (which == 1) part_sample();
+        else part_adapt();
+    });
 }
 
 void AmalgamEngine::inject_points(const double *x, int count)

@@ -180,15 +180,12 @@ void CcpsoEngine::launch_regroup_eval()
 {
     CcpConst &c = c_;
     const int P = c.npop;
-    timer_.begin(stream_, K_REGROUP);
-    hipLaunchKernelGGL(ccp_regroup, dim3(P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_REGROUP, [&] { hipLaunchKernelGGL(ccp_regroup, dim3(P), dim3(256), 0, stream_, d_, c_); });
     // the largest swarm count any subset size can ask for (the device knows the real one)
     int cpmin = c.pps[0];
     for (int k = 1; k < c.npps; k++) cpmin = std::min(cpmin, c.pps[k]);
     const int maxswarm = c.n / cpmin;
-    timer_.begin(stream_, K_EVAL);
+    timer_.begin(stream_, K_EVAL);      // (with a host objective the slot holds the host's evaluation)
     if (obj_.fused()) {
         if (c.ld <= 256)
             hipLaunchKernelGGL(ccp_eval<16>, dim3((CCP_SPLIT * maxswarm + 15) / 16, P), dim3(256),
@@ -209,24 +206,20 @@ void CcpsoEngine::launch_rest()
     const int P = c.npop;
     int cpmin = c.pps[0];
     for (int k = 1; k < c.npps; k++) cpmin = std::min(cpmin, c.pps[k]);
-    timer_.begin(stream_, K_UPDATE);
+    timer_.begin(stream_, K_UPDATE);    // (the host's evaluation of yhat lies between its two launches)
     hipLaunchKernelGGL(ccp_update, dim3(c.n / cpmin, P), dim3(64), 0, stream_, d_, c_);
     if (obj_.needs_host()) host_eval_yhat();
     hipLaunchKernelGGL(ccp_yhat, dim3(P), dim3(256), (size_t) c.ld * sizeof(double), stream_, d_,
             c_);
     timer_.end(stream_);
     BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_POSITION);
-    hipLaunchKernelGGL(ccp_strategy, dim3(((c.n / cpmin) * c.np + 255) / 256, P), dim3(256), 0,
-            stream_, d_, c_);
     const int rparts = (c.ld / 2 + 255) / 256;
-    hipLaunchKernelGGL(ccp_position, dim3(rparts, c.np, P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(ccp_finish, dim3(P), dim3(256), 0, stream_, d_, c_, rparts);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_POSITION, [&] {
+        hipLaunchKernelGGL(ccp_strategy, dim3(((c.n / cpmin) * c.np + 255) / 256, P), dim3(256), 0,
+                stream_, d_, c_);
+        hipLaunchKernelGGL(ccp_position, dim3(rparts, c.np, P), dim3(256), 0, stream_, d_, c_);
+    });
+    timed(K_FINISH, [&] { hipLaunchKernelGGL(ccp_finish, dim3(P), dim3(256), 0, stream_, d_, c_, rparts); });
 }
 
 void CcpsoEngine::generation(bool honor_stop)

@@ -563,28 +563,27 @@ void CmaEngine::launch_sample_eval()
         if (allow) allow_lds((const void*) kernel, allow);
         hipLaunchKernelGGL(kernel, dim3(r.gx, r.gy), dim3(r.block), r.lds, stream_, d_, c_, args...);
     };
-    timer_.begin(stream_, K_SAMPLE);
-    switch (r.k) {
-    case SK_NONE: break;
-    case SK_SEP_16: go(sep_sample_eval<16>, 128 * 1024); break;
-    case SK_SEP_64_512: go(sep_sample_eval<64, 512>, 140 * 1024); break;
-    case SK_SEP_64_512_LEAN: go(sep_sample_eval<64, 512, true>, 140 * 1024); break;
-    case SK_SEP_SUM: go(sep_sum_kernel<0>(c_.obj), 0); break;
-    case SK_SEP_SUM4: go(sep_sum_kernel<4>(c_.obj), 0); break;
-    case SK_SEP_64: go(sep_sample_eval<64>, 140 * 1024); break;
-    case SK_EVAL128: go(cma_sample_eval128, 128 * 1024, r.rows_per_wg, r.full, r.transposed); break;
-    case SK_EVAL128_TRI: go(cma_sample_eval128_tri, 128 * 1024, r.rows_per_wg, r.full, r.transposed); break;
-    case SK_TILE8: go(cma_sample_eval<1, 8>, 0); break;
-    case SK_TILE8_TRI: go(cma_sample_eval<1, 8, true>, 0); break;
-    case SK_EVAL64_1_8: go(cma_sample_eval64<1, 8>, 0); break;
-    case SK_EVAL64_1: go(cma_sample_eval64<1>, 80 * 1024); break;
-    case SK_EVAL64_2: go(cma_sample_eval64<2>, 80 * 1024); break;
-    case SK_TILE16: go(cma_sample_eval<1, 16>, 0); break;
-    case SK_EVAL_4: go(cma_sample_eval<4>, 0); break;
-    case SK_EVAL_8: go(cma_sample_eval<8>, 80 * 1024); break;      // ld = 512: 65 792 bytes
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_SAMPLE, [&] {
+        switch (r.k) {
+        case SK_NONE: break;
+        case SK_SEP_16: go(sep_sample_eval<16>, 128 * 1024); break;
+        case SK_SEP_64_512: go(sep_sample_eval<64, 512>, 140 * 1024); break;
+        case SK_SEP_64_512_LEAN: go(sep_sample_eval<64, 512, true>, 140 * 1024); break;
+        case SK_SEP_SUM: go(sep_sum_kernel<0>(c_.obj), 0); break;
+        case SK_SEP_SUM4: go(sep_sum_kernel<4>(c_.obj), 0); break;
+        case SK_SEP_64: go(sep_sample_eval<64>, 140 * 1024); break;
+        case SK_EVAL128: go(cma_sample_eval128, 128 * 1024, r.rows_per_wg, r.full, r.transposed); break;
+        case SK_EVAL128_TRI: go(cma_sample_eval128_tri, 128 * 1024, r.rows_per_wg, r.full, r.transposed); break;
+        case SK_TILE8: go(cma_sample_eval<1, 8>, 0); break;
+        case SK_TILE8_TRI: go(cma_sample_eval<1, 8, true>, 0); break;
+        case SK_EVAL64_1_8: go(cma_sample_eval64<1, 8>, 0); break;
+        case SK_EVAL64_1: go(cma_sample_eval64<1>, 80 * 1024); break;
+        case SK_EVAL64_2: go(cma_sample_eval64<2>, 80 * 1024); break;
+        case SK_TILE16: go(cma_sample_eval<1, 16>, 0); break;
+        case SK_EVAL_4: go(cma_sample_eval<4>, 0); break;
+        case SK_EVAL_8: go(cma_sample_eval<8>, 80 * 1024); break;      // ld = 512: 65 792 bytes
+        }
+    });
     // ||z||^2 stands in for the whitened norm only if this launch wrote it and no x was clamped
     c_.use_zn = (r.writes_zn && !c_.bound) ? 1 : 0;
     last_sample_ = r;
@@ -594,38 +593,37 @@ void CmaEngine::launch_rank()
 {
     const CmaConst &c = c_;
     rank_wrote_norms_ = false;
-    timer_.begin(stream_, K_RANK);
     // (which form, and why: rank_route, bbo_rank.hpp)
     last_rank_ = rank_route(c.lambda, c.npop, d_.dbg);
-    switch (last_rank_) {
-    case RK_WAVE:
-        hipLaunchKernelGGL(cma_rank_wave, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_);
-        break;
-    case RK_COUNT64:
-        hipLaunchKernelGGL(cma_rank64, dim3((c.lambda + 3) / 4, c.npop), dim3(256), 0, stream_, d_, c_);
-        break;
-    case RK_COUNT32:
-        hipLaunchKernelGGL(cma_rank32, dim3((c.lambda + 7) / 8, c.npop), dim3(256), 0, stream_, d_, c_);
-        break;
-    case RK_COUNT8:
-        hipLaunchKernelGGL(cma_rank, dim3((c.lambda + 31) / 32, c.npop), dim3(256), 0, stream_, d_, c_);
-        break;
-    default: {   // the in-LDS sorts: cma_rank_sort picks the instantiation from m and dbg like rank_route
-        const int m = rank_sort_m(c.lambda);
-        allow_lds((const void*) cma_rank_sort, 128 * 1024);
-        const size_t lds = rank_sort_merges(m, d_.dbg) ? (size_t) m * 24 : (size_t) std::max(m, 1024) * 12;
-        hipLaunchKernelGGL(cma_rank_sort, dim3(c.npop), dim3(sort_threads(m)), lds, stream_, d_,
-                c_, m);
-        break;
-    }
-    }
+    timed(K_RANK, [&] {
+        switch (last_rank_) {
+        case RK_WAVE:
+            hipLaunchKernelGGL(cma_rank_wave, dim3((c.npop + 3) / 4), dim3(256), 0, stream_, d_, c_);
+            break;
+        case RK_COUNT64:
+            hipLaunchKernelGGL(cma_rank64, dim3((c.lambda + 3) / 4, c.npop), dim3(256), 0, stream_, d_, c_);
+            break;
+        case RK_COUNT32:
+            hipLaunchKernelGGL(cma_rank32, dim3((c.lambda + 7) / 8, c.npop), dim3(256), 0, stream_, d_, c_);
+            break;
+        case RK_COUNT8:
+            hipLaunchKernelGGL(cma_rank, dim3((c.lambda + 31) / 32, c.npop), dim3(256), 0, stream_, d_, c_);
+            break;
+        default: {   // the in-LDS sorts: cma_rank_sort picks the instantiation from m and dbg like rank_route
+            const int m = rank_sort_m(c.lambda);
+            allow_lds((const void*) cma_rank_sort, 128 * 1024);
+            const size_t lds = rank_sort_merges(m, d_.dbg) ? (size_t) m * 24 : (size_t) std::max(m, 1024) * 12;
+            hipLaunchKernelGGL(cma_rank_sort, dim3(c.npop), dim3(sort_threads(m)), lds, stream_, d_,
+                    c_, m);
+            break;
+        }
+        }
+    });
     // the whitened norms of the worst mu, where they are the sampler's sigma^2 ||z||^2 handed
     // round through the ranking (cma_whiten128's shortcut): written by the sort itself, which
     // has the ranking in LDS, and by cma_rank_body -- a launch less per generation (10 us of the
     // M step).  Not by the one-wavefront form.
     if (last_rank_ != RK_WAVE) rank_wrote_norms_ = c.variant == 1 && c.use_zn && !basis_maybe_stale_;
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
 }
 
 // The kernels of one update of the distribution, with their geometry: a decision like sample_route.
@@ -701,25 +699,24 @@ void CmaEngine::launch_update(bool with_cov)
             if (allow) allow_lds((const void*) kernel, allow);
             hipLaunchKernelGGL(kernel, dim3(s.gx, s.gy, s.gz), dim3(s.block), s.lds, stream_, d_, c_, args...);
         };
-        timer_.begin(stream_, s.slot);
-        switch (s.k) {
-        case UK_CHOL_PATHS: go(chol_paths, 0); break;
-        case UK_CHOL_CPRIME: go(chol_cprime, 0); break;
-        case UK_CHOL_FACTOR: go(chol_factor, 0, s.arg); break;
-        case UK_SEP_MOMENTS: go(sep_moments, 0); break;
-        case UK_SEP_PATHS: go(sep_paths, 0); break;
-        case UK_WHITEN128: go(cma_whiten128, 132 * 1024, s.arg); break;
-        case UK_WHITEN: go(whiten_kernel(s.arg), s.arg == 8 ? 80 * 1024 : 0); break;      // ld = 512: 66 304 bytes
-        case UK_GRAM128S: go(cma_gram128s, 0); break;
-        case UK_GRAM128: go(cma_gram128, 80 * 1024); break;
-        case UK_GRAM: go(cma_gram, (int) GRAM_LDS_MAX, s.arg); break;
-        case UK_PATHS: go(cma_paths, 0); break;
-        case UK_PATHS_LAZY: go(cma_paths_lazy, 0); break;
-        case UK_PATHS_LAZY1K: go(cma_paths_lazy1k, 0); break;
-        case UK_COV: go(cma_cov, 0); break;
-        }
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+        timed(s.slot, [&] {
+            switch (s.k) {
+            case UK_CHOL_PATHS: go(chol_paths, 0); break;
+            case UK_CHOL_CPRIME: go(chol_cprime, 0); break;
+            case UK_CHOL_FACTOR: go(chol_factor, 0, s.arg); break;
+            case UK_SEP_MOMENTS: go(sep_moments, 0); break;
+            case UK_SEP_PATHS: go(sep_paths, 0); break;
+            case UK_WHITEN128: go(cma_whiten128, 132 * 1024, s.arg); break;
+            case UK_WHITEN: go(whiten_kernel(s.arg), s.arg == 8 ? 80 * 1024 : 0); break;      // ld = 512: 66 304 bytes
+            case UK_GRAM128S: go(cma_gram128s, 0); break;
+            case UK_GRAM128: go(cma_gram128, 80 * 1024); break;
+            case UK_GRAM: go(cma_gram, (int) GRAM_LDS_MAX, s.arg); break;
+            case UK_PATHS: go(cma_paths, 0); break;
+            case UK_PATHS_LAZY: go(cma_paths_lazy, 0); break;
+            case UK_PATHS_LAZY1K: go(cma_paths_lazy1k, 0); break;
+            case UK_COV: go(cma_cov, 0); break;
+            }
+        });
     }
     last_update_ = r;
 }
@@ -848,7 +845,7 @@ void CmaEngine::launch_eigen(EigRoute r)
     auto per_columns = [&](auto kernel, int w, int threads, auto... args) {   // ceil(n / w) workgroups per matrix
         hipLaunchKernelGGL(kernel, dim3((c.n + w - 1) / w, c.npop), dim3(threads), 0, stream_, d_, c_, args...);
     };
-    timer_.begin(stream_, K_EIGEN);
+    timer_.begin(stream_, K_EIGEN);     // (by hand: the slot closes at step r.timed, inside the loop)
     for (int i = 0; i < r.count; i++) {
         if (i == r.timed) {          // (the top merge's products are not part of the slot)
             timer_.end(stream_);
@@ -917,21 +914,19 @@ void CmaEngine::launch_eigen(EigRoute r)
     }
     if (r.timed == r.count) timer_.end(stream_);
     BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_POST);
-    if (r.post) launch_post(0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_POST, [&] {
+        if (r.post) launch_post(0);
+    });
 }
 
 void CmaEngine::launch_history_stop()
 {
-    timer_.begin(stream_, K_STOP);
-    if (c_.variant == 3)
-        hipLaunchKernelGGL(chol_history_stop, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
-    else
-        hipLaunchKernelGGL(cma_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_STOP, [&] {
+        if (c_.variant == 3)
+            hipLaunchKernelGGL(chol_history_stop, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
+        else
+            hipLaunchKernelGGL(cma_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
+    });
 }
 
 // the compatibility path for arbitrary host objectives: X leaves HBM once per generation

@@ -86,8 +86,7 @@ void CrsEngine::init(int n, const double *lower, const double *upper, const doub
     value_.alloc(P);
     stack_.alloc((size_t) P * c.stack_words);
     more_.alloc(1);
-    draws_.alloc(0);
-    inject_.alloc(0);
+    tables_.clear();
     scal_.alloc(P);
     upload_box(n, c.ld, lower, upper, obj);
     {
@@ -112,26 +111,12 @@ void CrsEngine::init(int n, const double *lower, const double *upper, const doub
 
     if (obj_.needs_host()) {
         launch_init(0, P, CRS_INIT_DRAW);
-        host_evaluate_pool(0, P);
+        host_evaluate_range(X_, f_, 0, P, np, 0, np, n, c.ld);      // (in row order: :61-70)
     } else {
         launch_init(0, P, CRS_INIT_DRAW | CRS_INIT_EVAL);
     }
     launch_rank(0, P);
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// host objective: the points of the populations p0 .. p0 + pcount - 1 in row order (:61-70)
-void CrsEngine::host_evaluate_pool(int p0, int pcount)
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int np = c_.np, ld = c_.ld;
-    std::vector<double> xh((size_t) np * ld), fh(np);
-    for (int p = p0; p < p0 + pcount; p++) {
-        X_.download(xh.data(), xh.size(), (size_t) p * np * ld);
-        obj_.eval_host(xh.data(), np, c_.n, ld, fh.data());
-        nan_to_inf(fh.data(), np);
-        f_.upload(fh.data(), np, (size_t) p * np);
-    }
 }
 
 void CrsEngine::launch_init(int p0, int pcount, int mode)
@@ -240,9 +225,8 @@ void CrsEngine::inject_draws(const double *table, int count)
     }
     // a record whose uniforms are not spent belongs to the table before: the walk goes on with a new one
     for (auto &s : sc) s.wused = 1;
-    inject_.alloc((size_t) count);
-    inject_.upload(table, (size_t) count);
-    d_.inject = inject_.p;
+    tables_.inject.alloc(0);        // (the table before may have had another length)
+    d_.inject = tables_.load(table, (size_t) count);
     c_.inject_n = (int) nrec;
     scal_.upload(sc.data(), P);
 }
@@ -291,7 +275,7 @@ int CrsEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "draws") {
         require_record(c.record > 0, k);
         const int kept = std::min(s.nrec, c.record);
-        return o.vec(draws_, (size_t) p * c.record * 2 * c.n, kept * 2 * c.n);
+        return o.vec(tables_.draws, (size_t) p * c.record * 2 * c.n, kept * 2 * c.n);
     }
     if (k == "fcand") return o.one(s.ft);
     if (k == "fcand2") return o.one(s.ft2);
@@ -334,15 +318,9 @@ int CrsEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "record_draws") {      // (the whole handle: every population) 1: CRS_DEFAULT_RECORD records, else so many
         BBO_REQUIRE(whole(0., 4096.), "record_draws: 0, 1 (64 records per iteration) or the records to keep, up to 4096");
         const int want = in[0] == 1. ? CRS_DEFAULT_RECORD : (int) in[0];
-        if (want != c.record) {
-            draws_.alloc((size_t) c.npop * want * 2 * c.n);
-            if (want) {
-                std::vector<double> z((size_t) c.npop * want * 2 * c.n, 0.);
-                draws_.upload(z.data(), z.size());
-            }
-        }
+        if (want != c.record) tables_.draws.alloc(0);       // (a table of another length)
         c_.record = want;
-        d_.draws = want ? draws_.p : nullptr;
+        d_.draws = tables_.record(want > 0, (size_t) c.npop * want * 2 * c.n);
         return 1;
     }
     if (k == "launch_evals") {
@@ -358,7 +336,7 @@ int CrsEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "x") {             // rows in place; f, the ranking, the best and the worst follow; fev does not move
         BBO_REQUIRE(count == c.np * c.n, "x: np * n values");
         upload_rows(X_, pr, c.np, c.n, c.ld, in);
-        if (obj_.needs_host()) host_evaluate_pool(p, 1);
+        if (obj_.needs_host()) host_evaluate_range(X_, f_, p, 1, c.np, 0, c.np, c.n, c.ld);
         else launch_init(p, 1, CRS_INIT_EVAL);
         launch_rank(p, 1);
         BBO_HIP(hipStreamSynchronize(stream_));

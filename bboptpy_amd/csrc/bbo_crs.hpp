@@ -131,7 +131,6 @@ private:
     void launch_rank(int p0, int pcount);
     void launch_body(int mode, int k, bool begin);
     void fused(int k);
-    void host_evaluate_pool(int p0, int pcount);
     void reset_walk(int p);
     int workgroup() const;
     int launch_evals(int k) const;
@@ -139,7 +138,8 @@ private:
     bbo_crs_params cp_ {};
     CrsConst c_ {};
     CrsDev d_ {};
-    DevBuf<double> X_, f_, cand_, cand2_, value_, draws_, inject_;
+    DevBuf<double> X_, f_, cand_, cand2_, value_;
+    DrawTables tables_;      // records of 2 n draws: the injected table and the recorded one
     DevBuf<int> order_, more_;
     DevBuf<uint32_t> stack_;
     int launch_evals_ = 0;           // bbo_set "launch_evals": 0 = CRS_LAUNCH_STEPS_PER_ITERATION per iteration

@@ -143,54 +143,49 @@ void CsoEngine::generation(bool honor_stop)
     CsoConst &c = c_;
     c.honor_stop = honor_stop ? 1 : 0;
     const int P = c.npop;
-    timer_.begin(stream_, K_MEAN);
-    if (c.ring) {
-        hipLaunchKernelGGL(cso_ring_mean, dim3((c.np + 15) / 16, P), dim3(256), 0, stream_, d_, c_);
-    } else if (fuse_g_) {
-        hipLaunchKernelGGL(cso_wgsum, dim3(c.parts, P), dim3(256), 0, stream_, d_, c_);
-        hipLaunchKernelGGL(cso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, 0, c.np);
-    } else {
-        hipLaunchKernelGGL(cso_colsum, dim3(c.parts, P), dim3(256), 0, stream_, d_, c_, 1, c.np);
-        hipLaunchKernelGGL(cso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, 0, c.np);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_SHUFFLE);
-    hipLaunchKernelGGL(cso_shuffle, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_, c_,
-            shuffle_key_bits(c.np));
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_GROUPS);
-    hipLaunchKernelGGL(cso_groups, dim3((c.ngroup + 255) / 256, P), dim3(256), 0, stream_, d_, c_);
-    hipLaunchKernelGGL(cso_colsum, dim3(c.parts, P), dim3(256), 0, stream_, d_, c_, c.pc,
-            c.ngroup);
-    hipLaunchKernelGGL(cso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, 1, c.ngroup);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_COMPETE);
-    if (fuse_g_) {
-        const size_t lds = (size_t) (256 / fuse_g_ + 2) * c.ld * sizeof(double);   // rows + the box
-        const dim3 grid(c.nwg, P);
-        if (fuse_g_ == 16)
-            hipLaunchKernelGGL((cso_compete<16, true>), grid, dim3(256), lds, stream_, d_, c_);
-        else if (fuse_g_ == 32)
-            hipLaunchKernelGGL((cso_compete<32, true>), grid, dim3(256), lds, stream_, d_, c_);
-        else
-            hipLaunchKernelGGL((cso_compete<64, true>), grid, dim3(256), lds, stream_, d_, c_);
-    } else {
-        const int R = rows_per_wg16(c.ld);     // groups staged in LDS per workgroup
-        allow_lds((const void*) cso_compete<16, false>, 128 * 1024);
-        hipLaunchKernelGGL((cso_compete<16, false>), dim3((c.ngroup + R - 1) / R, P), dim3(16 * R),
-                (size_t) (R + 2) * c.ld * sizeof(double), stream_, d_, c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_MEAN, [&] {
+        if (c.ring) {
+            hipLaunchKernelGGL(cso_ring_mean, dim3((c.np + 15) / 16, P), dim3(256), 0, stream_, d_, c_);
+        } else if (fuse_g_) {
+            hipLaunchKernelGGL(cso_wgsum, dim3(c.parts, P), dim3(256), 0, stream_, d_, c_);
+            hipLaunchKernelGGL(cso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, 0, c.np);
+        } else {
+            hipLaunchKernelGGL(cso_colsum, dim3(c.parts, P), dim3(256), 0, stream_, d_, c_, 1, c.np);
+            hipLaunchKernelGGL(cso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, 0, c.np);
+        }
+    });
+    timed(K_SHUFFLE, [&] {
+        hipLaunchKernelGGL(cso_shuffle, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_, c_,
+                shuffle_key_bits(c.np));
+    });
+    timed(K_GROUPS, [&] {
+        hipLaunchKernelGGL(cso_groups, dim3((c.ngroup + 255) / 256, P), dim3(256), 0, stream_, d_, c_);
+        hipLaunchKernelGGL(cso_colsum, dim3(c.parts, P), dim3(256), 0, stream_, d_, c_, c.pc,
+                c.ngroup);
+        hipLaunchKernelGGL(cso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, 1, c.ngroup);
+    });
+    timed(K_COMPETE, [&] {
+        if (fuse_g_) {
+            const size_t lds = (size_t) (256 / fuse_g_ + 2) * c.ld * sizeof(double);   // rows + the box
+            const dim3 grid(c.nwg, P);
+            if (fuse_g_ == 16)
+                hipLaunchKernelGGL((cso_compete<16, true>), grid, dim3(256), lds, stream_, d_, c_);
+            else if (fuse_g_ == 32)
+                hipLaunchKernelGGL((cso_compete<32, true>), grid, dim3(256), lds, stream_, d_, c_);
+            else
+                hipLaunchKernelGGL((cso_compete<64, true>), grid, dim3(256), lds, stream_, d_, c_);
+        } else {
+            const int R = rows_per_wg16(c.ld);     // groups staged in LDS per workgroup
+            allow_lds((const void*) cso_compete<16, false>, 128 * 1024);
+            hipLaunchKernelGGL((cso_compete<16, false>), dim3((c.ngroup + R - 1) / R, P), dim3(16 * R),
+                    (size_t) (R + 2) * c.ld * sizeof(double), stream_, d_, c_);
+        }
+    });
     if (obj_.needs_host()) host_evaluate(true);
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(cso_finish_part, dim3(c_.fparts, P), dim3(256), 0, stream_, d_, c_);
-    hipLaunchKernelGGL(cso_finish, dim3(P), dim3(64), 0, stream_, d_, c_, 0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_FINISH, [&] {
+        hipLaunchKernelGGL(cso_finish_part, dim3(c_.fparts, P), dim3(256), 0, stream_, d_, c_);
+        hipLaunchKernelGGL(cso_finish, dim3(P), dim3(64), 0, stream_, d_, c_, 0);
+    });
 }
 
 void CsoEngine::solution(int population, double *x_out, int *n_evals, int *converged)

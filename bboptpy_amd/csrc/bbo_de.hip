@@ -210,45 +210,32 @@ void DeEngine::generation(bool honor_stop)
     const int R = rows_per_wg16(c.ld);     // rows staged in LDS per workgroup
     dim3 gR((np_host_ + R - 1) / R, P);
     const size_t lds = (size_t) R * c.ld * sizeof(double);
-    timer_.begin(stream_, K_GEN);
     const size_t lds_box = lds + (size_t) 2 * c.ld * sizeof(double);   // + lower, upper
-    if (c.variant == 2) {
-        allow_lds((const void*) sansde_generation, 128 * 1024);
-        hipLaunchKernelGGL(sansde_generation, gR, dim3(16 * R), lds_box, stream_, d_, c_);
-    } else {
-        allow_lds((const void*) de_generation, 128 * 1024);
-        hipLaunchKernelGGL(de_generation, gR, dim3(16 * R), lds_box, stream_, d_, c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_GEN, [&] {
+        if (c.variant == 2) {
+            allow_lds((const void*) sansde_generation, 128 * 1024);
+            hipLaunchKernelGGL(sansde_generation, gR, dim3(16 * R), lds_box, stream_, d_, c_);
+        } else {
+            allow_lds((const void*) de_generation, 128 * 1024);
+            hipLaunchKernelGGL(de_generation, gR, dim3(16 * R), lds_box, stream_, d_, c_);
+        }
+    });
     if (!obj_.fused()) {
         if (obj_.is_program()) program_evaluate(-1, np_host_);
         else host_evaluate(-1, np_host_);
-        timer_.begin(stream_, K_SELECT);
-        hipLaunchKernelGGL(de_select, g16, dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+        timed(K_SELECT, [&] { hipLaunchKernelGGL(de_select, g16, dim3(256), 0, stream_, d_, c_); });
     }
-    timer_.begin(stream_, K_BOOK);
-    if (c.variant == 2)
-        hipLaunchKernelGGL(sansde_bookkeep, dim3(P), dim3(pop_threads()), 0, stream_, d_, c_);
-    else
-        hipLaunchKernelGGL(de_bookkeep, dim3(P), dim3(pop_threads()), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_BOOK, [&] {
+        if (c.variant == 2)
+            hipLaunchKernelGGL(sansde_bookkeep, dim3(P), dim3(pop_threads()), 0, stream_, d_, c_);
+        else
+            hipLaunchKernelGGL(de_bookkeep, dim3(P), dim3(pop_threads()), 0, stream_, d_, c_);
+    });
     if (c.archive) {
-        timer_.begin(stream_, K_ARCH);
-        hipLaunchKernelGGL(de_archive_copy, g16, dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+        timed(K_ARCH, [&] { hipLaunchKernelGGL(de_archive_copy, g16, dim3(256), 0, stream_, d_, c_); });
     }
-    timer_.begin(stream_, K_RANK);
-    launch_rank(1, np_host_);
-    timer_.end(stream_);
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(de_finish, dim3(P), dim3(pop_threads()), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] { launch_rank(1, np_host_); });
+    timed(K_FINISH, [&] { hipLaunchKernelGGL(de_finish, dim3(P), dim3(pop_threads()), 0, stream_, d_, c_); });
     // the same population-size schedule on the host (shade.cpp:218-225), for the grid only
     fev_host_ += np_host_;
     if (c.variant == 0) {

@@ -106,17 +106,11 @@ void DsaEngine::init(int n, const double *lower, const double *upper, const doub
     hipLaunchKernelGGL(dsa_init, dim3((c.np + 3) / 4, P), dim3(256), 4 * ld * sizeof(double),
             stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (obj_.needs_host()) host_evaluate(true);
+    // host objective: the pool, and in generation() the trials, in row order like the reference's loop
+    if (obj_.needs_host()) host_evaluate_rows(X0_, f_, c.np, c.n, c.ld, c.honor_stop);
     hipLaunchKernelGGL(dsa_finish, dim3(P), dim3(256), 0, stream_, d_, c_, 1);
     BBO_HIP(hipGetLastError());
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// host objective: the pool (init) or the trials of this generation, in row order like the
-// reference's loop
-void DsaEngine::host_evaluate(bool init)
-{
-    host_evaluate_rows(init ? X0_ : T_, init ? f_ : ftrial_, c_.np, c_.n, c_.ld, c_.honor_stop);
 }
 
 void DsaEngine::generation(bool honor_stop)
@@ -125,27 +119,17 @@ void DsaEngine::generation(bool honor_stop)
     c.honor_stop = honor_stop ? 1 : 0;
     const int P = c.npop;
     const dim3 members((c.np + 3) / 4, P);
-    timer_.begin(stream_, K_RANK);
-    hipLaunchKernelGGL(dsa_rank, dim3((c.np + 31) / 32, P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_PLAN);
-    hipLaunchKernelGGL(dsa_plan, dim3(P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_EVOLVE);
-    hipLaunchKernelGGL(dsa_evolve, members, dim3(256), (size_t) 4 * c.ld * sizeof(double), stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] { hipLaunchKernelGGL(dsa_rank, dim3((c.np + 31) / 32, P), dim3(256), 0, stream_, d_, c_); });
+    timed(K_PLAN, [&] { hipLaunchKernelGGL(dsa_plan, dim3(P), dim3(256), 0, stream_, d_, c_); });
+    timed(K_EVOLVE, [&] {
+        hipLaunchKernelGGL(dsa_evolve, members, dim3(256), (size_t) 4 * c.ld * sizeof(double), stream_, d_, c_);
+    });
     if (obj_.needs_host()) {
-        host_evaluate(false);
+        host_evaluate_rows(T_, ftrial_, c.np, c.n, c.ld, c.honor_stop);
         hipLaunchKernelGGL(dsa_select, members, dim3(256), 0, stream_, d_, c_);
         BBO_HIP(hipGetLastError());
     }
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(dsa_finish, dim3(P), dim3(256), 0, stream_, d_, c_, 0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_FINISH, [&] { hipLaunchKernelGGL(dsa_finish, dim3(P), dim3(256), 0, stream_, d_, c_, 0); });
 }
 
 void DsaEngine::solution(int population, double *x_out, int *n_evals, int *converged)

@@ -82,7 +82,6 @@ public:
 private:
     static const bbo_params &checked(const bbo_params &p);
     void generation(bool honor_stop) override;
-    void host_evaluate(bool init);
     void alloc_record();
 
     bbo_dsa_params dp_ {};

@@ -299,7 +299,8 @@ protected:
         BBO_HIP(hipStreamSynchronize(stream_));
     }
 
-    // the engines that have no program path yet say which have
+    // the engines that have no program path yet say which have (the same list, in Python's words:
+    // PROGRAM_FAMILIES, bboptpy_amd/multivariate.py)
     void reject_program(const ObjectiveSpec &obj, const char *who) const
     {
         if (obj.is_program())
@@ -372,6 +373,10 @@ protected:
             bool honor_stop, const DevBuf<int> *order = nullptr,
             const std::function<bool(int)> &skip = nullptr)
     {
+        if (!order) {
+            host_evaluate_range(src, dst, 0, params_.populations, np, 0, np, n, ld, honor_stop);
+            return;
+        }
         BBO_HIP(hipStreamSynchronize(stream_));
         const int P = params_.populations;
         std::vector<Scal> sc(P);
@@ -381,22 +386,37 @@ protected:
         for (int p = 0; p < P; p++) {
             if (honor_stop && sc[p].stop) continue;
             src.download(xh.data(), xh.size(), (size_t) p * np * ld);
-            if (!order) {
-                obj_.eval_host(xh.data(), np, n, ld, fh.data());
-                nan_to_inf(fh.data(), np);
-            } else {
-                if (skip) dst.download(fh.data(), np, (size_t) p * np);
-                order->download(occ.data(), np, (size_t) p * np);
-                for (int s = 0; s < np; s++) {
-                    if (skip && skip(s)) continue;
-                    const int row = occ[s];
-                    double f = 0.;
-                    obj_.eval_host(xh.data() + (size_t) row * ld, 1, n, ld, &f);
-                    nan_to_inf(&f, 1);
-                    fh[row] = f;
-                }
+            if (skip) dst.download(fh.data(), np, (size_t) p * np);
+            order->download(occ.data(), np, (size_t) p * np);
+            for (int s = 0; s < np; s++) {
+                if (skip && skip(s)) continue;
+                const int row = occ[s];
+                double f = 0.;
+                obj_.eval_host(xh.data() + (size_t) row * ld, 1, n, ld, &f);
+                nan_to_inf(&f, 1);
+                fh[row] = f;
             }
             dst.upload(fh.data(), np, (size_t) p * np);
+        }
+    }
+
+    // The same in row order for the populations [p0, p0 + pcount) only, of each the rows [r0, r1) of
+    // the `nrows` it holds in src ([P][nrows][ld]) and dst ([P][nrows]): one call of eval_host per
+    // population (an engine's initial points, or the points set("x") replaced in one population).
+    void host_evaluate_range(const DevBuf<double> &src, DevBuf<double> &dst, int p0, int pcount, int nrows,
+            int r0, int r1, int n, int ld, bool honor_stop = false)
+    {
+        BBO_HIP(hipStreamSynchronize(stream_));
+        std::vector<Scal> sc(params_.populations);
+        scal_.download(sc.data(), sc.size());
+        const int cnt = r1 - r0;
+        std::vector<double> xh((size_t) cnt * ld), fh(cnt);
+        for (int p = p0; p < p0 + pcount; p++) {
+            if (honor_stop && sc[p].stop) continue;
+            src.download(xh.data(), xh.size(), ((size_t) p * nrows + r0) * ld);
+            obj_.eval_host(xh.data(), cnt, n, ld, fh.data());
+            nan_to_inf(fh.data(), cnt);
+            dst.upload(fh.data(), cnt, (size_t) p * nrows + r0);
         }
     }
 
@@ -424,7 +444,8 @@ protected:
         }
     }
 
-    // one kernel launch in its slot of get("profile"): `launch` holds the hipLaunchKernelGGL
+    // the launches of one slot of get("profile"): `launch` holds the hipLaunchKernelGGLs, with the
+    // allow_lds calls and the choice of the kernel, and nothing that waits for the host
     template<class Launch>
     void timed(int slot, Launch launch)
     {
@@ -432,6 +453,19 @@ protected:
         launch();
         timer_.end(stream_);
         BBO_HIP(hipGetLastError());
+    }
+
+    // One part of a generation on its own, what an engine's bbo_<engine>_phase runs: `part` clears the
+    // engine's honor_stop and launches part `which` of the `count`; `call` and `usage` are the
+    // engine's own texts.
+    template<class Part>
+    void run_phase(const char *call, int which, int count, const std::string &usage, Part part)
+    {
+        enter(call);
+        BBO_REQUIRE(which >= 0 && which < count, usage);
+        part();
+        BBO_HIP(hipStreamSynchronize(stream_));
+        timer_.collect();
     }
 
     bool all_stopped()
@@ -483,22 +517,20 @@ public:
     // bbo_<engine>_phase: 0 advance to the next pending evaluation, 1 evaluate, 2 absorb
     void phase(int which)
     {
-        this->enter(phase_fn_);
-        BBO_REQUIRE(which >= 0 && which <= 2, std::string(phase_fn_) + ": 0 advance, 1 evaluate, 2 absorb");
-        honor_stop() = 0;
-        if (which == 0) {
-            // the first advance of a generation starts it in every population; the later ones leave a
-            // population that has completed it alone until none has a point pending
-            launch_walk(WALK_ADVANCE, !mid_generation_);
-            mid_generation_ = any_pending();
-        } else if (which == 1) {
-            launch_eval();
-        } else {
-            launch_walk(WALK_ABSORB, false);
-            if (absorb_advances_) mid_generation_ = any_pending();
-        }
-        BBO_HIP(hipStreamSynchronize(this->stream_));
-        this->timer_.collect();
+        this->run_phase(phase_fn_, which, 3, std::string(phase_fn_) + ": 0 advance, 1 evaluate, 2 absorb", [&] {
+            honor_stop() = 0;
+            if (which == 0) {
+                // the first advance of a generation starts it in every population; the later ones leave a
+                // population that has completed it alone until none has a point pending
+                launch_walk(WALK_ADVANCE, !mid_generation_);
+                mid_generation_ = any_pending();
+            } else if (which == 1) {
+                launch_eval();
+            } else {
+                launch_walk(WALK_ABSORB, false);
+                if (absorb_advances_) mid_generation_ = any_pending();
+            }
+        });
     }
 
 protected:

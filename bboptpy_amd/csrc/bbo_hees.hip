@@ -169,64 +169,55 @@ void HeesEngine::part_sample()
     const HeesConst &c = c_;
     const int P = c.npop;
     const dim3 rows((c.mu + 3) / 4, P);
-    timer_.begin(stream_, K_DRAW);
-    if (d_.zin) hipLaunchKernelGGL(hees_take, rows, dim3(256), 0, stream_, d_, c_);
-    else {
-        hipLaunchKernelGGL(hees_draw, rows, dim3(256), 0, stream_, d_, c_);
-        hipLaunchKernelGGL(hees_settle, rows, dim3(256), 0, stream_, d_, c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_DRAW, [&] {
+        if (d_.zin) hipLaunchKernelGGL(hees_take, rows, dim3(256), 0, stream_, d_, c_);
+        else {
+            hipLaunchKernelGGL(hees_draw, rows, dim3(256), 0, stream_, d_, c_);
+            hipLaunchKernelGGL(hees_settle, rows, dim3(256), 0, stream_, d_, c_);
+        }
+    });
     const size_t batch = (size_t) std::min(c.n, c.mu) * c.ld * sizeof(double);
     const int use_lds = !c.ortho_global && batch <= (size_t) HEES_ORTHO_LDS ? 1 : 0;
-    timer_.begin(stream_, K_ORTHO);
-    // (a batch of 64 rows and more: 16 wavefronts, whose rows hide one another's latency)
-    hipLaunchKernelGGL(hees_ortho, dim3(c.B, P), dim3(std::min(c.n, c.mu) >= 64 ? 1024 : 256),
-            use_lds ? batch : 0, stream_, d_, c_, use_lds);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_POINTS);
-    if (use_mfma())
-        hipLaunchKernelGGL(hees_points_mfma, dim3((c.mu + 15) / 16, P), dim3(256),
-                (size_t) 32 * c.ld * sizeof(double), stream_, d_, c_);
-    else
-        hipLaunchKernelGGL(hees_points, rows, dim3(256), (size_t) 12 * c.ld * sizeof(double), stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_ORTHO, [&] {
+        // (a batch of 64 rows and more: 16 wavefronts, whose rows hide one another's latency)
+        hipLaunchKernelGGL(hees_ortho, dim3(c.B, P), dim3(std::min(c.n, c.mu) >= 64 ? 1024 : 256),
+                use_lds ? batch : 0, stream_, d_, c_, use_lds);
+    });
+    timed(K_POINTS, [&] {
+        if (use_mfma())
+            hipLaunchKernelGGL(hees_points_mfma, dim3((c.mu + 15) / 16, P), dim3(256),
+                    (size_t) 32 * c.ld * sizeof(double), stream_, d_, c_);
+        else
+            hipLaunchKernelGGL(hees_points, rows, dim3(256), (size_t) 12 * c.ld * sizeof(double), stream_, d_, c_);
+    });
     if (obj_.needs_host()) host_evaluate_rows(X_, f_, 2 * c.mu, c.n, c.ld, c.honor_stop);
     sampled_ = true;
 }
 
 void HeesEngine::part_rank()
 {
-    timer_.begin(stream_, K_RANK);
-    hipLaunchKernelGGL(hees_rank, dim3((2 * c_.mu + 31) / 32, c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] {
+        hipLaunchKernelGGL(hees_rank, dim3((2 * c_.mu + 31) / 32, c_.npop), dim3(256), 0, stream_, d_, c_);
+    });
 }
 
 void HeesEngine::part_update()
 {
     const int t = (c_.n + 15) / 16;
-    timer_.begin(stream_, K_UPDATE);
-    hipLaunchKernelGGL(hees_update, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
+    timed(K_UPDATE, [&] { hipLaunchKernelGGL(hees_update, dim3(c_.npop), dim3(256), 0, stream_, d_, c_); });
     sampled_ = false;
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_ADAPT);
-    if (use_mfma()) hipLaunchKernelGGL(hees_adapt_mfma, dim3(t, t, c_.npop), dim3(256), 0, stream_, d_, c_);
-    else hipLaunchKernelGGL(hees_adapt, dim3(t, t, c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_ADAPT, [&] {
+        if (use_mfma()) hipLaunchKernelGGL(hees_adapt_mfma, dim3(t, t, c_.npop), dim3(256), 0, stream_, d_, c_);
+        else hipLaunchKernelGGL(hees_adapt, dim3(t, t, c_.npop), dim3(256), 0, stream_, d_, c_);
+    });
 }
 
 void HeesEngine::part_finish(bool init_only)
 {
     if (obj_.needs_host()) host_mean();
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(hees_finish, dim3(c_.npop), dim3(256), 0, stream_, d_, c_, init_only ? 1 : 0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_FINISH, [&] {
+        hipLaunchKernelGGL(hees_finish, dim3(c_.npop), dim3(256), 0, stream_, d_, c_, init_only ? 1 : 0);
+    });
 }
 
 void HeesEngine::generation(bool honor_stop)
@@ -240,15 +231,13 @@ void HeesEngine::generation(bool honor_stop)
 
 void HeesEngine::phase(int which)
 {
-    enter("phase()");
-    BBO_REQUIRE(which >= 0 && which <= 3, "HEES phase: 0 sample, 1 rank, 2 update, 3 finish");
-    c_.honor_stop = 0;
-    if (which == 0) part_sample();
-    else if (which == 1) part_rank();
-    else if (which == 2) part_update();
-    else part_finish(false);
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("phase()", which, 4, "HEES phase: 0 sample, 1 rank, 2 update, 3 finish", [&] {
+        c_.honor_stop = 0;
+        if (which == 0) part_sample();
+        else if (which == 1) part_rank();
+        else if (which == 2) part_update();
+        else part_finish(false);
+    });
 }
 
 void HeesEngine::inject_normals(const double *z, int count)

@@ -131,17 +131,11 @@ void JayaEngine::init(int n, const double *lower, const double *upper, const dou
     hipLaunchKernelGGL(jaya_init_eval, dim3((c.np + 3) / 4, P), dim3(256), 4 * ld * sizeof(double),
             stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (obj_.needs_host()) host_evaluate(true);
+    // host objective: the pool, and in generation() the trials, in slot order like the reference's loop
+    if (obj_.needs_host()) host_evaluate_rows(X_, f_, c.np, c.n, c.ld, c.honor_stop, &occ_);
     hipLaunchKernelGGL(jaya_finish, dim3(P), dim3(256), 0, stream_, d_, c_, 1);
     BBO_HIP(hipGetLastError());
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// host objective: the pool (init) or the trials of this generation, in slot order like the
-// reference's loop
-void JayaEngine::host_evaluate(bool init)
-{
-    host_evaluate_rows(init ? X_ : T_, init ? f_ : ftrial_, c_.np, c_.n, c_.ld, c_.honor_stop, &occ_);
 }
 
 void JayaEngine::generation(bool honor_stop)
@@ -149,28 +143,19 @@ void JayaEngine::generation(bool honor_stop)
     JayaConst &c = c_;
     c.honor_stop = honor_stop ? 1 : 0;
     const int P = c.npop;
-    timer_.begin(stream_, K_PARTITION);
-    hipLaunchKernelGGL(jaya_partition, dim3(P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_EVOLVE);
-    {
+    timed(K_PARTITION, [&] { hipLaunchKernelGGL(jaya_partition, dim3(P), dim3(256), 0, stream_, d_, c_); });
+    timed(K_EVOLVE, [&] {
         const dim3 grid((c.np + 3) / 4, P);
         const size_t lds = (size_t) 4 * c.ld * sizeof(double);
         if (c.mutation == JAYA_LEVY) hipLaunchKernelGGL(jaya_evolve<true>, grid, dim3(256), lds, stream_, d_, c_);
         else hipLaunchKernelGGL(jaya_evolve<false>, grid, dim3(256), lds, stream_, d_, c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    });
     if (obj_.needs_host()) {
-        host_evaluate(false);
+        host_evaluate_rows(T_, ftrial_, c.np, c.n, c.ld, c.honor_stop, &occ_);
         hipLaunchKernelGGL(jaya_select, dim3((c.np + 3) / 4, P), dim3(256), 0, stream_, d_, c_);
         BBO_HIP(hipGetLastError());
     }
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(jaya_finish, dim3(P), dim3(256), 0, stream_, d_, c_, 0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_FINISH, [&] { hipLaunchKernelGGL(jaya_finish, dim3(P), dim3(256), 0, stream_, d_, c_, 0); });
 }
 
 void JayaEngine::solution(int population, double *x_out, int *n_evals, int *converged)

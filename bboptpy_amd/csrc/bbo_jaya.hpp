@@ -79,7 +79,6 @@ private:
     static const bbo_params &checked(const bbo_params &p);
     static void check_jaya(const bbo_params &p, const bbo_jaya_params &jp);
     void generation(bool honor_stop) override;
-    void host_evaluate(bool init);
     void alloc_record();
 
     bbo_jaya_params jp_ {};

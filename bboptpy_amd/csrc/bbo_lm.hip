@@ -195,48 +195,34 @@ void LmEngine::part_sample()
         g_.upload(g.data(), g.size());
         draws_next_++;
     } else {
-        timer_.begin(stream_, K_DRAW);
-        hipLaunchKernelGGL(lm_draw, dim3((c.half + 3) / 4, P), dim3(256), 0, stream_, d_, c_);
-        timer_.end(stream_);
-        BBO_HIP(hipGetLastError());
+        timed(K_DRAW, [&] { hipLaunchKernelGGL(lm_draw, dim3((c.half + 3) / 4, P), dim3(256), 0, stream_, d_, c_); });
     }
-    timer_.begin(stream_, K_SAMPLE);
-    launch_sample(c.n, dim3((c.half + LM_BLOCK - 1) / LM_BLOCK, P), stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_SAMPLE, [&] { launch_sample(c.n, dim3((c.half + LM_BLOCK - 1) / LM_BLOCK, P), stream_, d_, c_); });
 }
 
 void LmEngine::part_eval()
 {
-    timer_.begin(stream_, K_EVAL);
-    hipLaunchKernelGGL(lm_eval, dim3((c_.lambda + 3) / 4, c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_EVAL, [&] {
+        hipLaunchKernelGGL(lm_eval, dim3((c_.lambda + 3) / 4, c_.npop), dim3(256), 0, stream_, d_, c_);
+    });
     if (obj_.needs_host()) host_evaluate_rows(X_, f_, c_.lambda, c_.n, c_.ld, c_.honor_stop);
 }
 
 void LmEngine::part_rank()
 {
-    timer_.begin(stream_, K_RANK);
-    hipLaunchKernelGGL(lm_rank, dim3((c_.lambda + 31) / 32, c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] {
+        hipLaunchKernelGGL(lm_rank, dim3((c_.lambda + 31) / 32, c_.npop), dim3(256), 0, stream_, d_, c_);
+    });
 }
 
 void LmEngine::part_update()
 {
-    timer_.begin(stream_, K_UPDATE);
-    launch_update(c_.n, dim3(c_.npop), stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_UPDATE, [&] { launch_update(c_.n, dim3(c_.npop), stream_, d_, c_); });
 }
 
 void LmEngine::part_history()
 {
-    timer_.begin(stream_, K_HISTORY);
-    hipLaunchKernelGGL(lm_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_HISTORY, [&] { hipLaunchKernelGGL(lm_history_stop, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 void LmEngine::generation(bool honor_stop)
@@ -251,16 +237,14 @@ void LmEngine::generation(bool honor_stop)
 
 void LmEngine::phase(int which)
 {
-    enter("phase()");
-    BBO_REQUIRE(which >= 0 && which <= 4, "LmCMAES phase: 0 sample, 1 evaluate, 2 rank, 3 update, 4 history + stop");
-    c_.honor_stop = 0;
-    if (which == 0) part_sample();
-    else if (which == 1) part_eval();
-    else if (which == 2) part_rank();
-    else if (which == 3) part_update();
-    else part_history();
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("phase()", which, 5, "LmCMAES phase: 0 sample, 1 evaluate, 2 rank, 3 update, 4 history + stop", [&] {
+        c_.honor_stop = 0;
+        if (which == 0) part_sample();
+        else if (which == 1) part_eval();
+        else if (which == 2) part_rank();
+        else if (which == 3) part_update();
+        else part_history();
+    });
 }
 
 void LmEngine::inject_draws(const double *table, int count)

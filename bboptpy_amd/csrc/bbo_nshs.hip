@@ -90,8 +90,7 @@ void NshsEngine::init(int n, const double *lower, const double *upper, const dou
     f_.alloc(rows);
     cand_.alloc((size_t) P * c.ld);
     fcand_.alloc(P);
-    draws_.alloc(0);
-    inject_.alloc(0);
+    tables_.clear();
     scal_.alloc(P);
     upload_box(n, c.ld, lower, upper, obj);
     std::vector<NshsScal> sc(P);
@@ -109,7 +108,7 @@ void NshsEngine::init(int n, const double *lower, const double *upper, const dou
 
     if (obj_.needs_host()) {
         launch_init(0, P, NSHS_INIT_DRAW);
-        host_evaluate_memory(0, P);
+        host_evaluate_range(X_, f_, 0, P, c.hms, 0, c.hms, n, c.ld);    // (in row order, like :60-67)
         launch_init(0, P, 0);
     } else {
         launch_init(0, P, NSHS_INIT_DRAW | NSHS_INIT_EVAL);
@@ -117,35 +116,14 @@ void NshsEngine::init(int n, const double *lower, const double *upper, const dou
     BBO_HIP(hipStreamSynchronize(stream_));
 }
 
-// host objective: the rows of the populations p0 .. p0 + pcount - 1 in row order, like the
-// reference's loop (:60-67)
-void NshsEngine::host_evaluate_memory(int p0, int pcount)
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int hms = c_.hms, ld = c_.ld;
-    std::vector<double> xh((size_t) hms * ld), fh(hms);
-    for (int p = p0; p < p0 + pcount; p++) {
-        X_.download(xh.data(), xh.size(), (size_t) p * hms * ld);
-        obj_.eval_host(xh.data(), hms, c_.n, ld, fh.data());
-        nan_to_inf(fh.data(), hms);
-        f_.upload(fh.data(), hms, (size_t) p * hms);
-    }
-}
-
 void NshsEngine::launch_init(int p0, int pcount, int mode)
 {
-    timer_.begin(stream_, K_INIT);
-    hipLaunchKernelGGL(nshs_init, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, mode);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_INIT, [&] { hipLaunchKernelGGL(nshs_init, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, mode); });
 }
 
 void NshsEngine::launch_generate()
 {
-    timer_.begin(stream_, K_GENERATE);
-    hipLaunchKernelGGL(nshs_generate, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_GENERATE, [&] { hipLaunchKernelGGL(nshs_generate, dim3(c_.npop), dim3(256), 0, stream_, d_, c_); });
 }
 
 void NshsEngine::launch_eval()
@@ -155,32 +133,25 @@ void NshsEngine::launch_eval()
         host_evaluate_rows(cand_, fcand_, 1, c_.n, c_.ld, c_.honor_stop != 0);
         return;
     }
-    timer_.begin(stream_, K_EVAL);
-    hipLaunchKernelGGL(nshs_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_EVAL, [&] { hipLaunchKernelGGL(nshs_eval, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 void NshsEngine::launch_replace()
 {
-    timer_.begin(stream_, K_REPLACE);
-    hipLaunchKernelGGL(nshs_replace, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_REPLACE, [&] { hipLaunchKernelGGL(nshs_replace, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 void NshsEngine::launch_steps(int k)
 {
     const bool lds = hm_in_lds();
     const size_t bytes = ((size_t) 3 * c_.ld + (lds ? (size_t) c_.hms * (c_.ld + 1) : 0)) * sizeof(double);
-    timer_.begin(stream_, K_STEPS);
-    switch (workgroup()) {
-    case 64: launch_steps_t<64>(lds, c_.npop, bytes, stream_, d_, c_, k); break;
-    case 128: launch_steps_t<128>(lds, c_.npop, bytes, stream_, d_, c_, k); break;
-    default: launch_steps_t<256>(lds, c_.npop, bytes, stream_, d_, c_, k); break;
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_STEPS, [&] {
+        switch (workgroup()) {
+        case 64: launch_steps_t<64>(lds, c_.npop, bytes, stream_, d_, c_, k); break;
+        case 128: launch_steps_t<128>(lds, c_.npop, bytes, stream_, d_, c_, k); break;
+        default: launch_steps_t<256>(lds, c_.npop, bytes, stream_, d_, c_, k); break;
+        }
+    });
 }
 
 // one iteration in its three parts: the path of bbo_iterate and of a host objective
@@ -219,15 +190,13 @@ void NshsEngine::iterate()
 // the three parts of iterate(), one at a time
 void NshsEngine::phase(int which)
 {
-    enter("bbo_nshs_phase");
-    BBO_REQUIRE(which >= 0 && which <= 2, "bbo_nshs_phase: 0 generate, 1 evaluate, 2 replace");
-    require_iterations("bbo_nshs_phase");
-    c_.honor_stop = 0;
-    if (which == 0) launch_generate();
-    else if (which == 1) launch_eval();
-    else launch_replace();
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("bbo_nshs_phase", which, 3, "bbo_nshs_phase: 0 generate, 1 evaluate, 2 replace", [&] {
+        require_iterations("bbo_nshs_phase");
+        c_.honor_stop = 0;
+        if (which == 0) launch_generate();
+        else if (which == 1) launch_eval();
+        else launch_replace();
+    });
 }
 
 void NshsEngine::inject_uniforms(const double *u, int count)
@@ -242,9 +211,7 @@ void NshsEngine::inject_uniforms(const double *u, int count)
     BBO_REQUIRE(count >= 0 && (size_t) count == want, "bbo_nshs_inject_uniforms: populations * n * 4 values");
     for (size_t q = 0; q < want; q++)
         BBO_REQUIRE(u[q] >= 0. && u[q] < 1., "bbo_nshs_inject_uniforms: uniforms lie in [0, 1)");
-    if (!inject_.p) inject_.alloc(want);
-    inject_.upload(u, want);
-    d_.inject = inject_.p;
+    d_.inject = tables_.load(u, want);
 }
 
 void NshsEngine::solution(int population, double *x_out, int *n_evals, int *converged)
@@ -271,7 +238,7 @@ int NshsEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "xbest") return o.vec(X_, (pb + s.ibest) * c.ld, c.n);
     if (k == "draws") {
         require_record(c.record, k);
-        return o.vec(draws_, (size_t) p * c.n * 4, c.n * 4);
+        return o.vec(tables_.draws, (size_t) p * c.n * 4, c.n * 4);
     }
     if (k == "fbest") return o.one(s.fbest);
     if (k == "fworst") return o.one(s.fworst);
@@ -307,8 +274,7 @@ int NshsEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "record_draws") {      // (the whole handle: every population)
         BBO_REQUIRE(count == 1, "record_draws: one value");
         c_.record = in[0] != 0. ? 1 : 0;
-        if (c_.record && !draws_.p) draws_.alloc((size_t) c.npop * c.n * 4);
-        d_.draws = c_.record ? draws_.p : nullptr;
+        d_.draws = tables_.record(c_.record != 0, (size_t) c.npop * c.n * 4);
         return 1;
     }
     if (k == "dbg") {
@@ -326,7 +292,7 @@ int NshsEngine::set(const std::string &k, int p, const double *in, int count)
         BBO_REQUIRE(count == c.hms * c.n, "x: hms * n values");
         upload_rows(X_, pb, c.hms, c.n, c.ld, in);
         if (obj_.needs_host()) {
-            host_evaluate_memory(p, 1);
+            host_evaluate_range(X_, f_, p, 1, c.hms, 0, c.hms, c.n, c.ld);
             launch_init(p, 1, 0);
         } else {
             launch_init(p, 1, NSHS_INIT_EVAL);

@@ -99,14 +99,14 @@ private:
     void launch_eval();
     void launch_replace();
     void launch_steps(int k);
-    void host_evaluate_memory(int p0, int pcount);
     bool hm_in_lds() const;
     int workgroup() const;
 
     bbo_nshs_params np_ {};
     NshsConst c_ {};
     NshsDev d_ {};
-    DevBuf<double> X_, f_, cand_, fcand_, draws_, inject_;
+    DevBuf<double> X_, f_, cand_, fcand_;
+    DrawTables tables_;      // [P][n][4] uniforms: the injected table and the recorded one
     int wg_ = 0;             // bbo_set "wg": 0 = by n, else 64, 128 or 256 threads for nshs_steps
 };
 

@@ -106,7 +106,7 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
             (size_t) R * c.ld * sizeof(double), stream_, d_, c_);
     BBO_HIP(hipGetLastError());
     if (obj_.needs_host()) {
-        host_evaluate_swarm();
+        host_evaluate_range(X_, f_, 0, P, c.np, 0, c.np, c.n, c.ld);
         hipLaunchKernelGGL(pso_copy_fb, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_,
                 c_);
         BBO_HIP(hipGetLastError());
@@ -114,25 +114,6 @@ void PsoEngine::init(int n, const double *lower, const double *upper, const doub
     hipLaunchKernelGGL(pso_gbest_init, dim3(P), dim3(256), 0, stream_, d_, c_);
     BBO_HIP(hipGetLastError());
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// the particles [i0, i1) of every population through the host objective (i1 < 0: the whole swarm)
-void PsoEngine::host_evaluate_swarm(int i0, int i1)
-{
-    const PsoConst &c = c_;
-    if (i1 < 0) i1 = c.np;
-    const int cnt = i1 - i0;
-    BBO_HIP(hipStreamSynchronize(stream_));
-    std::vector<PsoScal> sc(c.npop);
-    scal_.download(sc.data(), c.npop);
-    std::vector<double> xh((size_t) cnt * c.ld), fh(cnt);
-    for (int p = 0; p < c.npop; p++) {
-        if (c.honor_stop && sc[p].stop) continue;
-        X_.download(xh.data(), xh.size(), ((size_t) p * c.np + i0) * c.ld);
-        obj_.eval_host(xh.data(), cnt, c.n, c.ld, fh.data());
-        nan_to_inf(fh.data(), cnt);
-        f_.upload(fh.data(), cnt, (size_t) p * c.np + i0);
-    }
 }
 
 void PsoEngine::host_evaluate_elite()
@@ -163,24 +144,20 @@ void PsoEngine::generation(bool honor_stop)
     dim3 g16((c.np + 15) / 16, P);
     const int R = rows_per_wg16(c.ld);     // rows staged in LDS per workgroup
     const size_t ldsR = (size_t) R * c.ld * sizeof(double);
-    timer_.begin(stream_, K_CENTER);
-    hipLaunchKernelGGL(pso_center, dim3(parts_, P), dim3(256), 0, stream_, d_, c_, parts_);
-    hipLaunchKernelGGL(pso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, parts_);
-    hipLaunchKernelGGL(pso_nrm, g16, dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_ESE);
-    {
+    timed(K_CENTER, [&] {
+        hipLaunchKernelGGL(pso_center, dim3(parts_, P), dim3(256), 0, stream_, d_, c_, parts_);
+        hipLaunchKernelGGL(pso_mean, dim3(P), dim3(256), 0, stream_, d_, c_, parts_);
+        hipLaunchKernelGGL(pso_nrm, g16, dim3(256), 0, stream_, d_, c_);
+    });
+    timed(K_ESE, [&] {
         const size_t lds = (size_t) ESE2_LDS_DOUBLES * sizeof(double);
         allow_lds((const void*) pso_ese_sym, (int) lds);
         hipLaunchKernelGGL(pso_ese_sym, dim3((c.np + 127) / 128, P), dim3(256), lds, stream_, d_,
                 c_);
         hipLaunchKernelGGL(pso_ese_finish, dim3((c.np + 255) / 256, P), dim3(256), 0, stream_, d_,
                 c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_CTRL);
+    });
+    timer_.begin(stream_, K_CTRL);      // (the host's evaluation of the elite lies between its two launches)
     hipLaunchKernelGGL(pso_control_a, dim3(P), dim3(256), 0, stream_, d_, c_);
     BBO_HIP(hipGetLastError());
     if (obj_.needs_host()) host_evaluate_elite();
@@ -195,26 +172,20 @@ void PsoEngine::generation(bool honor_stop)
     // and the closing kernel)
     for (int i0 = 0; i0 < c.np; i0 += step) {
         const int i1 = std::min(c.np, i0 + step);
-        timer_.begin(stream_, K_UPDATE);
-        hipLaunchKernelGGL(pso_update, dim3((i1 - i0 + R - 1) / R, P), dim3(16 * R), ldsR, stream_, d_,
-                c_, i0, i1);
-        timer_.end(stream_);
+        timed(K_UPDATE, [&] {
+            hipLaunchKernelGGL(pso_update, dim3((i1 - i0 + R - 1) / R, P), dim3(16 * R), ldsR, stream_, d_,
+                    c_, i0, i1);
+        });
         if (obj_.needs_host()) {
-            host_evaluate_swarm(i0, i1);
+            host_evaluate_range(X_, f_, 0, P, c.np, i0, i1, c.n, c.ld, c.honor_stop != 0);   // (this chunk's particles)
             hipLaunchKernelGGL(pso_pbest, dim3((i1 - i0 + 15) / 16, P), dim3(256), 0, stream_, d_, c_, i0,
                     i1);
         }
-        if (i1 < c.np) {
-            timer_.begin(stream_, K_FINISH);
-            hipLaunchKernelGGL(pso_gbest, dim3(P), dim3(256), 0, stream_, d_, c_, i0, i1);
-            timer_.end(stream_);
-        }
+        if (i1 < c.np)
+            timed(K_FINISH, [&] { hipLaunchKernelGGL(pso_gbest, dim3(P), dim3(256), 0, stream_, d_, c_, i0, i1); });
     }
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_FINISH);
-    hipLaunchKernelGGL(pso_finish, dim3(P), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    BBO_HIP(hipGetLastError());     // (pso_pbest's)
+    timed(K_FINISH, [&] { hipLaunchKernelGGL(pso_finish, dim3(P), dim3(256), 0, stream_, d_, c_); });
 }
 
 void PsoEngine::inspect(const std::vector<PsoScal> &sc)

@@ -71,7 +71,6 @@ private:
     bool budget_spent(const PsoScal &s) const override { return s.it >= s.maxit || s.fev >= c_.mfev; }
     void inspect(const std::vector<PsoScal> &sc) override;   // throws on a bad rule base
     void after_chunk(bool in_run) override;                  // iterate() looks at the rule base too
-    void host_evaluate_swarm(int i0 = 0, int i1 = -1);
     void host_evaluate_elite();
 
     PsoConst c_ {};

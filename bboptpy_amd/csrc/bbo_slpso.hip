@@ -124,26 +124,12 @@ void SlpsoEngine::init(int n, const double *lower, const double *upper, const do
 
     if (obj_.needs_host()) {
         launch_init(0, P, SLPSO_INIT_DRAW);
-        host_evaluate_swarm(0, P);
+        host_evaluate_range(x_, fx_, 0, P, c.np, 0, c.np, n, c.ld);     // (in swarm order: :84-91)
         launch_init(0, P, SLPSO_INIT_RESET | SLPSO_INIT_PAR);
     } else {
         launch_init(0, P, SLPSO_INIT_DRAW | SLPSO_INIT_EVAL | SLPSO_INIT_RESET | SLPSO_INIT_PAR);
     }
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// host objective: the particles of the populations p0 .. p0 + pcount - 1 in swarm order (:84-91)
-void SlpsoEngine::host_evaluate_swarm(int p0, int pcount)
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int np = c_.np, ld = c_.ld;
-    std::vector<double> xh((size_t) np * ld), fh(np);
-    for (int p = p0; p < p0 + pcount; p++) {
-        x_.download(xh.data(), xh.size(), (size_t) p * np * ld);
-        obj_.eval_host(xh.data(), np, c_.n, ld, fh.data());
-        nan_to_inf(fh.data(), np);
-        fx_.upload(fh.data(), np, (size_t) p * np);
-    }
 }
 
 void SlpsoEngine::launch_init(int p0, int pcount, int mode)
@@ -289,7 +275,7 @@ int SlpsoEngine::set(const std::string &k, int p, const double *in, int count)
         mid_generation_ = false;
         if (obj_.needs_host()) {
             launch_init(0, c.npop, SLPSO_INIT_DRAW);
-            host_evaluate_swarm(0, c.npop);
+            host_evaluate_range(x_, fx_, 0, c.npop, c.np, 0, c.np, c.n, c.ld);
             launch_init(0, c.npop, SLPSO_INIT_RESET | SLPSO_INIT_PAR);
         } else {
             launch_init(0, c.npop, SLPSO_INIT_DRAW | SLPSO_INIT_EVAL | SLPSO_INIT_RESET | SLPSO_INIT_PAR);
@@ -302,7 +288,7 @@ int SlpsoEngine::set(const std::string &k, int p, const double *in, int count)
         upload_rows(x_, pr, c.np, c.n, c.ld, in);
         if (c.npop == 1) mid_generation_ = false;   // (the generation in progress, if any, is abandoned)
         if (obj_.needs_host()) {
-            host_evaluate_swarm(p, 1);
+            host_evaluate_range(x_, fx_, p, 1, c.np, 0, c.np, c.n, c.ld);
             launch_init(p, 1, SLPSO_INIT_RESET | SLPSO_INIT_PAR);
         } else {
             launch_init(p, 1, SLPSO_INIT_EVAL | SLPSO_INIT_RESET | SLPSO_INIT_PAR);

@@ -93,7 +93,6 @@ private:
     PendingPoints pending_points(int p, const SlpsoScal&) override { return { &cand_, (size_t) p * c_.ld, 1, c_.ld, &fcand_ }; }
     int &honor_stop() override { return c_.honor_stop; }
     void launch_init(int p0, int pcount, int mode);
-    void host_evaluate_swarm(int p0, int pcount);
     int workgroup() const;
     size_t table_len() const { return 1 + (size_t) c_.np + (size_t) c_.np * (3 + 4 * (size_t) c_.n); }
 

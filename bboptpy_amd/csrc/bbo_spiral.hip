@@ -90,8 +90,7 @@ void SpiralEngine::init(int n, const double *lower, const double *upper, const d
     cs_.alloc(rows);
     sn_.alloc(rows);
     xbest_.alloc((size_t) P * c.ld);
-    draws_.alloc(0);
-    inject_.alloc(0);
+    tables_.clear();
     tile_.alloc(0);
     tile_split_ = 0;
     scal_.alloc(P);
@@ -112,37 +111,17 @@ void SpiralEngine::init(int n, const double *lower, const double *upper, const d
 
     hipLaunchKernelGGL(spiral_init, dim3((c.np + 3) / 4, P), dim3(256), 0, stream_, d_, c_);
     BBO_HIP(hipGetLastError());
-    if (obj_.needs_host()) host_evaluate(0, P);
-    else launch_eval(0, P);
+    launch_eval(0, P);
     launch_best(0, P, 0);
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// host objective: the rows of the populations p0 .. p0 + pcount - 1 in row order, like the
-// reference's loop
-void SpiralEngine::host_evaluate(int p0, int pcount)
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int np = c_.np, ld = c_.ld;
-    std::vector<SpiralScal> sc(c_.npop);
-    scal_.download(sc.data(), sc.size());
-    std::vector<double> xh((size_t) np * ld), fh(np);
-    for (int p = p0; p < p0 + pcount; p++) {
-        if (c_.honor_stop && sc[p].stop) continue;
-        X_.download(xh.data(), xh.size(), (size_t) p * np * ld);
-        obj_.eval_host(xh.data(), np, c_.n, ld, fh.data());
-        nan_to_inf(fh.data(), np);
-        f_.upload(fh.data(), np, (size_t) p * np);
-    }
 }
 
 void SpiralEngine::launch_draw()
 {
     const long total = (long) c_.npop * c_.np;
-    timer_.begin(stream_, K_DRAW);
-    hipLaunchKernelGGL(spiral_draw, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_DRAW, [&] {
+        hipLaunchKernelGGL(spiral_draw, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, stream_, d_, c_);
+    });
 }
 
 void SpiralEngine::launch_rotate()
@@ -156,31 +135,31 @@ void SpiralEngine::launch_rotate()
         tile_split_ = split;
     }
     d_.tile = tile_.p;
-    timer_.begin(stream_, K_ROTATE);
-    switch (c_.kfuse) {
-    case 1: launch_rotate_k<1>(split, grid, stream_, d_, c_); break;
-    case 2: launch_rotate_k<2>(split, grid, stream_, d_, c_); break;
-    case 4: launch_rotate_k<4>(split, grid, stream_, d_, c_); break;
-    default: launch_rotate_k<8>(split, grid, stream_, d_, c_); break;
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_ROTATE, [&] {
+        switch (c_.kfuse) {
+        case 1: launch_rotate_k<1>(split, grid, stream_, d_, c_); break;
+        case 2: launch_rotate_k<2>(split, grid, stream_, d_, c_); break;
+        case 4: launch_rotate_k<4>(split, grid, stream_, d_, c_); break;
+        default: launch_rotate_k<8>(split, grid, stream_, d_, c_); break;
+        }
+    });
 }
 
 void SpiralEngine::launch_eval(int p0, int pcount)
 {
-    timer_.begin(stream_, K_EVAL);
-    hipLaunchKernelGGL(spiral_eval, dim3((c_.np + 3) / 4, pcount), dim3(256), 0, stream_, d_, c_, p0);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    if (obj_.needs_host()) {
+        // the rows of the populations p0 .. p0 + pcount - 1 in row order, like the reference's loop
+        host_evaluate_range(X_, f_, p0, pcount, c_.np, 0, c_.np, c_.n, c_.ld, c_.honor_stop != 0);
+        return;
+    }
+    timed(K_EVAL, [&] {
+        hipLaunchKernelGGL(spiral_eval, dim3((c_.np + 3) / 4, pcount), dim3(256), 0, stream_, d_, c_, p0);
+    });
 }
 
 void SpiralEngine::launch_best(int p0, int pcount, int counters)
 {
-    timer_.begin(stream_, K_BEST);
-    hipLaunchKernelGGL(spiral_best, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, counters);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_BEST, [&] { hipLaunchKernelGGL(spiral_best, dim3(pcount), dim3(256), 0, stream_, d_, c_, p0, counters); });
 }
 
 void SpiralEngine::generation(bool honor_stop)
@@ -188,25 +167,20 @@ void SpiralEngine::generation(bool honor_stop)
     c_.honor_stop = honor_stop ? 1 : 0;
     launch_draw();
     launch_rotate();
-    if (obj_.needs_host()) host_evaluate(0, c_.npop);
-    else launch_eval(0, c_.npop);
+    launch_eval(0, c_.npop);
     launch_best(0, c_.npop, 1);
 }
 
 // the four parts of iterate(), one at a time
 void SpiralEngine::phase(int which)
 {
-    enter("bbo_spiral_phase");
-    BBO_REQUIRE(which >= 0 && which <= 3, "bbo_spiral_phase: 0 draw, 1 rotate, 2 evaluate, 3 best");
-    c_.honor_stop = 0;
-    if (which == 0) launch_draw();
-    else if (which == 1) launch_rotate();
-    else if (which == 2) {
-        if (obj_.needs_host()) host_evaluate(0, c_.npop);
-        else launch_eval(0, c_.npop);
-    } else launch_best(0, c_.npop, 1);
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("bbo_spiral_phase", which, 4, "bbo_spiral_phase: 0 draw, 1 rotate, 2 evaluate, 3 best", [&] {
+        c_.honor_stop = 0;
+        if (which == 0) launch_draw();
+        else if (which == 1) launch_rotate();
+        else if (which == 2) launch_eval(0, c_.npop);
+        else launch_best(0, c_.npop, 1);
+    });
 }
 
 void SpiralEngine::inject_uniforms(const double *u, int count)
@@ -221,9 +195,7 @@ void SpiralEngine::inject_uniforms(const double *u, int count)
     BBO_REQUIRE(count >= 0 && (size_t) count == want, "bbo_spiral_inject_uniforms: populations * np * 4 values");
     for (size_t q = 0; q < want; q++)
         BBO_REQUIRE(u[q] >= 0. && u[q] < 1., "bbo_spiral_inject_uniforms: uniforms lie in [0, 1)");
-    if (!inject_.p) inject_.alloc(want);
-    inject_.upload(u, want);
-    d_.inject = inject_.p;
+    d_.inject = tables_.load(u, want);
 }
 
 void SpiralEngine::solution(int population, double *x_out, int *n_evals, int *converged)
@@ -252,7 +224,7 @@ int SpiralEngine::get(const std::string &k, int p, double *out, int cap)
     if (k == "xbest") return o.vec(xbest_, (size_t) p * c.ld, c.n);
     if (k == "draws") {
         require_record(c.record, k);
-        return o.vec(draws_, pb * 4, c.np * 4);
+        return o.vec(tables_.draws, pb * 4, c.np * 4);
     }
     if (k == "fbest") return o.one(s.fbest);
     if (k == "ibest") return o.one(s.ibest);
@@ -278,8 +250,7 @@ int SpiralEngine::set(const std::string &k, int p, const double *in, int count)
     if (k == "record_draws") {      // (the whole handle: every population)
         BBO_REQUIRE(count == 1, "record_draws: one value");
         c_.record = in[0] != 0. ? 1 : 0;
-        if (c_.record && !draws_.p) draws_.alloc((size_t) c.npop * c.np * 4);
-        d_.draws = c_.record ? draws_.p : nullptr;
+        d_.draws = tables_.record(c_.record != 0, (size_t) c.npop * c.np * 4);
         return 1;
     }
     if (k == "dbg") {
@@ -296,8 +267,7 @@ int SpiralEngine::set(const std::string &k, int p, const double *in, int count)
         BBO_REQUIRE(count == c.np * c.n, "x: np * n values");
         upload_rows(X_, pb, c.np, c.n, c.ld, in);
         c_.honor_stop = 0;
-        if (obj_.needs_host()) host_evaluate(p, 1);
-        else launch_eval(p, 1);
+        launch_eval(p, 1);
         launch_best(p, 1, 0);
         BBO_HIP(hipStreamSynchronize(stream_));
         return count;

@@ -87,14 +87,14 @@ private:
     void launch_rotate();
     void launch_eval(int p0, int pcount);
     void launch_best(int p0, int pcount, int counters);
-    void host_evaluate(int p0, int pcount);
     int lds_coords() const;
     int tile_split() const;
 
     bbo_spiral_params sp_ {};
     SpiralConst c_ {};
     SpiralDev d_ {};
-    DevBuf<double> X_, f_, r_, theta_, cs_, sn_, xbest_, draws_, inject_, tile_;
+    DevBuf<double> X_, f_, r_, theta_, cs_, sn_, xbest_, tile_;
+    DrawTables tables_;      // [P][np][4] uniforms: the injected table and the recorded one
     int tile_split_ = 0;     // the split tile_ was allocated for
 };
 

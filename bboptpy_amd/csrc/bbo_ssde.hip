@@ -118,26 +118,13 @@ void SsdeEngine::seed_pool(int p0, int pcount)
     const int draw = SSDE_INIT_DRAW | (c_.usede ? SSDE_INIT_OPP : 0), rank = SSDE_INIT_RESET | SSDE_INIT_SORT;
     if (obj_.needs_host()) {
         launch_init(p0, pcount, draw, 0, 0);
-        host_evaluate_rows_of(p0, pcount, 0, c_.nrows);     // (the points, then their opposites: :95, :107)
+        // (the points, then their opposites: :95, :107)
+        host_evaluate_range(x_, f_, p0, pcount, c_.nrows, 0, c_.nrows, c_.n, c_.ld);
         launch_init(p0, pcount, rank, 0, c_.nrows);
     } else {
         launch_init(p0, pcount, draw | SSDE_INIT_EVAL | rank, 0, c_.nrows);
     }
     BBO_HIP(hipStreamSynchronize(stream_));
-}
-
-// host objective: the rows [r0, r1) of the populations p0 .. p0 + pcount - 1 in row order
-void SsdeEngine::host_evaluate_rows_of(int p0, int pcount, int r0, int r1)
-{
-    BBO_HIP(hipStreamSynchronize(stream_));
-    const int ld = c_.ld, cnt = r1 - r0;
-    std::vector<double> xh((size_t) cnt * ld), fh(cnt);
-    for (int p = p0; p < p0 + pcount; p++) {
-        x_.download(xh.data(), xh.size(), ((size_t) p * c_.nrows + r0) * ld);
-        obj_.eval_host(xh.data(), cnt, c_.n, ld, fh.data());
-        nan_to_inf(fh.data(), cnt);
-        f_.upload(fh.data(), cnt, (size_t) p * c_.nrows + r0);
-    }
 }
 
 void SsdeEngine::launch_init(int p0, int pcount, int mode, int r0, int r1)
@@ -284,7 +271,7 @@ int SsdeEngine::set(const std::string &k, int p, const double *in, int count)
         upload_rows(x_, (size_t) p * c.nrows, m, c.n, c.ld, in);
         if (c.npop == 1) mid_generation_ = false;   // (the generation in progress, if any, is abandoned)
         if (obj_.needs_host()) {
-            host_evaluate_rows_of(p, 1, 0, m);
+            host_evaluate_range(x_, f_, p, 1, c.nrows, 0, m, c.n, c.ld);
             launch_init(p, 1, SSDE_INIT_SORT, 0, m);
         } else {
             launch_init(p, 1, SSDE_INIT_EVAL | SSDE_INIT_SORT, 0, m);

@@ -104,7 +104,6 @@ private:
     int &honor_stop() override { return c_.honor_stop; }
     void seed_pool(int p0, int pcount);
     void launch_init(int p0, int pcount, int mode, int r0, int r1);
-    void host_evaluate_rows_of(int p0, int pcount, int r0, int r1);
     int workgroup() const;
     size_t table_len() const { return (size_t) c_.n + (size_t) c_.npinit * (SSDE_REC_HEAD + 3 * (size_t) c_.n); }
     void set_memory(DevBuf<double> &b, int p, const double *in, int count, const char *what);

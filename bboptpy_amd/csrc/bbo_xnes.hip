@@ -130,53 +130,44 @@ void XnesEngine::part_sample()
     if (zin_gens_ > 0 && zin_pos_ >= zin_gens_)
         throw Error(BBO_ERR_STATE, "xNES: the injected normals are used up (inject more, or NULL for the "
                 "device's draws)");
-    timer_.begin(stream_, K_DRAW);
-    if (zin_gens_ > 0) {
-        d_.zin = zin_.p + (size_t) zin_pos_ * P * c.np * c.ld;
-        zin_pos_++;
-        hipLaunchKernelGGL(xnes_take, rows, dim3(256), 0, stream_, d_, c_);
-    } else {
-        hipLaunchKernelGGL(xnes_draw, rows, dim3(256), 0, stream_, d_, c_);
-        hipLaunchKernelGGL(xnes_settle, rows, dim3(256), 0, stream_, d_, c_);
-    }
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
-    timer_.begin(stream_, K_POINTS);
-    if (c.n >= XNES_MFMA_MIN_N)
-        hipLaunchKernelGGL(xnes_points_mfma, dim3(P), dim3(256), (size_t) c.np * c.ld * sizeof(double), stream_,
-                d_, c_);
-    else
-        hipLaunchKernelGGL(xnes_points, rows, dim3(256), (size_t) 8 * c.ld * sizeof(double), stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    const bool take = zin_gens_ > 0;    // the next generation of the injected table
+    if (take) d_.zin = zin_.p + (size_t) zin_pos_++ * P * c.np * c.ld;
+    timed(K_DRAW, [&] {
+        if (take) {
+            hipLaunchKernelGGL(xnes_take, rows, dim3(256), 0, stream_, d_, c_);
+        } else {
+            hipLaunchKernelGGL(xnes_draw, rows, dim3(256), 0, stream_, d_, c_);
+            hipLaunchKernelGGL(xnes_settle, rows, dim3(256), 0, stream_, d_, c_);
+        }
+    });
+    timed(K_POINTS, [&] {
+        if (c.n >= XNES_MFMA_MIN_N)
+            hipLaunchKernelGGL(xnes_points_mfma, dim3(P), dim3(256), (size_t) c.np * c.ld * sizeof(double), stream_,
+                    d_, c_);
+        else
+            hipLaunchKernelGGL(xnes_points, rows, dim3(256), (size_t) 8 * c.ld * sizeof(double), stream_, d_, c_);
+    });
     if (obj_.needs_host()) host_evaluate_rows(X_, f_, c.np, c.n, c.ld, c.honor_stop);
 }
 
 void XnesEngine::part_rank()
 {
-    timer_.begin(stream_, K_RANK);
-    hipLaunchKernelGGL(xnes_rank, dim3(c_.npop), dim3(64), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_RANK, [&] { hipLaunchKernelGGL(xnes_rank, dim3(c_.npop), dim3(64), 0, stream_, d_, c_); });
 }
 
 void XnesEngine::part_step()
 {
-    timer_.begin(stream_, K_STEP);
-    hipLaunchKernelGGL(xnes_step, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_STEP, [&] { hipLaunchKernelGGL(xnes_step, dim3(c_.npop), dim3(256), 0, stream_, d_, c_); });
 }
 
 void XnesEngine::part_adapt()
 {
-    timer_.begin(stream_, K_ADAPT);
-    if (c_.lowrank)
-        hipLaunchKernelGGL(xnes_adapt_lr, dim3((c_.n + 15) / 16, c_.npop), dim3(256), 0, stream_, d_, c_);
-    else
-        hipLaunchKernelGGL(xnes_adapt_dense, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
-    timer_.end(stream_);
-    BBO_HIP(hipGetLastError());
+    timed(K_ADAPT, [&] {
+        if (c_.lowrank)
+            hipLaunchKernelGGL(xnes_adapt_lr, dim3((c_.n + 15) / 16, c_.npop), dim3(256), 0, stream_, d_, c_);
+        else
+            hipLaunchKernelGGL(xnes_adapt_dense, dim3(c_.npop), dim3(256), 0, stream_, d_, c_);
+    });
 }
 
 void XnesEngine::generation(bool honor_stop)
@@ -190,15 +181,13 @@ void XnesEngine::generation(bool honor_stop)
 
 void XnesEngine::phase(int which)
 {
-    enter("phase()");
-    BBO_REQUIRE(which >= 0 && which <= 3, "xNES phase: 0 sample, 1 rank, 2 small step, 3 adapt");
-    c_.honor_stop = 0;
-    if (which == 0) part_sample();
-    else if (which == 1) part_rank();
-    else if (which == 2) part_step();
-    else part_adapt();
-    BBO_HIP(hipStreamSynchronize(stream_));
-    timer_.collect();
+    run_phase("phase()", which, 4, "xNES phase: 0 sample, 1 rank, 2 small step, 3 adapt", [&] {
+        c_.honor_stop = 0;
+        if (which == 0) part_sample();
+        else if (which == 1) part_rank();
+        else if (which == 2) part_step();
+        else part_adapt();
+    });
 }
 
 void XnesEngine::inject_normals(const double *z, int count)

@@ -122,6 +122,7 @@ class _ObjectiveBinding:
             self.struct.scalar = self._keep
 
 
+# (the same list, in the library's words: Engine::reject_program, csrc/bbo_engine.hpp)
 PROGRAM_FAMILIES = ("CMAES, ActiveCMAES, SepCMAES, CholeskyCMAES (and IPopCMAES / BiPopCMAES over them), "
                     "JADE, SHADE, SANSDE, PIKAIA")
 
