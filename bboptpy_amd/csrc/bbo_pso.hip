@@ -253,7 +253,9 @@ int PsoEngine::set(const std::string &k, int p, const double *in, int count)
     enter_population("set()", p);
     const PsoConst &c = c_;
     if (k == "chunk") {        // 0 or >= np: the whole swarm sees the best of the generation start
-        chunk_ = (int) in[0] <= 0 ? c.np : (int) in[0];
+        BBO_REQUIRE(count == 1, "set: wrong element count");
+        BBO_REQUIRE(std::isfinite(in[0]) && in[0] >= 0., "set: chunk must be finite and >= 0");
+        chunk_ = in[0] < 1. || in[0] >= (double) c.np ? c.np : (int) in[0];
         return 1;
     }
     if (k == "profile") return profile_enable(in, K_COUNT, K_NAMES);

@@ -686,6 +686,9 @@ __global__ __launch_bounds__(256) void pso_gbest(PsoDev d, PsoConst c, int i0, i
     __shared__ int sidx[4];
     const int tid = threadIdx.x, np = c.np, ld = c.ld;
     const double *f = d.f + (size_t) p * np;
+    // the best so far, read before block_arg: its barriers put every wavefront's read ahead of
+    // thread 0's store below, so no wavefront sees the new value and skips its slice of the copy
+    const double fbest = sc->fbest;
     double fv = PSO_INF;
     int ib = 0x7fffffff;
     for (int i = i0 + tid; i < i1; i += 256)
@@ -694,7 +697,7 @@ __global__ __launch_bounds__(256) void pso_gbest(PsoDev d, PsoConst c, int i0, i
             ib = i;
         }
     block_arg<1>(fv, ib, sval, sidx);
-    const bool improved = ib != 0x7fffffff && fv < sc->fbest;
+    const bool improved = ib != 0x7fffffff && fv < fbest;
     if (improved)
         for (int j = tid; j < ld; j += 256)
             d.xbest[(size_t) p * ld + j] = d.X[((size_t) p * np + ib) * ld + j];

@@ -262,7 +262,8 @@ int bbo_run(bbo_handle h, int max_generations, int *generations_done);
  * One key changes semantics the reference's user can see: APSO "chunk" -- the number of particles
  * that move between two refreshes of the swarm's best inside a generation (the reference refreshes
  * after every particle, apso.cpp:194-197; the default here is np / 16 in whole workgroups, at least
- * 64; 0 = the whole swarm sees the best of the generation start). */
+ * 64; 0 or any value from np up = the whole swarm sees the best of the generation start; a NaN,
+ * infinite or negative value is BBO_ERR_ARG). */
 /* CholeskyCMAES (BBO_ALGO_CHOLESKY_CMAES): the keys the dense variants share (arx, xmean, xold,
  * sigma, pc, ps, fit_val, fit_idx, it, fev, flag, zlast, record_normals, ...) plus "A" (the lower
  * Cholesky factor of the covariance, n x n row-major, upper triangle exactly 0; readable and

@@ -81,9 +81,12 @@ def _box(n):
 
 
 # n = 5 and 17 AMaLGaM, 33 iAMaLGaM; n = 130 with np = 114: the factorisation through the global image;
-# n = 5 with np = 800: ss = 280, two slabs of the Gram
+# n = 5 with np = 800: ss = 280, two slabs of the Gram;
+# n = 257 (one live lane in the second pass of a 256-thread row loop), 301 (odd, no multiple of 4 or 64)
+# and 512 (the cap): rows, mean, covariance and factor well past AMALGAM_LDS_MAX_LD
 @pytest.mark.parametrize("n,iam,np_,gens", [(5, True, 0, 6), (5, False, 0, 6), (17, False, 0, 4), (33, True, 0, 6),
-                                            (130, True, 114, 3), (5, False, 800, 3)])
+                                            (130, True, 114, 3), (5, False, 800, 3),
+                                            (257, True, 114, 3), (301, True, 114, 3), (512, True, 114, 3)])
 def test_generations_against_the_device_form_of_the_model(hip, n, iam, np_, gens):
     P = 2
     obj = ["rosenbrock", "ellipsoid"][n % 2] if n != 5 else "rosenbrock"

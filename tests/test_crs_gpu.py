@@ -39,18 +39,18 @@ def _same_state(sa, sb, tag=""):
         _bits(sa[k], sb[k], tag + k)
 
 
-def _start(hip, n, np_, obj="rosenbrock", seed=7, P=1, mfev=10 ** 6, tol=0., box=5., lower=None, **kw):
+def _start(hip, n, np_, obj="rosenbrock", seed=7, P=1, mfev=10 ** 6, tol=0., box=5., lower=None, inner=0.84, **kw):
     """At n >= 63 a pool that fills the box reflects out of it in all but one trial in thousands (every
     coordinate has to stay inside), and the walk would be one run of B pushes into the depth cap: there
     the pool is set to points of the inner 84 % of the box, from which about every second or third
-    trial stays inside."""
+    trial stays inside (`inner`: another share, for the rows past n = 256)."""
     g = hip.CRS(mfev, np_, tol, seed=seed, populations=P, **kw)
     lo = -box * np.ones(n) if lower is None else lower * np.ones(n)
     g.initialize(obj, lo, box * np.ones(n) if lower is None else lo.copy(), np.zeros(P * n))
     if n >= 63 and lower is None:
         rng = np.random.default_rng(seed)
         for p in range(P):
-            g.set_state("x", rng.uniform(-0.84 * box, 0.84 * box, (np_, n)), p)
+            g.set_state("x", rng.uniform(-inner * box, inner * box, (np_, n)), p)
     return g
 
 
@@ -100,18 +100,32 @@ def _records(g, n, p=0):
     return g.get_state("draws", p).reshape(nrec, 2 * n)
 
 
-@pytest.mark.parametrize("np_", [2, 5, 70])
-@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 130])
+# rows past one pass of a 256-thread workgroup: one live lane in the second pass (257), an odd n that
+# is no multiple of 4 or 64 (301, ld = 302) and the cap; rosenbrock, ellipsoid, ellipsoid by the rule below
+# (rosenbrock at n = 512 with np = 8 runs into the depth cap in the very first iteration under one set of
+# draws in four: its first worst point is hard to beat; the ellipsoid with np = 12 walked all 20 iterations
+# under every one of 12 generators tried with the model)
+WIDE_SHAPES = [(257, 5), (301, 7), (512, 12)]
+WALK_SHAPES = [(n, np_) for np_ in (2, 5, 70) for n in (1, 2, 63, 64, 65, 130)]
+
+
+@pytest.mark.parametrize("n,np_", WALK_SHAPES + WIDE_SHAPES)
 def test_the_walk_is_the_model_bit_for_bit(hip, n, np_):
-    """40 iterations: the odd ones through bbo_crs_phase, the even ones fused (bbo_iterate and bbo_run in
-    turn).  The model reads the records the device logged.  A pool that collapses (np = 2 does) ends at
-    the depth cap, in the model at the same evaluation."""
+    """40 iterations (20 past n = 256): the odd ones through bbo_crs_phase, the even ones fused
+    (bbo_iterate and bbo_run in turn).  The model reads the records the device logged.  A pool that
+    collapses (np = 2 does) ends at the depth cap, in the model at the same evaluation.  Past n = 256
+    the pool starts in the inner 60 % of the box: with np <= 8 the centroid of n drawn rows is close to
+    the pool's mean, and from there the model with a generator of its own takes every path of the
+    recursion (B, M, an accepted mutation, a stale replacement) within 16 iterations."""
+    wide = n > 256
     obj = ("sphere", "rosenbrock", "ellipsoid")[(n + np_) % 3] if n > 1 else "sphere"
-    g = _start(hip, n, np_, obj=obj, seed=100 * n + np_, max_depth=DEPTH)
+    g = _start(hip, n, np_, obj=obj, seed=100 * n + np_, max_depth=DEPTH, **({"inner": 0.6} if wide else {}))
+    # a lane per coordinate up to 256: the walk runs the configuration its n is meant to reach
+    assert int(g.get_state("wg")[0]) == (64 if n <= 128 else 128 if n <= 256 else 256)
     g.set_state("record_draws", [float(RECORDS)])
     m = _model_of(g, n, np_, obj, 5., max_depth=DEPTH)
     tag0 = "n %d np %d " % (n, np_)
-    for it in range(40):
+    for it in range(20 if wide else 40):
         tag = tag0 + "iteration %d " % it
         if it % 2:
             _walk(g)
@@ -130,6 +144,8 @@ def test_the_walk_is_the_model_bit_for_bit(hip, n, np_):
             assert m.flag == 3 and m.maxdepth == DEPTH, tag
             break
     print(tag0, obj, "iterations", m.it, "fev", m.fev, "paths", m.paths, "flag", m.flag)
+    if wide:
+        assert m.it >= 10 and m.fev > np_ + m.it, "the wide walk ended early or never mutated: choose another pool"
 
 
 @pytest.mark.parametrize("n,np_", [(5, 20), (65, 5), (130, 70)])

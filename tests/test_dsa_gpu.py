@@ -175,6 +175,13 @@ CASES = [
     (-1, -1, 65, 70, 3, 0, "rosenbrock"),
     (-1, -1, 3, 7, 1, 1, "sphere"),
     (-1, -1, 130, 2, 1, 0, "sphere"),
+    # rows past one pass of a 256-thread workgroup: one live lane in the second pass (257), in the
+    # third (513), and the cap (1024: four full passes)
+    (0, 0, 257, 7, 1, 1, "rosenbrock"),
+    (1, 1, 513, 7, 1, 1, "ellipsoid"),
+    (2, 2, 1024, 7, 1, 1, "rosenbrock"),
+    (3, 1, 1024, 8, 1, 1, "ellipsoid"),
+    (-1, -1, 513, 7, 3, 0, "rosenbrock"),
 ]
 
 

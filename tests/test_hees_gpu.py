@@ -28,6 +28,9 @@ STREAM_RESTART, STREAM_HEES_NORMAL = 7, 18
 # the large shapes; n off the tiles with few rows (still in LDS unless forced) and, at (130, 140),
 # past the LDS form
 SHAPES = [(4, 0), (5, 12), (8, 16), (17, 0), (33, 7), (64, 150), (128, 0), (128, 256), (130, 9), (130, 140)]
+# rows past one pass of a 256-thread workgroup, mu small and explicit: one live lane in the second pass
+# (257), an odd n that is no multiple of 4 or 64 (301) and the cap (512); one population, six generations
+WIDE_SHAPES = [(257, 5), (301, 7), (512, 6)]
 
 
 def _bits(a, b, what):
@@ -58,6 +61,9 @@ def _cases():
         for P in (1, 5):
             for og in ((0, 1) if _lds_form_applies(n, mu) else (1,)):
                 out.append((n, np_, P, og))
+    for n, np_ in WIDE_SHAPES:
+        for og in ((0, 1) if _lds_form_applies(n, np_) else (1,)):
+            out.append((n, np_, 1, og))
     return out
 
 
@@ -84,7 +90,8 @@ def test_thirty_generations_against_the_device_form_of_the_model(hip, n, np_, P,
     mu = models[pops[0]].mu
     assert int(g.get_state("mu")[0]) == mu and int(g.get_state("B")[0]) == models[pops[0]].B
     worst = 0.
-    for gen in range(1, 31):
+    gens = 6 if n > 256 else 30
+    for gen in range(1, gens + 1):
         g.iterate()
         for p in pops:
             m = models[p]
@@ -100,8 +107,8 @@ def test_thirty_generations_against_the_device_form_of_the_model(hip, n, np_, P,
             assert int(g.get_state("it", p)[0]) == gen == m.it
             assert int(g.get_state("fev", p)[0]) == m.fev == 1 + gen * (2 * mu + 1)
             assert int(g.get_state("flag", p)[0]) == 0 and not m.converged_device()
-    print("n = %d, np = %d (mu = %d), P = %d, ortho in %s: worst relative deviation from the model over 30 "
-          "generations %.3e" % (n, np_, mu, P, "global memory" if og else "LDS", worst))
+    print("n = %d, np = %d (mu = %d), P = %d, ortho in %s: worst relative deviation from the model over %d "
+          "generations %.3e" % (n, np_, mu, P, "global memory" if og else "LDS", gens, worst))
 
 
 @pytest.mark.parametrize("n,np_", [(10, 5), (260, 3)])

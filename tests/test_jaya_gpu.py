@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import jaya_model as jm
+from slpso_model import device_objective
 from test_jaya_model import GOLD, band, _h
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,12 @@ CASES = [
     ("tent_map", 3, 7, 2, 1, 1, "sphere"),
     ("levy", 65, 70, 5, 3, 1, "rosenbrock"),
     ("levy", 3, 7, 2, 3, 3, "sphere"),
+    # rows past one pass of a 256-thread workgroup: one live lane in the second pass (257), in the
+    # third (513), and the cap (1024: four full passes)
+    ("original", 257, 7, 2, 3, 1, "rosenbrock"),
+    ("logistic", 513, 7, 1, 7, 1, "ellipsoid"),
+    ("tent_map", 1024, 8, 2, 3, 1, "rosenbrock"),
+    ("original", 1024, 7, 2, 3, 3, "ellipsoid"),
 ]
 
 
@@ -99,10 +106,16 @@ def test_three_generations_against_the_synchronous_model(hip, mut, n, np_, npmin
         assert int(g.get_state("fev", p)[0]) == np_ and int(g.get_state("nks", p)[0]) == m.nks
         assert ((g.get_state("X", p).reshape(np_, n) >= lo) & (g.get_state("X", p).reshape(np_, n) <= up)).all()
     errs = []
+    # past one pass of a row loop the trial's value is held too: the sum in the device's order
+    # (eval_row_group<64>, slpso_model.device_objective), bit for bit
+    fdev = device_objective(obj, n) if n > 256 else None
     for _ in range(3):
         g.iterate()
         for p, m in enumerate(models):
             _step_model(g, m, p, errs)
+            if fdev is not None:
+                T = g.get_state("trial", p).reshape(np_, n)
+                _bits(g.get_state("ftrial", p), [fdev(t) for t in T], "ftrial")
     if errs:
         print("levy: worst relative deviation of X from the model %.3e" % max(errs))
     if P > 1:       # the populations are independent streams

@@ -7,6 +7,7 @@ import pytest
 
 import mayfly_model as mm
 from slpso_model import device_objective
+from test_mayfly_golden_gpu import FTOL, XTOL, Worst, _ints
 
 pytestmark = pytest.mark.gpu
 
@@ -104,6 +105,72 @@ def test_a_python_callable_equals_the_builtin_bit_for_bit(hip, pgb, pmutnp):
                                b.get_state("off_x").reshape(np_, n), b.get_state("mut_x").reshape(nmut, n)])
         assert seen.tobytes() == want.tobytes(), "generation %d: the order of the calls" % k
     assert b.solution().n_evals == len(calls) == 2 * np_ + gens * (3 * np_ + nmut)
+
+
+# (n, np, objective, pgb): a shape of the other tests, then rows past one pass of a 256-thread workgroup:
+# one live lane in the second pass (257), an odd n that is no multiple of 4 or 64 (301) and the cap (512)
+WALK_SHAPES = [(33, 6, "rosenbrock", False), (257, 6, "rosenbrock", False), (301, 6, "ellipsoid", True),
+               (512, 8, "rosenbrock", True)]
+
+
+@pytest.mark.parametrize("n,np_,obj,pgb", WALK_SHAPES, ids=["n%d_np%d_%s_pgb%d" % s for s in WALK_SHAPES])
+def test_generations_under_the_devices_draws_are_the_model(hip, n, np_, obj, pgb):
+    """Four generations under the device's own generator.  Each is replayed by the model from the state the
+    device held before it, with the draws the device recorded and the objective summed in the device's
+    order, and compared by the rules of tests/test_mayfly_golden_gpu.py: every branch, rank, shuffle,
+    selection and counter equal; positions and velocities bit for bit, except the descendants of an exp()
+    form, which are held to XTOL of the box width; values to FTOL.  Two flies the mutation touches
+    (pmutnp = 0.3), a tenth of their coordinates each."""
+    f = device_objective(obj, n)
+    lo, up = [-5.] * n, [5.] * n
+    width = 10. * np.ones(n)
+    par = dict(pgb=pgb, pmutnp=0.3, pmutdim=0.1)
+    g = _start(hip, n, np_, obj=obj, seed=100 + n, record_draws=True, **par)
+    worst = Worst()
+    for k in range(4):
+        tag = "n %d generation %d " % (n, k)
+        before = {key: g.get_state(key).copy() for key in STATE}
+        g.iterate()
+        d = mm.Mayfly(f, n, np_, lo, up, 10 ** 6, **par)
+        d.stable_sort = True
+        d.start(before)
+        assert d.nmut == 2 == int(g.get_state("nmut")[0])
+        table = g.get_state("draws")
+        assert table.size == g.table_len()
+        d.iterate(mm.TableSource(table, n, np_, d.nmut, d.nmd))
+        # (no guard against close values, as the golden test needs one: the model's sums are the device's
+        # own, so two close values are the same two values on both sides and rank the same way)
+        assert _ints(g, "branch_f") == d.branch_f and _ints(g, "branch_m") == d.branch_m, tag + "branches"
+        for sex, flies in (("females", d.moved_females), ("males", d.moved_males)):
+            taint = [y.taint for y in flies]
+            worst.rows(g.get_state("moved_%s_x" % sex), [y.x for y in flies], taint, width, tag + sex + " x")
+            worst.rows(g.get_state("moved_%s_v" % sex), [y.v for y in flies], taint, width, tag + sex + " v")
+            worst.vals(g.get_state("moved_%s_f" % sex), [y.f for y in flies], tag + sex + " f")
+        assert _ints(g, "rank_m") == d.rank_m and _ints(g, "rank_f") == d.rank_f, tag + "ranks"
+        worst.rows(g.get_state("off_x"), [y.x for y in d.offspring], [y.taint for y in d.offspring], width, tag + "off x")
+        worst.vals(g.get_state("off_f"), [y.f for y in d.offspring], tag + "off f")
+        assert _ints(g, "perm_o") == d.perm_o and _ints(g, "perm_u") == d.perm_u, tag + "shuffles"
+        worst.rows(g.get_state("mut_x"), [y.x for y in d.mutated], [y.taint for y in d.mutated], width, tag + "mut x")
+        worst.vals(g.get_state("mut_f"), [y.f for y in d.mutated], tag + "mut f")
+        got = [int(g.get_state(key)[0]) for key in ("took", "fev", "nmut", "it", "flag")]
+        assert got == [d.took, d.fev, d.nmut, d.it, 0], (tag, got)
+        worst.vals(g.get_state("fbest"), [d.fbest], tag + "fbest")
+        worst.rows(g.get_state("xbest"), [d.best], [d.best_taint], width, tag + "xbest")
+        assert g.get_state("g")[0] == d.g and g.get_state("dance")[0] == d.dance_now and g.get_state("fl")[0] == d.fl_now
+        assert _ints(g, "sel_m") == d.sel_m and _ints(g, "sel_f") == d.sel_f, tag + "selection ranks"
+        assert _ints(g, "src_m") == d.src_m and _ints(g, "src_f") == d.src_f, tag + "selection sources"
+        tm, tf = [y.taint for y in d.males], [y.taint for y in d.females]
+        worst.rows(g.get_state("males_x"), [y.x for y in d.males], tm, width, tag + "males_x")
+        worst.rows(g.get_state("males_v"), [y.v for y in d.males], tm, width, tag + "males_v")
+        worst.rows(g.get_state("males_bx"), [y.bx for y in d.males], tm, width, tag + "males_bx")
+        worst.rows(g.get_state("females_x"), [y.x for y in d.females], tf, width, tag + "females_x")
+        worst.rows(g.get_state("females_v"), [y.v for y in d.females], tf, width, tag + "females_v")
+        worst.vals(g.get_state("males_f"), [y.f for y in d.males], tag + "males_f")
+        worst.vals(g.get_state("males_bf"), [y.bf for y in d.males], tag + "males_bf")
+        worst.vals(g.get_state("females_f"), [y.f for y in d.females], tag + "females_f")
+        print(tag + "worst exp() descendant %.3e of the box width (%s), worst value %.3e relative"
+              % (worst.x, worst.at, worst.f))
+        assert worst.x <= XTOL and worst.f <= FTOL, (tag, worst.x, worst.at, worst.f)
 
 
 def test_the_budget_passes_by_less_than_a_generation_and_nothing_converges(hip):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import nshs_model as nm
+from slpso_model import device_objective
 from test_hees_model import band
 from test_nshs_model import FSTD_BOUND, GOLD, _h
 
@@ -82,16 +83,27 @@ def _table(rng, n, every=3):
     return u
 
 
-@pytest.mark.parametrize("hms", [1, 2, 3, 64, 65, 130])
-@pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, 128, 130])
+# rows past one pass of a 256-thread workgroup: one live lane in the second pass (257), an odd n that
+# is no multiple of 4 or 64 (301) and the cap, with the objective whose sum the walk then checks
+WIDE_SHAPES = {(257, 5): "rosenbrock", (301, 6): "ellipsoid", (512, 8): "rosenbrock"}
+CANDIDATE_SHAPES = [(n, hms) for hms in (1, 2, 3, 64, 65, 130) for n in (1, 2, 3, 63, 64, 65, 128, 130)]
+
+
+@pytest.mark.parametrize("n,hms", CANDIDATE_SHAPES + sorted(WIDE_SHAPES))
 def test_the_candidate_is_the_model_bit_for_bit(hip, n, hms):
     """wide (box 5, fstdmin 1e-4) and narrow (box 0.05, fstdmin 0.05: the sphere's values spread by
     less); hms = 1 is narrow whatever fstdmin is, and its column minimum is its maximum.  The first
     iteration takes the device's draws, the second a table whose coin fails at every third
-    coordinate, so that the fresh value of either branch is drawn at any n; the third runs fused."""
+    coordinate, so that the fresh value of either branch is drawn at any n; the third runs fused.
+    Past n = 256 the box of 5 takes rosenbrock or the ellipsoid, the walk goes on for 12 iterations
+    under the device's draws (phase by phase and fused in turn), and every candidate's value is the
+    model's sum in the device's order (slpso_model.device_objective: eval_row_group<64>)."""
     rng = np.random.default_rng(1000 * n + hms)
     for box, fstdmin in ((5., 1e-4), (0.05, 0.05)):
-        g = _start(hip, n, hms, obj="sphere", seed=100 * n + hms, fstdmin=fstdmin, box=box, record_draws=True)
+        obj = WIDE_SHAPES[n, hms] if (n, hms) in WIDE_SHAPES and box == 5. else "sphere"
+        g = _start(hip, n, hms, obj=obj, seed=100 * n + hms, fstdmin=fstdmin, box=box, record_draws=True)
+        # a lane per coordinate up to 256: the walk runs the configuration its n is meant to reach
+        assert int(g.get_state("wg")[0]) == (64 if n <= 128 else 128 if n <= 256 else 256)
         m = _model_of(g, n, hms, box, 10 ** 6, fstdmin)
         tag = "n %d hms %d box %g " % (n, hms, box)
         _device_is_model(g, m, tag + "init ")
@@ -112,6 +124,23 @@ def test_the_candidate_is_the_model_bit_for_bit(hip, n, hms):
         m.evaluate(g.get_state("fcand")[0])
         m.replace()
         _device_is_model(g, m, tag + "fused ")
+        if n <= 256:
+            continue
+        fobj = device_objective(obj, n)
+        _bits(g.get_state("f"), [fobj(row) for row in m.x], tag + "the memory's values")
+        g.inject_uniforms(None)
+        for it in range(12):
+            wtag = tag + "iteration %d " % (3 + it)
+            if it % 2:
+                _phases_against_model(g, m, wtag)
+            else:
+                assert g.run(1) == 1
+                m.generate(g.get_state("draws").reshape(n, 4))
+                _bits(g.get_state("cand"), m.cand, wtag + "fused cand")
+                m.evaluate(g.get_state("fcand")[0])
+                m.replace()
+                _device_is_model(g, m, wtag + "fused ")
+            _bits(g.get_state("fcand"), [fobj(m.cand)], wtag + "fcand")
 
 
 @pytest.mark.parametrize("hms", [5, 65, 130])

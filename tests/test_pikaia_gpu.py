@@ -112,6 +112,56 @@ def test_a_python_callable_equals_the_builtin_bit_for_bit(hip, ielite, repair):
     assert b.solution().n_evals == want and len(calls) == np_ + gens * per
 
 
+# (n, np, objective, options): a shape of the other tests, then rows past one pass of a 256-thread
+# workgroup: one live lane in the second pass (257), an odd n that is no multiple of 4 or 64 (301), the cap
+WALK_SHAPES = [(17, 6, "rosenbrock", dict(imut=5, ielite=1)),
+               (257, 6, "rosenbrock", dict(imut=5, ielite=1)),
+               (301, 6, "ellipsoid", dict(imut=6, ielite=1, repair=True)),
+               (512, 8, "rosenbrock", dict(imut=2, ielite=0)),
+               (512, 6, "ellipsoid", dict(imut=5, ielite=1))]
+
+
+@pytest.mark.parametrize("n,np_,obj,kw", WALK_SHAPES,
+                         ids=["n%d_np%d_%s_imut%d" % (s[0], s[1], s[2], s[3]["imut"]) for s in WALK_SHAPES])
+def test_generations_under_the_devices_draws_are_the_model(hip, n, np_, obj, kw):
+    """Five generations under the device's own generator.  Each is replayed by the model (in the stable order,
+    the objective summed in the device's order) from the state the device held before it, with the draws the
+    device recorded: parents, crossover windows, kinds of mutation, phenotypes, points, values, the elite
+    decision, the rank order, pmut and the counters are the device's, the floats bit for bit.  A generation
+    with a decision too close to call (pikaia_model.Pikaia.ok) asks for another seed."""
+    nd = 6
+    g = _start(hip, n, np_, nd, obj=obj, seed=200 + n, record_draws=True, **kw)
+    assert g.table_len() == pm.table_layout(n, np_, nd)["len"]
+    d = pm.Pikaia(device_objective(obj, n), n, np_, 10 ** 5, nd, [LO] * n, [UP] * n, order="stable", **kw)
+    for k in range(5):
+        tag = "n %d generation %d " % (n, k)
+        before = {key: g.get_state(key).copy() for key in ("ph", "fitns", "order", "pmut", "ig", "fev")}
+        g.iterate()
+        d.start(before["ph"].reshape(np_, n), before["fitns"], before["order"], before["pmut"][0], before["ig"][0],
+                before["fev"][0])
+        d.iterate(pm.TableSource(g.get_state("draws")))
+        # (close values are no obstacle here: the model's sums are the device's own; only rdif, which goes
+        # through pow and sqrt, may fall on the other side of a threshold)
+        assert not d.rdif_close, tag + "rdif too close to a threshold: choose another seed"
+        ints = lambda key: [int(v) for v in g.get_state(key)]
+        assert ints("parents") == [v for pr in d.parents for v in pr], tag + "parents"
+        assert ints("cross") == [v for cr in d.cross for v in cr], tag + "crossover windows"
+        assert ints("mode") == d.mode, tag + "kinds of mutation"
+        ph = np.asarray(d.ph, float)
+        assert g.get_state("new_ph").tobytes() == ph.tobytes(), tag + "new phenotypes"
+        assert g.get_state("ph").tobytes() == ph.tobytes(), tag + "the population"
+        x = np.asarray([d.map(r) for r in d.ph], float)
+        assert g.get_state("new_x").tobytes() == x.tobytes() and g.get_state("x").tobytes() == x.tobytes(), tag + "points"
+        assert int(g.get_state("elite")[0]) == d.elite, tag + "elite"
+        fit = np.asarray(d.fitns, float)
+        assert g.get_state("fitns").tobytes() == fit.tobytes(), (tag + "values", g.get_state("fitns"), fit)
+        assert ints("order") == d.order, tag + "rank order"
+        assert g.get_state("pmut")[0] == d.pmut, tag + "pmut"
+        got = [int(g.get_state(key)[0]) for key in ("fev", "ig", "flag")]
+        assert got == [d.fev, d.ig, 0], (tag, got)
+    print("n %d np %d %s: paths %s" % (n, np_, obj, {p: c for p, c in d.paths.items() if c}))
+
+
 def test_recorded_draws_injected_again_reproduce_the_run(hip):
     n, np_, nd = 5, 12, 6
     kw = dict(imut=5, ielite=1, pmut=0.05)

@@ -32,6 +32,10 @@ def _close(a, b, rtol, what):
     (513, 40, "sphere", True),
     (1024, 24, "rastrigin", True),
     (2048, 20, "sphere", False),
+    # wide rows AND the best refreshed between chunks (48, 48, 34 particles): every wavefront of
+    # pso_gbest copies a slice of xbest (ld > 64; at 513 a lane copies in three passes)
+    (300, 130, "rosenbrock", True),
+    (513, 130, "ellipsoid", True),
 ])
 def test_generations_match_sync_oracle(hip, oracle_lib, n, np_, obj, correct):
     lo, up = -5. * np.ones(n), 5. * np.ones(n)
@@ -44,6 +48,8 @@ def test_generations_match_sync_oracle(hip, oracle_lib, n, np_, obj, correct):
     # (the swarm moves in chunks with the best refreshed in between: the oracle is told the chunk)
     chunk = int(g.get_state("chunk")[0])
     assert chunk == np_ if np_ <= 64 else (chunk % 16 == 0 and np_ / 16 <= chunk < np_)
+    if n >= 300 and np_ == 130:
+        assert -(-np_ // chunk) >= 3        # the best is refreshed at least twice inside a generation
     o.set_chunk(chunk)
     np.testing.assert_array_equal(g.get_state("x"), o.get("x"))   # same Philox words
     _close(g.get_state("f"), o.get("f"), 1e-12, "init f")
@@ -119,6 +125,29 @@ def test_chunk_of_the_whole_swarm_is_the_synchronous_form(hip, oracle_lib):
         _close(g.get_state("xbest"), o.get("xbest"), 1e-11, "gen %d gbest" % gen)
 
 
+def test_a_chunk_that_is_no_count_is_refused(hip):
+    """NaN, a negative and an infinite chunk are BBO_ERR_ARG and leave the chunk as it was; 0 and
+    anything from np up, 1e300 included, mean the whole swarm; a count below np is taken as given"""
+    from bboptpy_amd import _ffi
+    n, np_ = 4, 200
+    g = hip.APSO(mfev=10 ** 7, tol=1e-12, np=np_, seed=1)
+    g.initialize(hip.objectives.sphere, -np.ones(n), np.ones(n), np.zeros(n))
+    chunk = int(g.get_state("chunk")[0])
+    assert 0 < chunk < np_
+    for bad in (float("nan"), -1., -1e300, float("inf"), -float("inf")):
+        with pytest.raises(_ffi.BboError) as ei:
+            g.set_state("chunk", [bad])
+        assert ei.value.status == _ffi.ERR_ARG, bad
+        assert int(g.get_state("chunk")[0]) == chunk
+    for whole in (1e300, float(np_), np_ + 1., 2. ** 31, 0.):
+        g.set_state("chunk", [32.])
+        assert int(g.get_state("chunk")[0]) == 32
+        g.set_state("chunk", [whole])
+        assert int(g.get_state("chunk")[0]) == np_, whole
+    g.iterate()
+    assert int(g.get_state("it")[0]) == 1 and int(g.get_state("fev")[0]) >= 2 * np_
+
+
 @pytest.mark.parametrize("np_", [30, 64, 65, 200, 1024, 5000, 40000])
 def test_bench_prices_a_launch_with_the_engines_chunk(hip, np_):
     """bench.py prices ONE pso_update launch with the chunk of particles it moves: its rule and
@@ -132,20 +161,25 @@ def test_bench_prices_a_launch_with_the_engines_chunk(hip, np_):
 
 def test_python_objective_sees_the_same_chunks(hip):
     """a Python callable and the built-in objective of the same function: the same swarm after
-    every generation (the host path evaluates chunk by chunk, the best refreshed in between)"""
-    n, np_, seed = 6, 150, 3
-    lo, up = -5. * np.ones(n), 5. * np.ones(n)
-    a = hip.APSO(mfev=10 ** 7, tol=1e-12, np=np_, seed=seed)
-    b = hip.APSO(mfev=10 ** 7, tol=1e-12, np=np_, seed=seed)
-    a.initialize(hip.objectives.sphere, lo, up, np.zeros(n))
-    b.initialize(lambda x: float(np.sum(np.asarray(x) ** 2)), lo, up, np.zeros(n))
-    assert int(a.get_state("chunk")[0]) == int(b.get_state("chunk")[0]) == 64   # three chunks: 64, 64, 22
-    for gen in range(8):
-        a.iterate()
-        b.iterate()
-        _close(a.get_state("x"), b.get_state("x"), 1e-12, "gen %d x" % gen)
-        _close(a.get_state("xbest"), b.get_state("xbest"), 1e-12, "gen %d gbest" % gen)
-        assert int(a.get_state("fev")[0]) == int(b.get_state("fev")[0])
+    every generation (the host path evaluates chunk by chunk, the best refreshed in between).  The
+    second shape has rows of more than 256 doubles: pso_pbest and pso_gbest on the host path copy a
+    row in more than one pass, every wavefront of pso_gbest a slice of it"""
+    # three chunks each: 64, 64, 22 and 48, 48, 34
+    for n, np_, seed, chunk in ((6, 150, 3, 64), (257, 130, 3, 48)):
+        lo, up = -5. * np.ones(n), 5. * np.ones(n)
+        a = hip.APSO(mfev=10 ** 7, tol=1e-12, np=np_, seed=seed)
+        b = hip.APSO(mfev=10 ** 7, tol=1e-12, np=np_, seed=seed)
+        a.initialize(hip.objectives.sphere, lo, up, np.zeros(n))
+        b.initialize(lambda x: float(np.sum(np.asarray(x) ** 2)), lo, up, np.zeros(n))
+        assert int(a.get_state("chunk")[0]) == int(b.get_state("chunk")[0]) == chunk
+        for gen in range(8):
+            a.iterate()
+            b.iterate()
+            tag = "n %d gen %d " % (n, gen)
+            _close(a.get_state("x"), b.get_state("x"), 1e-12, tag + "x")
+            _close(a.get_state("xb"), b.get_state("xb"), 1e-12, tag + "pbest")
+            _close(a.get_state("xbest"), b.get_state("xbest"), 1e-12, tag + "gbest")
+            assert int(a.get_state("fev")[0]) == int(b.get_state("fev")[0])
 
 
 def test_apso_solves_sphere(hip):

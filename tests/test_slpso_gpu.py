@@ -37,7 +37,14 @@ def model_beside(g, obj, n, np_, mfev, stol, w, population=0, **kw):
 # (a) ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,np_,obj,ufmax", [(2, 2, "rosenbrock", 10.), (5, 3, "rosenbrock", 10.),
                                              (33, 6, "rosenbrock", 10.), (65, 4, "rosenbrock", 10.),
-                                             (130, 5, "rosenbrock", 10.), (12, 8, "ellipsoid", 1.)])
+                                             (130, 5, "rosenbrock", 10.), (12, 8, "ellipsoid", 1.),
+                                             # rows past one pass of the 256-thread workgroup: one live lane in
+                                             # the second pass, an odd n off every tile, and the cap (rosenbrock
+                                             # throughout: on the ellipsoid past n = 256 a step of Algorithm 2
+                                             # along a light coordinate moves the value by 1e-12 of it, under the
+                                             # gap asserted below, whatever the seed or np)
+                                             (257, 5, "rosenbrock", 10.), (301, 6, "rosenbrock", 1.),
+                                             (512, 5, "rosenbrock", 10.)])
 def test_device_generator_against_the_model_fed_its_recorded_draws(hip, n, np_, obj, ufmax):
     """10 generations with mfev = 40 np under the device's generator; the recorded draws of every
     generation drive the model: the states agree as in tests/test_slpso_golden_gpu.py.  The seed is one

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import spiral_model as sm
+from slpso_model import device_objective
 from test_hees_model import band
 from test_spiral_model import GOLD, _h
 
@@ -57,13 +58,25 @@ def _rotation_is_the_model(g, n, np_, p=0, gens=2):
         g.phase(3)
 
 
-@pytest.mark.parametrize("np_", [1, 20, 63, 64, 65, 130])
-@pytest.mark.parametrize("n", [1, 2, 3, K, K + 1, 2 * K + 1, 33, 128])
+# rows wider than one pass of a 256-thread workgroup: one live lane in the second pass (257), an
+# odd n that is no multiple of 4 or 64 (301) and the cap (512), where most of the tile is in global memory
+WIDE_SHAPES = [(257, 5), (301, 6), (512, 8)]
+ROTATION_SHAPES = [(n, np_) for np_ in (1, 20, 63, 64, 65, 130) for n in (1, 2, 3, K, K + 1, 2 * K + 1, 33, 128)]
+
+
+@pytest.mark.parametrize("n,np_", ROTATION_SHAPES + WIDE_SHAPES)
 def test_the_rotation_is_the_device_form_of_the_model_bit_for_bit(hip, n, np_):
-    g = _start(hip, n, np_, seed=100 * n + np_, taur=1., tautheta=1.)      # every point its own r and angle
+    wide = n > 256
+    g = _start(hip, n, np_, obj="ellipsoid" if n == 301 else "rosenbrock", seed=100 * n + np_, taur=1.,
+               tautheta=1.)                                                 # every point its own r and angle
     assert int(g.get_state("rot_k")[0]) == K
     assert int(g.get_state("rot_split")[0]) == max(n - int(g.get_state("rot_lds_coords")[0]), 0)
-    _rotation_is_the_model(g, n, np_)
+    if n == 512:
+        assert int(g.get_state("rot_split")[0]) > 0        # the model against the tile in global memory
+    _rotation_is_the_model(g, n, np_, gens=4 if wide else 2)
+    if wide:        # the values of the rotated rows: the sum in the device's order (eval_row_group<64>), bit for bit
+        fobj = device_objective("ellipsoid" if n == 301 else "rosenbrock", n)
+        _bits(g.get_state("f"), [fobj(row) for row in g.get_state("x").reshape(np_, n)], "values")
     assert len(set(g.get_state("theta").tolist())) == np_
 
 

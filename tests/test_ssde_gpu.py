@@ -28,6 +28,12 @@ SHAPES = [
     (66, 8, "rosenbrock", 640, {}),
     (130, 6, "rosenbrock", 120, {}),
     (130, 6, "ellipsoid", 120, {"usede": True}),
+    # rows past one pass of the 256-thread workgroup: one live lane in the second pass (257), an odd n
+    # that is no multiple of 4 or 64 (301) and the cap (512), with and without the DE step
+    (257, 6, "rosenbrock", 120, {}),
+    (301, 6, "ellipsoid", 120, {"usede": True}),
+    (512, 6, "rosenbrock", 120, {}),
+    (512, 6, "ellipsoid", 120, {"usede": True}),
 ]
 BAND_RUNS, BAND_MAY_MISS = 32, 2     # tests/test_ssde_model.py holds the reference's own other seeds to this
 
