@@ -76,6 +76,7 @@ struct De {
     std::vector<double> lower, upper, aux;
     /* state */
     int np = 0, fev = 0, k = 1, gen = 0;
+    long repairs_lo = 0, repairs_up = 0;   /* coordinates repair() moved, per side (read-only) */
     double mucr = 0.5, muf = 0.5;
     std::vector<double> MCR, MF, work, SCR, SF, W;
     std::vector<std::vector<double>> arch;
@@ -99,6 +100,7 @@ struct De {
         bbo_objective_aux(obj, n, aux.data());
         fev = 0;
         gen = 0;
+        repairs_lo = repairs_up = 0;
         MCR.assign(h, 0.5);
         MF.assign(h, 0.5);
         mucr = muf = 0.5;
@@ -162,8 +164,13 @@ struct De {
     void repair(const double *parent)
     {
         for (int j = 0; j < n; j++) {
-            if (work[j] < lower[j]) work[j] = (lower[j] + parent[j]) / 2.;
-            else if (work[j] > upper[j]) work[j] = (upper[j] + parent[j]) / 2.;
+            if (work[j] < lower[j]) {
+                work[j] = (lower[j] + parent[j]) / 2.;
+                repairs_lo++;
+            } else if (work[j] > upper[j]) {
+                work[j] = (upper[j] + parent[j]) / 2.;
+                repairs_up++;
+            }
         }
     }
 
@@ -528,6 +535,8 @@ struct De {
         if (key == "np") return put1(np);
         if (key == "fev") return put1(fev);
         if (key == "larch") return put1((double) arch.size());
+        if (key == "repairs_lo") return put1((double) repairs_lo);
+        if (key == "repairs_up") return put1((double) repairs_up);
         if (key == "mucr") return put1(mucr);
         if (key == "muf") return put1(muf);
         return -1;
@@ -553,6 +562,7 @@ struct Sansde {
     std::vector<double> lower, upper, aux, work;
     /* state */
     int fev = 0, it = 0;
+    long repairs_lo = 0, repairs_up = 0;   /* coordinates repair() moved, per side (read-only) */
     double p = 0.5, fp = 0.5, crrec = 0., crdeltaf = 0., crm = 0.5;
     int pns[2] = { 0, 0 }, pnf[2] = { 0, 0 };
     double fpns[2] = { 0., 0. }, fpnf[2] = { 0., 0. };
@@ -581,6 +591,7 @@ struct Sansde {
         aux.assign(n, 0.);
         bbo_objective_aux(obj, n, aux.data());
         fev = it = 0;
+        repairs_lo = repairs_up = 0;
         p = fp = 0.5;
         crrec = crdeltaf = 0.;
         crm = 0.5;
@@ -612,8 +623,13 @@ struct Sansde {
     void repair(const double *parent)
     {
         for (int j = 0; j < n; j++) {
-            if (work[j] < lower[j]) work[j] = (lower[j] + parent[j]) / 2.;
-            else if (work[j] > upper[j]) work[j] = (upper[j] + parent[j]) / 2.;
+            if (work[j] < lower[j]) {
+                work[j] = (lower[j] + parent[j]) / 2.;
+                repairs_lo++;
+            } else if (work[j] > upper[j]) {
+                work[j] = (upper[j] + parent[j]) / 2.;
+                repairs_up++;
+            }
         }
     }
 
@@ -854,6 +870,8 @@ struct Sansde {
         if (key == "crm") return put1(crm);
         if (key == "crrec") return put1(crrec);
         if (key == "crdeltaf") return put1(crdeltaf);
+        if (key == "repairs_lo") return put1((double) repairs_lo);
+        if (key == "repairs_up") return put1((double) repairs_up);
         if (key == "pns" || key == "pnf") {
             const int *a = key == "pns" ? pns : pnf;
             if (cap >= 2) { out[0] = a[0]; out[1] = a[1]; }

@@ -303,6 +303,11 @@ class Handle:
         a generation -- what the device's `chunk` state key reports (0: the whole swarm)"""
         self.lib.f("apso_set_chunk")(self.ptr, int(chunk))
 
+    def repairs(self):
+        """SHADE / JADE / SaNSDE (oracle only, read-only): coordinates the midpoint repair moved
+        since init(), as (below the lower bound, above the upper bound)"""
+        return int(self.scalar("repairs_lo")), int(self.scalar("repairs_up"))
+
     def rset(self, key, value):
         """restart drivers (oracle only): overwrite one bookkeeping field"""
         if self.lib.f("restart_set")(self.ptr, key.encode(), float(value)) < 0:

@@ -64,6 +64,9 @@ SHAPES = [
     ("n33_np40_pgb", 33, 40, "rosenbrock", 5., 66, 20, {"pgb": True}),
     ("n65_np66", 65, 66, "rosenbrock", 5., 77, 20, {"pmutdim": 0.1}),
 ]
+# one short record under the per-coordinate box of tests/_boxes.py (the harness is handed its bounds, box_arg): vmax, the
+# mutation's sigma and the clamps with bounds that differ in every coordinate
+PERCOORD = ("percoord_n11_np6", 11, 6, "sphere", "percoord", 88, 5, {"pmutnp": 0.3})
 MFEV = 1000000
 SEEDS_TRIED = 40
 MIN_OK, GOOD_OK = 4, 12     # of a shape's recorded generations, those the device can be held to: at least, enough
@@ -137,6 +140,24 @@ static void words_between(std::mt19937 before, const std::mt19937 &after)
     printf("],");
 }
 
+// "l0,l1,...|u0,u1,...": bounds given coordinate by coordinate (box_arg() below writes them from
+// tests/_boxes.py); false, and nothing touched, where `s` is a plain number
+static bool bounds_arg(const char *s, std::vector<double> &lo, std::vector<double> &up)
+{
+    if (!strchr(s, '|')) return false;
+    std::vector<double> *v = &lo;
+    size_t i = 0;
+    for (const char *p = s; *p;) {
+        if (*p == '|') { v = &up; i = 0; p++; continue; }
+        if (*p == ',') { p++; continue; }
+        char *e;
+        const double x = strtod(p, &e);
+        if (i < v->size()) (*v)[i++] = x;
+        p = e;
+    }
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     // steps <obj> <n> <np> <box> <seed> <generations> <mfev> <pmutnp> <pmutdim> <pgb> <lower>
@@ -157,6 +178,7 @@ int main(int argc, char **argv)
     if (!strcmp(argv[1], "steps")) {
         const double box = atof(argv[5]);
         std::vector<double> lo(n, atof(argv[12])), up(n, box), guess(n, 0.);
+        bounds_arg(argv[5], lo, up);
         multivariate_problem prob { f, n, lo.data(), up.data() };
         Random::seed((unsigned) atoi(argv[6]));
         Probe p(np, atoi(argv[8]), 1., 1.5, 1.5, 2., 5., 0.8, 1., 0.99, 0.8, 0.8, 0.1, 0.1, atof(argv[10]),
@@ -264,14 +286,33 @@ def params_of(shape):
 
 
 def lower_of(shape):
+    if shape[4] == "percoord":
+        return "percoord"
     return shape[7].get("lower", -shape[4])
+
+
+def bounds_of(shape):
+    n, box = shape[1], shape[4]
+    if box == "percoord":
+        from _boxes import percoord_box
+        return [list(v) for v in percoord_box(n)]
+    return [lower_of(shape)] * n, [box] * n
+
+
+def box_arg(box, n):
+    """the harness's box argument: a number, or for "percoord" the bounds of tests/_boxes.py, "l0,..|u0,.." """
+    if box != "percoord":
+        return repr(box)
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    return ",".join(repr(float(v)) for v in lo) + "|" + ",".join(repr(float(v)) for v in up)
 
 
 def run_shape(exe, shape, seed):
     name, n, np_, obj, box, _, gens, _ = shape
     par = params_of(shape)
     out = subprocess.check_output(
-        [exe, "steps", str(OBJ_IDS[obj]), str(n), str(np_), repr(box), str(seed), str(gens), str(MFEV),
+        [exe, "steps", str(OBJ_IDS[obj]), str(n), str(np_), box_arg(box, n), str(seed), str(gens), str(MFEV),
          repr(par["pmutnp"]), repr(par["pmutdim"]), str(int(par["pgb"])), repr(lower_of(shape))])
     return _norm(json.loads(out))
 
@@ -290,7 +331,8 @@ def replay(rec, shape, seed):
         words += st["words"]
     assert mm.mt19937_words(seed, len(words)) == words, "std::mt19937(seed) is not what numpy regenerates"
     w = jaya_model.Words(words)
-    m = mm.Mayfly(chol_model.objective(obj, n), n, np_, [lower_of(shape)] * n, [box] * n, MFEV, **par)
+    lo, up = bounds_of(shape)
+    m = mm.Mayfly(chol_model.objective(obj, n), n, np_, lo, up, MFEV, **par)
     src = mm.WordsSource(w, n)
 
     def same(st, tag):
@@ -305,7 +347,8 @@ def replay(rec, shape, seed):
     m.init_words(w)
     assert w.i == counts[0]
     same(rec["init"], name + " init ")
-    out = {"name": name, "n": n, "np": np_, "objective": obj, "box": box, "lower": lower_of(shape), "mfev": MFEV,
+    out = {"name": name, "n": n, "np": np_, "objective": obj, "box": box,
+           "lower": lower_of(shape), "mfev": MFEV,
            "seed": seed, "params": {k: v for k, v in shape[7].items() if k != "lower"}, "nwords": counts, "nmut": m.nmut,
            "init": {"values_crc": crc(fx for _, fx in m.evals), "points_crc": crc(v for x, _ in m.evals for v in x),
                     "state_crc": state_crc(m.state()), "fbest": m.fbest.hex()},
@@ -336,21 +379,32 @@ def replay(rec, shape, seed):
     return out
 
 
-def record(exe, shape):
-    """the first seed with at least MIN_OK generations the device can be held to"""
+def record(exe, shape, need=(), good_ok=GOOD_OK):
+    """the first seed with at least MIN_OK generations the device can be held to (and every path of `need`)"""
     name, seed0 = shape[0], shape[5]
     best = None
     for attempt in range(SEEDS_TRIED):
         seed = seed0 + 1000 * attempt
         out = replay(run_shape(exe, shape, seed), shape, seed)
         good = sum(st["ok"] for st in out["states"])
+        if any(out["paths"][k] < 1 for k in need):
+            continue
         if best is None or good > best[0]:
             best = (good, out)
-        if good >= GOOD_OK:
+        if good >= good_ok:
             break
-    if best[0] < MIN_OK:
-        sys.exit("%s: no seed with %d comparable generations (the best has %d)" % (name, MIN_OK, best[0]))
+    if best is None or best[0] < MIN_OK:
+        sys.exit("%s: no seed with %d comparable generations" % (name, MIN_OK))
     return best[1]
+
+
+def generate_percoord(ref="/root/reference"):
+    """tests/golden/mayfly_percoord.json: PERCOORD alone, with both clamps in it"""
+    tmp = tempfile.mkdtemp(prefix="mayfly_golden_")
+    try:
+        return {"steps": [record(build(ref, tmp), PERCOORD, need=("clamp_box", "clamp_vmax"), good_ok=PERCOORD[6])]}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def signature(ref):
@@ -435,19 +489,24 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "mayfly_runs.json"))
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--percoord", action="store_true",
+                    help="write the per-coordinate record alone, to tests/golden/mayfly_percoord.json")
     a = ap.parse_args()
     if not os.path.isdir(os.path.join(a.ref, "src")):
         sys.exit("the reference sources are not at %s" % a.ref)
     if a.time:
         time_reference(a.ref)
         return
-    data = generate(a.ref)
+    if a.percoord and a.out.endswith("mayfly_runs.json"):
+        a.out = os.path.join(ROOT, "tests", "golden", "mayfly_percoord.json")
+    data = generate_percoord(a.ref) if a.percoord else generate(a.ref)
     text = dumps(data)
     with open(a.out, "w") as fh:
         fh.write(text)
     for rec in data["steps"]:
         print("%s: seed %d, paths %s" % (rec["name"], rec["seed"], rec["paths"]))
-    print("paths over all shapes: %s" % data["paths"])
+    if "paths" in data:
+        print("paths over all shapes: %s" % data["paths"])
     print("wrote %s (%d bytes)" % (a.out, len(text)))
 
 

@@ -37,6 +37,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 # (name, n, hms, objective, box, fstdmin, seed)
 SHAPES = [
@@ -52,6 +53,10 @@ SHAPES = [
     ("narrow_n9_h20", 9, 20, "sphere", 0.25, 0.25, 111),
 ]
 ITERATIONS = 12
+# one short record under the per-coordinate box of tests/_boxes.py (the harness is handed its bounds, box_arg):
+# the fresh value, the bandwidth (up[i] - lo[i]) / tunerange and the clamp with bounds that differ in every coordinate
+PERCOORD = ("percoord_n11_h6", 11, 6, "sphere", "percoord", 1e-4, 123)
+PERCOORD_ITERATIONS = 5
 MFEV = 1000000
 MIN_GAP = 1e-6
 OBJ_IDS = {"sphere": 0, "rosenbrock": 1, "rastrigin": 2, "ellipsoid": 3, "ackley": 4,
@@ -106,6 +111,24 @@ struct Probe: public NSHS {
 
 struct Ctx { int obj, n; std::vector<double> aux; };
 
+// "l0,l1,...|u0,u1,...": bounds given coordinate by coordinate (box_arg() below writes them from
+// tests/_boxes.py); false, and nothing touched, where `s` is a plain number
+static bool bounds_arg(const char *s, std::vector<double> &lo, std::vector<double> &up)
+{
+    if (!strchr(s, '|')) return false;
+    std::vector<double> *v = &lo;
+    size_t i = 0;
+    for (const char *p = s; *p;) {
+        if (*p == '|') { v = &up; i = 0; p++; continue; }
+        if (*p == ',') { p++; continue; }
+        char *e;
+        const double x = strtod(p, &e);
+        if (i < v->size()) (*v)[i++] = x;
+        p = e;
+    }
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     // steps <obj> <n> <hms> <box> <seed> <iterations> <fstdmin> <mfev>
@@ -119,6 +142,7 @@ int main(int argc, char **argv)
     if (!strcmp(argv[1], "steps")) {
         const double box = atof(argv[5]);
         std::vector<double> lo(n, -box), up(n, box), guess(n, 0.);
+        bounds_arg(argv[5], lo, up);
         multivariate_problem prob { f, n, lo.data(), up.data() };
         Random::seed((unsigned) atoi(argv[6]));
         Probe p(atoi(argv[9]), atoi(argv[4]), atof(argv[8]));
@@ -232,13 +256,23 @@ def compress(rec, n):
         x, f = nx, nf
 
 
-def record(exe, name, n, hms, obj, box, fstdmin, seed):
-    """one shape; the seed moves on until the branch holds and no decision is close"""
-    wide = name.startswith("wide")
+def box_arg(box, n):
+    """the harness's box argument: a number, or for "percoord" the bounds of tests/_boxes.py, "l0,..|u0,.." """
+    if box != "percoord":
+        return repr(box)
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    return ",".join(repr(float(v)) for v in lo) + "|" + ",".join(repr(float(v)) for v in up)
+
+
+def record(exe, name, n, hms, obj, box, fstdmin, seed, iterations=ITERATIONS, wide=None):
+    """one shape; the seed moves on until the branch holds and no decision is close (`wide`: the branch,
+    where the name does not begin with it)"""
+    wide = name.startswith("wide") if wide is None else wide
     for attempt in range(64):
         out = subprocess.check_output(
-            [exe, "steps", str(OBJ_IDS[obj]), str(n), str(hms), repr(box), str(seed + 1000 * attempt),
-             str(ITERATIONS), repr(fstdmin), str(MFEV)])
+            [exe, "steps", str(OBJ_IDS[obj]), str(n), str(hms), box_arg(box, n), str(seed + 1000 * attempt),
+             str(iterations), repr(fstdmin), str(MFEV)])
         rec = _norm(json.loads(out))
         if checks(rec, fstdmin, wide):
             break
@@ -249,9 +283,18 @@ def record(exe, name, n, hms, obj, box, fstdmin, seed):
         del st["ibest_kept"]
     replaced = sum(a["f"] != b["f"] for a, b in zip([rec["init"]] + rec["states"], rec["states"]))
     compress(rec, n)
-    rec.update({"name": name, "n": n, "hms": hms, "objective": obj, "box": box, "fstdmin": fstdmin, "mfev": MFEV,
-                "wide": wide, "seed": seed + 1000 * attempt, "replacements": replaced})
+    rec.update({"name": name, "n": n, "hms": hms, "objective": obj, "box": box,
+                "fstdmin": fstdmin, "mfev": MFEV, "wide": wide, "seed": seed + 1000 * attempt, "replacements": replaced})
     return rec
+
+
+def generate_percoord(ref="/root/reference"):
+    """tests/golden/nshs_percoord.json: PERCOORD alone"""
+    tmp = tempfile.mkdtemp(prefix="nshs_golden_")
+    try:
+        return {"steps": [record(build(ref, tmp), *PERCOORD, iterations=PERCOORD_ITERATIONS, wide=True)]}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def generate(ref="/root/reference"):
@@ -295,13 +338,17 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "nshs_runs.json"))
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--percoord", action="store_true",
+                    help="write the per-coordinate record alone, to tests/golden/nshs_percoord.json")
     a = ap.parse_args()
     if not os.path.isdir(os.path.join(a.ref, "src")):
         sys.exit("the reference sources are not at %s" % a.ref)
     if a.time:
         time_reference(a.ref)
         return
-    data = generate(a.ref)
+    if a.percoord and a.out.endswith("nshs_runs.json"):
+        a.out = os.path.join(ROOT, "tests", "golden", "nshs_percoord.json")
+    data = generate_percoord(a.ref) if a.percoord else generate(a.ref)
     text = dumps(data)
     with open(a.out, "w") as fh:
         fh.write(text)

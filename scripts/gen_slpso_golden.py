@@ -56,6 +56,10 @@ SHAPES = [
     ("n65_np4", 65, 4, "sphere", 5., 10., 55),
 ]
 GENERATIONS = 8
+# one short record under the per-coordinate box of tests/_boxes.py (the harness is handed its bounds, box_arg): the
+# eq. 11 redraw between a wall and the old position, and vmax, with bounds that differ in every coordinate
+PERCOORD = ("percoord_n11_np6", 11, 6, "sphere", "percoord", 10., 66)
+PERCOORD_GENERATIONS = 5
 STOL = 1e-12
 MIN_GAP = 1e-9
 OBJ_IDS = {"sphere": 0, "rosenbrock": 1, "rastrigin": 2, "ellipsoid": 3, "ackley": 4,
@@ -133,6 +137,24 @@ struct Probe: public SLPSOSearch {
 
 struct Ctx { int obj, n; std::vector<double> aux; };
 
+// "l0,l1,...|u0,u1,...": bounds given coordinate by coordinate (box_arg() below writes them from
+// tests/_boxes.py); false, and nothing touched, where `s` is a plain number
+static bool bounds_arg(const char *s, std::vector<double> &lo, std::vector<double> &up)
+{
+    if (!strchr(s, '|')) return false;
+    std::vector<double> *v = &lo;
+    size_t i = 0;
+    for (const char *p = s; *p;) {
+        if (*p == '|') { v = &up; i = 0; p++; continue; }
+        if (*p == ',') { p++; continue; }
+        char *e;
+        const double x = strtod(p, &e);
+        if (i < v->size()) (*v)[i++] = x;
+        p = e;
+    }
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     // steps <obj> <n> <np> <box> <seed> <generations> <Ufmax> <mfev> <stol>
@@ -146,6 +168,7 @@ int main(int argc, char **argv)
     if (!strcmp(argv[1], "steps")) {
         const double box = atof(argv[5]);
         std::vector<double> lo(n, -box), up(n, box), guess(n, 0.);
+        bounds_arg(argv[5], lo, up);
         multivariate_problem prob { f, n, lo.data(), up.data() };
         Random::seed((unsigned) atoi(argv[6]));
         Probe p(atoi(argv[9]), atof(argv[10]), np, 0.4, 0.9, 1.496, 0.01, 0.2, atof(argv[8]));
@@ -226,6 +249,13 @@ def build(ref, tmp):
     return exe
 
 
+def box_of(rec):
+    if rec["box"] == "percoord":
+        from _boxes import percoord_box
+        return [list(v) for v in percoord_box(rec["n"])]
+    return [-rec["box"]] * rec["n"], [rec["box"]] * rec["n"]
+
+
 def replay(rec):
     """the record through tests/slpso_model.py: (reproduced bit for bit, events, smallest gap, mfes ok)"""
     import numpy as np
@@ -237,7 +267,8 @@ def replay(rec):
         return np.array([float.fromhex(s) for s in v])
 
     n, np_ = rec["n"], rec["np"]
-    m = sm.Slpso(chol_model.objective(rec["objective"], n), [-rec["box"]] * n, [rec["box"]] * n, np_, rec["mfev"],
+    lo, up = box_of(rec)
+    m = sm.Slpso(chol_model.objective(rec["objective"], n), lo, up, np_, rec["mfev"],
                  rec["stol"], Ufmax=rec["Ufmax"])
     m.trace = True
     m.start(h(rec["init"]["x"]).reshape(np_, n), rec["init"]["perm"])
@@ -264,22 +295,32 @@ def replay(rec):
         r = m.mfes_real
         if abs(r - round(r)) < MIN_GAP and r != np_:
             ok_mfes = False
+    rec["repairs"] = dict(m.repairs)
     return True, set(m.events), min(m.gaps) if m.gaps else 1., ok_mfes
 
 
-def record(exe, name, n, np_, obj, box, ufmax, seed):
+def box_arg(box, n):
+    """the harness's box argument: a number, or for "percoord" the bounds of tests/_boxes.py, "l0,..|u0,.." """
+    if box != "percoord":
+        return repr(box)
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    return ",".join(repr(float(v)) for v in lo) + "|" + ",".join(repr(float(v)) for v in up)
+
+
+def record(exe, name, n, np_, obj, box, ufmax, seed, generations=GENERATIONS, need_repairs=0):
     mfev = 40 * np_
     for attempt in range(64):
         out = subprocess.check_output(
-            [exe, "steps", str(OBJ_IDS[obj]), str(n), str(np_), repr(box), str(seed + 1000 * attempt),
-             str(GENERATIONS), repr(ufmax), str(mfev), repr(STOL)])
+            [exe, "steps", str(OBJ_IDS[obj]), str(n), str(np_), box_arg(box, n), str(seed + 1000 * attempt),
+             str(generations), repr(ufmax), str(mfev), repr(STOL)])
         rec = _norm(json.loads(out))
-        rec.update({"name": name, "n": n, "np": np_, "objective": obj, "box": box, "Ufmax": ufmax, "mfev": mfev,
-                    "stol": STOL, "seed": seed + 1000 * attempt})
+        rec.update({"name": name, "n": n, "np": np_, "objective": obj, "box": box,
+                    "Ufmax": ufmax, "mfev": mfev, "stol": STOL, "seed": seed + 1000 * attempt})
         same, events, gap, ok_mfes = replay(rec)
         if not same:
             sys.exit("%s: tests/slpso_model.py does not reproduce the reference (seed %d)" % (name, rec["seed"]))
-        if gap >= MIN_GAP and ok_mfes:
+        if gap >= MIN_GAP and ok_mfes and min(rec["repairs"].values()) >= need_repairs:
             break
     else:
         sys.exit("%s: no seed without a close decision" % name)
@@ -330,6 +371,16 @@ def generate(ref="/root/reference"):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def generate_percoord(ref="/root/reference"):
+    """tests/golden/slpso_percoord.json: PERCOORD alone, with at least three coordinates redrawn at each wall ("repairs")"""
+    tmp = tempfile.mkdtemp(prefix="slpso_golden_")
+    try:
+        rec = record(build(ref, tmp), *PERCOORD, generations=PERCOORD_GENERATIONS, need_repairs=3)
+        return {"steps": [rec]}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def time_reference(ref="/root/reference"):
     """ms per generation of the reference on one core: the shape of scripts/bench_slpso.py"""
     tmp = tempfile.mkdtemp(prefix="slpso_time_")
@@ -355,13 +406,17 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "slpso_runs.json"))
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--percoord", action="store_true",
+                    help="write the per-coordinate record alone, to tests/golden/slpso_percoord.json")
     a = ap.parse_args()
     if not os.path.isdir(os.path.join(a.ref, "src")):
         sys.exit("the reference sources are not at %s" % a.ref)
     if a.time:
         time_reference(a.ref)
         return
-    data = generate(a.ref)
+    if a.percoord and a.out.endswith("slpso_runs.json"):
+        a.out = os.path.join(ROOT, "tests", "golden", "slpso_percoord.json")
+    data = generate_percoord(a.ref) if a.percoord else generate(a.ref)
     text = dumps(data)
     with open(a.out, "w") as fh:
         fh.write(text)

@@ -54,6 +54,10 @@ SHAPES = [
     ("n66_np8", 66, 8, "rosenbrock", (-3., 3.), 640, {}, 66),
 ]
 GENERATIONS = 6
+# one short record under the per-coordinate box of tests/_boxes.py (the harness is handed its bounds, box_arg): the
+# opposition point lower + upper - x of the usede start and the redraw, with bounds that differ in every coordinate
+PERCOORD = ("percoord_n11_np12_de", 11, 12, "sphere", "percoord", 400, {"usede": 1}, 77)
+PERCOORD_GENERATIONS = 5
 TOL = 1e-12
 MIN_GAP = 1e-6
 MAX_ATTEMPTS = 8
@@ -115,6 +119,24 @@ struct Probe: public SSDESearch {
 
 struct Ctx { int obj, n; std::vector<double> aux, pts, vals; bool log; };
 
+// "l0,l1,...|u0,u1,...": bounds given coordinate by coordinate (box_arg() below writes them from
+// tests/_boxes.py); false, and nothing touched, where `s` is a plain number
+static bool bounds_arg(const char *s, std::vector<double> &lo, std::vector<double> &up)
+{
+    if (!strchr(s, '|')) return false;
+    std::vector<double> *v = &lo;
+    size_t i = 0;
+    for (const char *p = s; *p;) {
+        if (*p == '|') { v = &up; i = 0; p++; continue; }
+        if (*p == ',') { p++; continue; }
+        char *e;
+        const double x = strtod(p, &e);
+        if (i < v->size()) (*v)[i++] = x;
+        p = e;
+    }
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     // steps <obj> <n> <npinit> <lo> <up> <seed> <generations> <mfev> <tol> <patience> <npmin> <ptop> <h> <usede> <repaircr>
@@ -134,6 +156,7 @@ int main(int argc, char **argv)
     };
     if (!strcmp(argv[1], "steps")) {
         std::vector<double> lo(n, atof(argv[5])), up(n, atof(argv[6])), guess(n, 0.);
+        bounds_arg(argv[5], lo, up);
         multivariate_problem prob { f, n, lo.data(), up.data() };
         Random::seed((unsigned) atoi(argv[7]));
         Probe p(atoi(argv[9]), npinit, atof(argv[10]), atoi(argv[11]), atoi(argv[12]), atof(argv[13]), atoi(argv[14]),
@@ -229,7 +252,8 @@ def model_of(rec, f=None, min_np=0):
     import chol_model
     import ssde_model as sm
     n, o = rec["n"], options(rec)
-    return sm.Ssde(f or chol_model.objective(rec["objective"], n), [rec["box"][0]] * n, [rec["box"][1]] * n, rec["mfev"],
+    lo, up = sm.box_of(rec)
+    return sm.Ssde(f or chol_model.objective(rec["objective"], n), lo, up, rec["mfev"],
                    rec["npinit"], rec["tol"], o["patience"], o["npmin"], o["ptop"], o["h"], bool(o["usede"]),
                    bool(o["repaircr"]), min_np=min_np)
 
@@ -276,25 +300,42 @@ def replay(rec):
         vals = np.array([v for _, v in m.points])
         if pts.tobytes() != h(st["pts"]).tobytes() or vals.tobytes() != h(st["vals"]).tobytes():
             return False, set(), 0., 0
+    rec["repairs"] = dict(m.repairs)
     return True, set(m.events), min(m.gaps) if m.gaps else 1., attempts
 
 
-def record(exe, name, n, npinit, obj, box, mfev, opts, seed):
+def box_arg(box, n):
+    """the harness's box argument: a number, or for "percoord" the bounds of tests/_boxes.py, "l0,..|u0,.." """
+    if box != "percoord":
+        return repr(box)
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    return ",".join(repr(float(v)) for v in lo) + "|" + ",".join(repr(float(v)) for v in up)
+
+
+def box_args(box, n):
+    """the harness's two box arguments: lower and upper, or the bounds string and a placeholder"""
+    return [box_arg(box, n), "0"] if box == "percoord" else [repr(box[0]), repr(box[1])]
+
+
+def record(exe, name, n, npinit, obj, box, mfev, opts, seed, generations=GENERATIONS, need_repairs=0):
     o = dict(DEFAULTS)
     o.update(opts)
     for attempt in range(400):
         out = subprocess.check_output(
-            [exe, "steps", str(OBJ_IDS[obj]), str(n), str(npinit), repr(box[0]), repr(box[1]), str(seed + 1000 * attempt),
-             str(GENERATIONS), str(mfev), repr(TOL), str(o["patience"]), str(o["npmin"]), repr(o["ptop"]),
+            [exe, "steps", str(OBJ_IDS[obj]), str(n), str(npinit), *box_args(box, n), str(seed + 1000 * attempt),
+             str(generations), str(mfev), repr(TOL), str(o["patience"]), str(o["npmin"]), repr(o["ptop"]),
              str(o["h"]), str(o["usede"]), str(o["repaircr"])])
         rec = _norm(json.loads(out))
-        rec.update({"name": name, "n": n, "npinit": npinit, "objective": obj, "box": list(box), "mfev": mfev, "tol": TOL,
+        rec.update({"name": name, "n": n, "npinit": npinit, "objective": obj,
+                    "box": box if box == "percoord" else list(box), "mfev": mfev, "tol": TOL,
                     "seed": seed + 1000 * attempt})
         rec.update(opts)
         same, events, gap, attempts = replay(rec)
         if not same:
             sys.exit("%s: tests/ssde_model.py does not reproduce the reference (seed %d)" % (name, rec["seed"]))
-        if (gap >= MIN_GAP or n <= EXACT_N) and attempts <= MAX_ATTEMPTS:
+        if (gap >= MIN_GAP or n <= EXACT_N) and attempts <= MAX_ATTEMPTS \
+                and min(rec["repairs"].values()) >= need_repairs:
             break
     else:
         sys.exit("%s: no seed without a close decision" % name)
@@ -356,6 +397,16 @@ def generate(ref="/root/reference"):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def generate_percoord(ref="/root/reference"):
+    """tests/golden/ssde_percoord.json: PERCOORD alone, with at least three coordinates redrawn at each bound ("repairs")"""
+    tmp = tempfile.mkdtemp(prefix="ssde_golden_")
+    try:
+        rec = record(build(ref, tmp), *PERCOORD, generations=PERCOORD_GENERATIONS, need_repairs=3)
+        return {"steps": [rec]}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def time_reference(ref="/root/reference"):
     """ms per generation of the reference on one core: the shape of scripts/bench_ssde.py"""
     tmp = tempfile.mkdtemp(prefix="ssde_time_")
@@ -383,13 +434,17 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "ssde_runs.json"))
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--percoord", action="store_true",
+                    help="write the per-coordinate record alone, to tests/golden/ssde_percoord.json")
     a = ap.parse_args()
     if not os.path.isdir(os.path.join(a.ref, "src")):
         sys.exit("the reference sources are not at %s" % a.ref)
     if a.time:
         time_reference(a.ref)
         return
-    data = generate(a.ref)
+    if a.percoord and a.out.endswith("ssde_runs.json"):
+        a.out = os.path.join(ROOT, "tests", "golden", "ssde_percoord.json")
+    data = generate_percoord(a.ref) if a.percoord else generate(a.ref)
     text = dumps(data)
     with open(a.out, "w") as fh:
         fh.write(text)

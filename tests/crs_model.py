@@ -89,7 +89,8 @@ class Crs:
         self.fev, self.it, self.trials, self.muts, self.stale = self.np, 0, 0, 0, 0
         self.depth = self.maxdepth = 0
         self.flag = 0
-        self.paths = dict(B=0, mut_acc=0, M=0, M_stale=0, M_inner_mut=0, popB_fail=0)
+        # (out_lo, out_up: coordinates of rejected trial points under their lower / over their upper bound)
+        self.paths = dict(B=0, mut_acc=0, M=0, M_stale=0, M_inner_mut=0, popB_fail=0, out_lo=0, out_up=0)
 
     # the pool in rank order, as the reference keeps it
     def x(self):
@@ -144,6 +145,8 @@ class Crs:
                 row = self.rows[self.order[idx[n - 1]]]
                 self.t = [2 * c[d] - row[d] for d in range(n)]
                 if not self.in_bounds(self.t):
+                    self.paths["out_lo"] += sum(self.t[d] < self.lower[d] for d in range(n))
+                    self.paths["out_up"] += sum(self.t[d] > self.upper[d] for d in range(n))
                     if self.repair:
                         if redraws >= self.max_depth:
                             return self._abandon(3)

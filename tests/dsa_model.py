@@ -54,6 +54,7 @@ class Dsa:
         self.n, self.np = self.lo.size, int(np_)
         self.adapt, self.nbatch, self.tol, self.stol = bool(adapt), int(nbatch), tol, stol
         self.gamma = gamma_of(self.nbatch)
+        self.paths = {"repair_lo": 0, "repair_up": 0}   # coordinates _repair met under / over their bound
 
     def start(self, X, f, fev=None):
         self.X = np.array(X, float).reshape(self.np, self.n)
@@ -80,9 +81,11 @@ class Dsa:
                 if T[i, j] < lo:
                     coin, u = coin_uniform(i, j)
                     T[i, j] = u * (up - lo) + lo if coin == 0 else lo
+                    self.paths["repair_lo"] += 1
                 if T[i, j] > up:
                     coin, u = coin_uniform(i, j)
                     T[i, j] = u * (up - lo) + lo if coin == 0 else up
+                    self.paths["repair_up"] += 1
         return T
 
     def _select(self, T, imethd, ftrial=None):

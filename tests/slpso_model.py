@@ -283,6 +283,7 @@ class Slpso:
         self.vmaxk, self.Ufmax = vmax, Ufmax
         self.trace = False               # collect `gaps`
         self.events = set()
+        self.repairs = {"low": 0, "high": 0}    # coordinates the eq. 11 redraw met past each wall
         self.gaps = []                  # relative gaps of the fitness comparisons when `trace`
 
     def evaluate(self, x):
@@ -351,9 +352,11 @@ class Slpso:
         x1 = x + v
         if x1 < self.lower[d]:
             self.events.add("redraw_low")
+            self.repairs["low"] += 1
             return between(src.redraw(kp, d), self.lower[d], x)
         if x1 > self.upper[d]:
             self.events.add("redraw_high")
+            self.repairs["high"] += 1
             return between(src.redraw(kp, d), x, self.upper[d])
         return x1
 

@@ -239,6 +239,7 @@ class Ssde:
         self.usede, self.repaircr, self.min_np = bool(usede), bool(repaircr), int(min_np)
         self.trace = False
         self.points, self.gaps, self.events = [], [], set()
+        self.repairs = {"low": 0, "high": 0}    # coordinates the DE trial's redraw met past each bound
 
     def evaluate(self, x):
         v = float(self.f(x))
@@ -363,6 +364,7 @@ class Ssde:
                     if d == j0 or src.ucross(i, d) <= CRi:
                         u[d] = x[pi][d] + R * (x[0][d] - x[qi][d]) + R * (x[0][d] - x[ri][d])
                         if u[d] < self.lower[d] or u[d] > self.upper[d]:
+                            self.repairs["low" if u[d] < self.lower[d] else "high"] += 1
                             u[d] = between(src.uredraw(i, d), self.lower[d], self.upper[d])
                             self.events.add("de_redraw")
                         cr1 += 1.
@@ -453,10 +455,18 @@ def _div(a, b):
 
 
 # ---- readers of tests/golden/ssde_runs.json ------------------------------------------------------------------
+def box_of(rec):
+    """a record's bounds: [lo, up] for every coordinate, or "percoord", the box of tests/_boxes.py"""
+    if rec["box"] == "percoord":
+        from _boxes import percoord_box
+        return [list(v) for v in percoord_box(rec["n"])]
+    return [rec["box"][0]] * rec["n"], [rec["box"][1]] * rec["n"]
+
+
 def model_of(rec, f, min_np=0):
     """the model of a "steps" record (or of any dict with its fields) over the objective f"""
-    n = rec["n"]
-    return Ssde(f, [rec["box"][0]] * n, [rec["box"][1]] * n, rec["mfev"], rec["npinit"], rec["tol"],
+    lo, up = box_of(rec)
+    return Ssde(f, lo, up, rec["mfev"], rec["npinit"], rec["tol"],
                 rec.get("patience", 1000), rec.get("npmin", 4), rec.get("ptop", 0.11), rec.get("h", 100),
                 bool(rec.get("usede", 0)), bool(rec.get("repaircr", 1)), min_np=min_np)
 

@@ -106,6 +106,54 @@ def test_the_device_is_the_model_fed_its_own_basis(hip, n, obj, first):
     assert updates >= 3
 
 
+@pytest.mark.parametrize("n", [37, 65])
+def test_the_first_sweep_under_bounds_that_differ_in_every_coordinate(hip, n):
+    """tests/_boxes.py's box: sigma[j] starts at (up[j] - lo[j]) / 4, another value in every coordinate, and the
+    two points of step j are clamp(x_best[j] -+ sigma[j]) to that coordinate's own bounds.  The first sweep only:
+    its basis is the identity on both sides, and from a strictly interior start no trial point equals x_best
+    (once x_best lies on a bound the clamped trial point IS x_best, an exact tie, which the decision-gap guard of
+    this file's walk rejects by construction).  First the model alone: at least three coordinates whose trial
+    point is clamped to the lower bound, three to the upper bound, three that stay strictly inside throughout,
+    and no decision closer than MIN_GAP.  Then the device, bit for bit."""
+    from _boxes import binding_witness, percoord_box, percoord_guess
+    lo, up = percoord_box(n)
+    x0 = percoord_guess(n, 3)[1]
+    f = device_objective("sphere", n)
+
+    def model():
+        return am.Acd(f, n, lo, up, 1 << 30, 0., 0.).start(x0)
+    w = model()
+    pts, margin = [], math.inf
+    for _ in range(n):
+        w.iterate()
+        margin = min(margin, w.margin)
+        pts.append(np.array([w.evals[0][0], w.evals[1][0]]))
+    binding_witness(pts, lo, up)
+    assert margin >= MIN_GAP and w.updated
+    g = hip.ACD(1 << 30, 0., 0., seed=7, from_guess=True)
+    g.initialize("sphere", lo, up, x0)
+    _bits(g.get_state("xbest"), x0, "from_guess")
+    _bits(g.get_state("sigma"), (up - lo) / 4., "initial sigma")
+    m = model()
+    for k in range(n):
+        tag = "n %d step %d: " % (n, k)
+        ix = m.ix
+        g.iterate()
+        m.iterate()
+        rows = g.get_state("x").reshape(2 * n, n)
+        _bits(rows[2 * ix:2 * ix + 2], [m.evals[0][0], m.evals[1][0]], tag + "points")
+        assert (rows[2 * ix:2 * ix + 2] >= lo).all() and (rows[2 * ix:2 * ix + 2] <= up).all(), tag
+        _bits(g.get_state("f")[2 * ix:2 * ix + 2], [m.evals[0][1], m.evals[1][1]], tag + "values")
+        _bits(g.get_state("xbest"), m.xbest, tag + "xbest")
+        _bits(g.get_state("fbest"), [m.fbest], tag + "fbest")
+        _bits(g.get_state("sigma"), m.sigma, tag + "sigma")
+        got = {q: int(g.get_state(q)[0]) for q in ("ix", "it", "fev", "improved", "itae", "flag")}
+        assert got == dict(ix=m.ix, it=m.it, fev=m.fev, improved=int(m.improved), itae=m.itae, flag=0), tag
+    assert m.updated
+    _bits(g.get_state("m"), m.m, "m after the first sweep")
+    _bits(g.get_state("p"), m.p, "p after the first sweep")
+
+
 @pytest.mark.parametrize("n,obj", [(2, "rosenbrock"), (33, "ellipsoid"), (128, "rosenbrock")])
 def test_run_iterate_and_a_chunk_of_one_give_the_same_bits(hip, n, obj):
     steps = 3 * n + 1

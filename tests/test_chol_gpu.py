@@ -28,21 +28,27 @@ def _rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
-def _pair(hip, n, lam, obj, P=1, ranked=False, bound=False, seed=77, mfev=10 ** 8, tol=1e-12,
-          stol=1e-12, box=5.):
-    lo, up = -box * np.ones(n), box * np.ones(n)
-    guess = np.random.default_rng(n + lam).uniform(-0.9 * box, 0.9 * box, (P, n))
-    g = hip.CholeskyCMAES(mfev, tol, stol, lam, 2., bound, seed=seed, populations=P, ranked=ranked)
-    g.initialize(getattr(hip.objectives, obj), lo, up, guess.ravel())
-    g.set_state("record_normals", [1.0])
+def _models(n, lam, obj, lo, up, guess, ranked=False, bound=False, mfev=10 ** 8, tol=1e-12, stol=1e-12, sigma0=2.):
     fast = n >= 64
     ms = []
-    for p in range(P):
-        m = CholModel(mfev, tol, stol, lam, 2., bound, ranked=ranked,
+    for row in guess:
+        m = CholModel(mfev, tol, stol, lam, sigma0, bound, ranked=ranked,
                       factor="cholesky" if fast else "chain", fast=fast)
-        m.init((objective_rows if fast else objective)(obj, n), lo, up, guess[p])
+        m.init((objective_rows if fast else objective)(obj, n), lo, up, row)
         ms.append(m)
-    return g, ms
+    return ms
+
+
+def _pair(hip, n, lam, obj, P=1, ranked=False, bound=False, seed=77, mfev=10 ** 8, tol=1e-12,
+          stol=1e-12, box=5., lo_up=None, guess=None, sigma0=2.):
+    """`lo_up`, `guess`, `sigma0`: other bounds, starting points and step than +-box, the drawn ones and 2"""
+    lo, up = (-box * np.ones(n), box * np.ones(n)) if lo_up is None else lo_up
+    if guess is None:
+        guess = np.random.default_rng(n + lam).uniform(-0.9 * box, 0.9 * box, (P, n))
+    g = hip.CholeskyCMAES(mfev, tol, stol, lam, sigma0, bound, seed=seed, populations=P, ranked=ranked)
+    g.initialize(getattr(hip.objectives, obj), lo, up, guess.ravel())
+    g.set_state("record_normals", [1.0])
+    return g, _models(n, lam, obj, lo, up, guess, ranked, bound, mfev, tol, stol, sigma0)
 
 
 @pytest.mark.parametrize("P", [1, 5])
@@ -73,6 +79,46 @@ def test_generations_match_the_model(hip, n, lam, ranked, bound, P):
         if bound and gen == 1:
             assert (np.abs(g.get_state("arx", 0)) == 2.5).any()
     print("n %d lambda %d ranked %d bound %d P %d: worst rel err %.3e" % (n, lam, ranked, bound, P, worst))
+
+
+@pytest.mark.parametrize("n,lam,tri,route", [(37, 16, 1, "cma_sample_eval64<1, 32>"),
+                                             (128, 16, 1, "cma_sample_eval<1, 8, true>"),
+                                             (128, 16, 0, "cma_sample_eval<1, 8, false>")])
+def test_the_clamp_takes_each_coordinates_own_bounds(hip, oracle_lib, n, lam, tri, route):
+    """bound=True under tests/_boxes.py's box, whose bounds differ in every coordinate and lie on three sides of
+    sphere's optimum; n = 37 is off every tile, n = 128 takes the triangular and the full operand.  First, on the
+    model alone under the generator's normals as the oracle states them: coordinates on their lower bound, on
+    their upper bound and strictly inside, three of each at least.  Then the walk of
+    test_generations_match_the_model, its tolerance."""
+    import cma_route_cases as rc
+    from _boxes import binding_witness, percoord_box, percoord_centre
+    seed, gens, sigma0 = 77, 6, 0.7
+    lo, up = percoord_box(n)
+    guess = percoord_centre(n)[None, :]
+    (w,) = _models(n, lam, "sphere", lo, up, guess, bound=True, sigma0=sigma0)
+    rows = []
+    for gen in range(gens):
+        z = np.zeros(lam * n)
+        oracle_lib.f("philox_normals")(seed, w.it, lam, n, z)
+        w.generation(z)
+        rows.append(np.array(w.arx, float))
+    binding_witness(rows, lo, up)
+    g, (m,) = _pair(hip, n, lam, "sphere", bound=True, seed=seed, lo_up=(lo, up), guess=guess, sigma0=sigma0)
+    g.set_state("chol_tri", [float(tri)])
+    for gen in range(1, gens + 1):
+        g.iterate()
+        assert rc.SAMPLE_NAMES[int(g.get_state("sample_route")[0])] == route
+        assert int(g.get_state("sample_lean")[0]) == 0
+        m.generation(g.get_state("zlast"))
+        for key in KEYS:
+            err = _rel(g.get_state(key), [m.sigma] if key == "sigma" else getattr(m, key))
+            assert err <= 1e-9, "n %d gen %d %s: %.3e" % (n, gen, key, err)
+        assert _rel(g.get_state("fit_val"), m.fit_val) <= 1e-9
+        X, Xm = g.get_state("arx").reshape(lam, n), np.asarray(m.arx, float).reshape(lam, n)
+        assert (X >= lo).all() and (X <= up).all()
+        np.testing.assert_array_equal(X == lo, Xm == lo)
+        np.testing.assert_array_equal(X == up, Xm == up)
+        assert (int(g.get_state("it")[0]), int(g.get_state("fev")[0])) == (m.it, m.fev)
 
 
 def _state(g, p=0):

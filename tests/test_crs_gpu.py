@@ -320,6 +320,67 @@ def test_the_depth_cap_ends_a_collapsed_pool_with_flag_3(hip, P):
         assert got == [2, 50, 0, 0, 0, 0], (p, got)
 
 
+def _percoord_handle(hip, n, np_, seed, lo, up, pool, repair):
+    g = hip.CRS(10 ** 6, np_, 0., seed=seed, max_depth=DEPTH, repair=repair)
+    g.initialize("sphere", lo, up, np.zeros(n))
+    X = g.get_state("rows").reshape(np_, n)
+    assert ((X >= lo) & (X <= up)).all()            # the initial draw, coordinate by coordinate
+    assert ((X.max(0) - X.min(0)) > 0.25 * (up - lo)).sum() >= n // 2
+    g.set_state("x", pool)
+    g.set_state("record_draws", [float(RECORDS)])
+    return g
+
+
+@pytest.mark.parametrize("n,np_,repair,inner", [(37, 20, False, 0.84), (37, 20, True, 0.84), (257, 7, False, 0.72)])
+def test_the_box_test_under_bounds_that_differ_in_every_coordinate(hip, n, np_, repair, inner):
+    """tests/_boxes.py's box: CRS rejects a reflected point with a coordinate outside [lo[i], up[i]] (and draws
+    again under `repair`); the kernel stages lo[i] / up[i], another pair in every coordinate.  CRS never clamps,
+    so the witness is the model's count of coordinates that put a trial point out (`paths`: out_lo, out_up),
+    three on each side at least.  It is established before anything is compared: a first handle only hands over
+    the records of what its generator drew, and the model runs alone on them from the pool made here, with its
+    own objective.  Then a second handle of the same seed walks beside a second model, as in
+    test_the_walk_is_the_model_bit_for_bit.  The pool fills the inner share of every coordinate's own interval
+    (see _start); n = 37 is off every tile, 257 puts one live lane into the second pass."""
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    seed, its = 100 * n + np_, 12
+    pool = 0.5 * (lo + up) + inner * 0.5 * (up - lo) * np.random.default_rng(seed).uniform(-1., 1., (np_, n))
+    # ---- the witness: the model alone on the generator's draws
+    a = _percoord_handle(hip, n, np_, seed, lo, up, pool, repair)
+    w = cm.Crs(device_objective("sphere", n), n, np_, list(lo), list(up), 10 ** 6, 0., max_depth=DEPTH, repair=repair)
+    w.start(pool)
+    for it in range(its):
+        a.iterate()
+        assert w.iterate(cm.TableSource(_records(a, n), n, np_)), "the pool collapsed: choose another"
+    assert w.paths["out_lo"] >= 3 and w.paths["out_up"] >= 3, w.paths
+    # ---- the walk
+    g = _percoord_handle(hip, n, np_, seed, lo, up, pool, repair)
+    order = [int(v) for v in g.get_state("order")]
+    fs = np.empty(np_)
+    fs[order] = g.get_state("f")
+    m = cm.Crs(device_objective("sphere", n), n, np_, list(lo), list(up), 10 ** 6, 0., max_depth=DEPTH, repair=repair)
+    m.start(g.get_state("rows").reshape(np_, n), fs=fs)
+    assert m.order == order, "the stable ranking"
+    for k in ("fev", "it", "trials", "muts", "stale"):
+        setattr(m, k, int(g.get_state(k)[0]))
+    for it in range(its):
+        tag = "n %d np %d iteration %d " % (n, np_, it)
+        if it % 2:
+            _walk(g)
+        elif it % 4:
+            assert g.run(1) == 1
+        else:
+            g.iterate()
+        rec = _records(g, n)
+        src = cm.TableSource(rec, n, np_)
+        assert m.iterate(src) and src.exhausted(), tag
+        _device_is_model(g, m, tag)
+        _bits(rec, m.records, tag + "records")
+        # (no containment is asserted: the reflected point is tested against the box, the mutated one that may
+        # take its place is not, in the reference either -- crs.cpp:176 tests the reflection alone)
+    assert m.paths["out_lo"] >= 3 and m.paths["out_up"] >= 3, m.paths
+
+
 def test_repair_is_the_model_and_only_better_points_go_in(hip):
     n, np_ = 5, 8
     g = _start(hip, n, np_, seed=4, repair=True, box=2.)

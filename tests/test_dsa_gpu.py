@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import dsa_model as dm
+from slpso_model import device_objective
 from test_dsa_model import GOLD, band, _h
 
 pytestmark = pytest.mark.gpu
@@ -215,6 +216,68 @@ def test_three_generations_against_the_keyed_model(hip, method, mapst, n, np_, P
     if P > 1:       # the populations are independent streams
         assert not np.array_equal(g.get_state("X", 0), g.get_state("X", 1))
         assert not np.array_equal(g.get_state("scalars", 0)[:6], g.get_state("scalars", 1)[:6])
+
+
+def _percoord_handle(hip, n, np_, P, seed, lo, up, pools):
+    """a handle under tests/_boxes.py's box whose populations start from the given host-made pools"""
+    f = device_objective("sphere", n)
+    g = hip.DSA(10 ** 9, 0., 0., np_, True, 2, seed=seed, populations=P)
+    g.initialize(hip.objectives.sphere, lo, up, np.zeros((P, n)))
+    for p in range(P):
+        X = g.get_state("X", p).reshape(np_, n)
+        assert ((X >= lo) & (X <= up)).all()
+        # the initial draw: every coordinate spread over its own interval, not a neighbour's
+        assert ((X.max(0) - X.min(0)) > 0.25 * (up - lo)).sum() >= n // 2
+        g.set_state("X", pools[p], p)
+        g.set_state("f", [f(x) for x in pools[p]], p)
+    g.set_state("record_draws", [1.])
+    return g
+
+
+@pytest.mark.parametrize("n,np_,P,gens", [(37, 7, 2, 15), (513, 7, 1, 10)])
+def test_the_repair_coin_under_bounds_that_differ_in_every_coordinate(hip, n, np_, P, gens):
+    """tests/_boxes.py's box: the initial draw u (up[j] - lo[j]) + lo[j] and the repair -- a redraw in
+    [lo[j], up[j]] or the bound itself, by a coin -- read another pair of bounds in every coordinate.  DSA does
+    not clamp, so the witness is the model's count of repaired coordinates (`paths`), three at each bound at
+    least in every population.  It is established before anything is compared: a first handle only hands over
+    the uniforms and words its generator drew (what _check_keying holds to the generator's host twin), and the
+    model runs alone on them, from a pool made on the host, with its own objective and its own R, and counts.
+    Then a second handle of the same seed walks beside a second model, as in
+    test_three_generations_against_the_keyed_model, longer, with both decisions drawn: n = 37 is off every tile,
+    513 puts one live lane into the third pass."""
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    seed = 41 + n
+    rng = np.random.default_rng(seed)
+    pools = [lo + (up - lo) * rng.random((np_, n)) for _ in range(P)]
+    fobj = device_objective("sphere", n)
+    # ---- the witness: the model alone on the generator's draws
+    a = _percoord_handle(hip, n, np_, P, seed, lo, up, pools)
+    alone = []
+    for p in range(P):
+        w = dm.Dsa(fobj, lo, up, np_, adapt=True, nbatch=2)
+        w.start(pools[p], [fobj(x) for x in pools[p]], np_)
+        alone.append(w)
+    for _ in range(gens):
+        a.iterate()
+        for p, w in enumerate(alone):
+            raw = a.get_state("scalars", p)[:6]
+            R = 0. if raw[5] == 1. else 1. / (-2. * math.log(raw[5]))
+            w.iterate_keyed(raw, R, a.get_state("dirdraws", p), a.get_state("mapdraws", p),
+                            a.get_state("bounddraws", p))
+    for p, w in enumerate(alone):
+        assert w.paths["repair_lo"] >= 3 and w.paths["repair_up"] >= 3, (p, w.paths)
+    # ---- the walk
+    g = _percoord_handle(hip, n, np_, P, seed, lo, up, pools)
+    models = [_model_of(g, p, lo, up, np_, 1, nbatch=2) for p in range(P)]
+    for _ in range(gens):
+        g.iterate()
+        for p, m in enumerate(models):
+            _step_model(g, m, p, seed if n < 256 else None)
+            T = g.get_state("trial", p).reshape(np_, n)
+            assert ((T >= lo) & (T <= up)).all()
+    for p, m in enumerate(models):
+        assert m.paths["repair_lo"] >= 3 and m.paths["repair_up"] >= 3, (p, m.paths)
 
 
 def test_a_pool_at_a_corner_is_repaired_into_the_box(hip):

@@ -406,9 +406,29 @@ def _u01(lo, hi):
 
 
 def test_restarts_double_mu_and_account_like_the_model(hip, capfd):
+    n = 4
+    _restarts_account_like_the_model(hip, capfd, -5. * np.ones(n), 5. * np.ones(n), 0.5 + np.arange(n) / 4.)
+
+
+def test_restart_points_come_from_each_coordinates_own_interval(hip, capfd):
+    """tests/_boxes.py's box: restart point j is u (upper[j] - lower[j]) + lower[j] (hees.cpp:194-196), another
+    map in every coordinate.  The chain of runs is re-run one run at a time from the points the host twin of the
+    generator maps into the box, as above: a run started anywhere else would not spend the evaluations or reach
+    the value the chain reports.  Every such point lies in its own coordinate's interval, and in no case do two
+    coordinates of it coincide (under a uniform box a shared u would show as equal coordinates)."""
+    from _boxes import percoord_box, percoord_guess
+    n = 7
+    lo, up = percoord_box(n)
+    starts = _restarts_account_like_the_model(hip, capfd, lo, up, percoord_guess(n))
+    assert len(starts) >= 1
+    for x0 in starts:
+        assert ((x0 >= lo) & (x0 <= up)).all() and np.unique(x0).size == n
+
+
+def _restarts_account_like_the_model(hip, capfd, lo, up, guess):
+    """returns the restart points (the start points of the runs after the first)"""
     from bboptpy_amd.distributed import philox4x32_10
-    n, np_, mfev, tol, sigma0, seed = 4, 6, 800, 1e-1, 1., 123
-    lo, up, guess = -5. * np.ones(n), 5. * np.ones(n), 0.5 + np.arange(n) / 4.
+    n, np_, mfev, tol, sigma0, seed = len(lo), 6, 800, 1e-1, 1., 123
     g = hip.HEES(mfev, tol, mres=3, print=True, np=np_, sigma0=sigma0, seed=seed)
     sol = g.optimize("sphere", lo, up, guess)
     out = capfd.readouterr().out.splitlines()
@@ -425,7 +445,7 @@ def test_restarts_double_mu_and_account_like_the_model(hip, capfd):
     assert sol.n_evals == fev and (fev >= mfev or len(runs) == 3)
     # every run again as a single run of its own (seed + r, the remaining budget, the keyed start
     # point), its normals fed to the model: the model's fev and incumbent are the run's
-    x0, spent, xbest, fbest = guess, 0, None, np.inf
+    x0, spent, xbest, fbest, starts = guess, 0, None, np.inf, []
     for r, (mu, fe, fb) in enumerate(runs):
         one = hip.HEES(mfev - spent, tol, np=int(mu), sigma0=sigma0, seed=seed + r)
         one.initialize("sphere", lo, up, x0)
@@ -443,7 +463,10 @@ def test_restarts_double_mu_and_account_like_the_model(hip, capfd):
         spent += int(fe)
         x0 = np.array([_u01(*philox4x32_10(seed, j, 0, r + 1, STREAM_RESTART << 24)[:2]) * (up[j] - lo[j]) + lo[j]
                        for j in range(n)])
+        if r + 1 < len(runs):
+            starts.append(x0)
     assert _rel(sol.x, xbest) <= RTOL
+    return starts
 
 
 def test_restarts_refuse_batches_and_open_boxes(hip):

@@ -122,6 +122,83 @@ def test_three_generations_against_the_synchronous_model(hip, mut, n, np_, npmin
         assert not np.array_equal(g.get_state("X", 0), g.get_state("X", 1))
 
 
+def _percoord_pool(n, np_, rng):
+    """rows under tests/_boxes.py's box from which the clamp binds on both sides and leaves a third of the
+    coordinates alone: the trial is x + r1 (best - |x|) - r2 (worst - |x|), so the coordinates that are
+    negative throughout (class 1) move by up to twice their size and meet both bounds, those packed next to
+    their lower bound (class 0) meet it, and those packed in [0.9, 1.1], well inside (class 2), stay inside"""
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    j, U = np.arange(n), rng.random((np_, n))
+    return lo, up, np.where(j % 3 == 0, lo + 0.3 * U, np.where(j % 3 == 1, lo + (up - lo) * U, 0.9 + 0.2 * U))
+
+
+def _percoord_handle(hip, n, np_, npmin, k0, P, seed, lo, up, pools, f):
+    g = hip.JAYA(10 ** 7, 0., np_, npmin, k0=k0, mutation=jm.MUTATIONS["original"], seed=seed, populations=P)
+    g.initialize(hip.objectives.sphere, lo, up, np.zeros((P, n)))
+    for p in range(P):
+        X = g.get_state("X", p).reshape(np_, n)
+        assert ((X >= lo) & (X <= up)).all()        # the initial draw, coordinate by coordinate
+        assert ((X.max(0) - X.min(0)) > 0.25 * (up - lo)).sum() >= n // 2
+        g.set_state("X", pools[p], p)
+        g.set_state("f", [f(x) for x in pools[p]], p)
+    g.set_state("record_draws", [1.])
+    return g
+
+
+def _percoord_model(g, p, n, np_, npmin, k0, lo, up, f=None):
+    m = jm.Jaya(f, lo, up, np_, npmin, adapt=True, k0=k0, mutation=jm.ORIGINAL, order="sync")
+    m.start(g.get_state("X", p), g.get_state("f", p), g.get_state("xchaos", p)[0])
+    # (the incumbent is the best point ever evaluated, the drawn pool's included)
+    m.fgbest, m.bestx = float(g.get_state("fgbest", p)[0]), g.get_state("bestx", p).copy()
+    m.best = m.pbest = float(g.get_state("best", p)[0])
+    return m
+
+
+@pytest.mark.parametrize("n,np_,npmin,k0,P", [(37, 7, 2, 3, 2), (513, 7, 2, 3, 1)])
+def test_the_clamp_of_the_trial_under_bounds_that_differ_in_every_coordinate(hip, n, np_, npmin, k0, P):
+    """tests/_boxes.py's box: the initial draw and the clamp of every trial (jaya_trials) read another pair of
+    bounds in every coordinate.  The witness is established before anything is compared: a first handle only
+    hands over its starting state and what its generator drew (the shuffle and the uniforms), and the model runs
+    alone on them with its own objective; over its trials at least three coordinates sit on their lower bound,
+    three on their upper bound and three stay strictly inside in every row.  Then a second handle of the same
+    seed walks beside a second model as in test_three_generations_against_the_synchronous_model.  n = 37 is
+    off every tile, 513 puts one live lane into the third pass."""
+    from _boxes import binding_witness
+    seed = 31 + n
+    rng = np.random.default_rng(seed)
+    f = device_objective("sphere", n)
+    pools = []
+    for _ in range(P):
+        lo, up, X = _percoord_pool(n, np_, rng)
+        pools.append(X)
+    # ---- the witness: the model alone on the generator's draws
+    a = _percoord_handle(hip, n, np_, npmin, k0, P, seed, lo, up, pools, f)
+    alone = [_percoord_model(a, p, n, np_, npmin, k0, lo, up, f) for p in range(P)]
+    trials = [[] for _ in range(P)]
+    for _ in range(3):
+        a.iterate()
+        for p, w in enumerate(alone):
+            raw = a.get_state("draws", p)
+            d = raw[:-1].reshape(np_, n, 2)
+            w.iterate_sync(a.get_state("occ", p).astype(int), a.get_state("len", p).astype(int), d[..., 0],
+                           d[..., 1], uroul=raw[-1])
+            trials[p].append(np.array(w.trial))
+    for p in range(P):
+        binding_witness(trials[p], lo, up)
+    # ---- the walk
+    g = _percoord_handle(hip, n, np_, npmin, k0, P, seed, lo, up, pools, f)
+    models = [_percoord_model(g, p, n, np_, npmin, k0, lo, up) for p in range(P)]
+    for gen in range(3):
+        g.iterate()
+        for p, m in enumerate(models):
+            _step_model(g, m, p)
+            T = g.get_state("trial", p).reshape(np_, n)
+            assert ((T >= lo) & (T <= up)).all()
+            if n > 256:     # (as there: past one pass the trial's value is the sum in the device's order)
+                _bits(g.get_state("ftrial", p), [f(t) for t in T], "ftrial")
+
+
 def test_bounded_pool_at_a_corner_and_a_nan_objective(hip):
     """a crafted pool next to the upper corner (the trials are clamped to the box) and a callback
     that returns NaN for part of the trials (they rank last: +inf, never accepted)"""

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import lm_model as lm
+from _boxes import binding_witness, percoord_box, percoord_guess
 from test_lm_model import GOLD, KEYS, INT_KEYS
 
 pytestmark = pytest.mark.gpu
@@ -58,18 +59,29 @@ def _snapshot(g, p=0, keys=SNAP):
     return {k: g.get_state(k, p).copy() for k in keys}
 
 
-def _against_model(hip, n, lam, memory, rad, usenew, obj, gens, P=3, bound=False, seed=1):
-    rng = np.random.default_rng(1000 * n + 10 * lam + memory)
-    guess = rng.uniform(-3., 3., (P, n))
-    lo, up = -5. * np.ones(n), 5. * np.ones(n)
-    g = hip.LmCMAES(10 ** 9, 0., lam, memory, 1.5, bound, bool(rad), bool(usenew), seed=seed, populations=P)
-    g.initialize(obj, lo, up, guess.ravel())
+def _models(P, lam, memory, usenew, bound, obj, lo, up, guess):
     models = []
     for p in range(P):
         m = lm.LmModel(10 ** 9, 0., lam, memory, 1.5, bound, bool(usenew), device=True)
         m.init(obj, lo, up, guess[p])
         models.append(m)
+    return models
+
+
+def _against_model(hip, n, lam, memory, rad, usenew, obj, gens, P=3, bound=False, seed=1, box=None, guess=None,
+                   before=None):
+    """`box`, `guess`: other bounds and starting points than +-5 and the drawn ones; `before(models, table)`
+    is called with models of their own, before the device has done anything"""
+    rng = np.random.default_rng(1000 * n + 10 * lam + memory)
+    if guess is None:
+        guess = rng.uniform(-3., 3., (P, n))
+    lo, up = (-5. * np.ones(n), 5. * np.ones(n)) if box is None else box
+    g = hip.LmCMAES(10 ** 9, 0., lam, memory, 1.5, bound, bool(rad), bool(usenew), seed=seed, populations=P)
+    g.initialize(obj, lo, up, guess.ravel())
+    models = _models(P, lam, memory, usenew, bound, obj, lo, up, guess)
     table = np.array([[m.draw(rng, bool(rad)) for m in models] for _ in range(gens)])
+    if before is not None:
+        before(_models(P, lam, memory, usenew, bound, obj, lo, up, guess), table)
     g.inject_draws(table)
     worst = (0., None)
     for gen in range(gens):
@@ -105,6 +117,34 @@ def test_wrapping_runs_against_the_device_form_of_the_model(hip, n, lam, memory,
     g, models = _against_model(hip, n, lam, memory, rad, usenew, obj, m * t + 3)
     assert int(g.get_state("memlen")[0]) == m == models[0].m
     assert sorted(g.get_state("jarr").astype(int)) == list(range(m))
+
+
+def percoord_witness(models, table):
+    """from the models alone: the clamp of the mean binds under tests/_boxes.py's box"""
+    lo, up = models[0].lower, models[0].upper
+    for p, m in enumerate(models):
+        means = []
+        for gen in range(table.shape[0]):
+            m.generation(table[gen, p])
+            means.append(np.array(m.xmean, float))
+        binding_witness(means, np.asarray(lo, float), np.asarray(up, float))
+
+
+@pytest.mark.parametrize("n,lam,memory,rad", [(33, 8, 0, 1), (257, 8, 2, 0)])
+def test_the_mean_is_clamped_to_each_coordinates_own_bounds(hip, n, lam, memory, rad):
+    """bound=True under bounds that differ in every coordinate (tests/_boxes.py): sphere drives the mean
+    onto its lower bound in a third of the coordinates, onto its upper bound in a third, and leaves a third
+    free -- asserted on the models alone before the device runs; then the walk of this file, its tolerance.
+    n = 33 is off every tile, 257 the first n past one pass of the workgroup."""
+    lo, up = percoord_box(n)
+    g, models = _against_model(hip, n, lam, memory, rad, 1, "sphere", 12, bound=True, box=(lo, up),
+                               guess=percoord_guess(n, 3), before=percoord_witness)
+    for p in range(3):
+        xm = g.get_state("xmean", p)
+        assert (xm >= lo).all() and (xm <= up).all()
+        # on a bound exactly where the model's mean is
+        np.testing.assert_array_equal(xm == lo, np.asarray(models[p].xmean) == lo)
+        np.testing.assert_array_equal(xm == up, np.asarray(models[p].xmean) == up)
 
 
 def test_n4096_three_generations(hip):

@@ -30,7 +30,7 @@ import pytest
 
 import mayfly_model as mm
 from test_hees_model import band
-from test_mayfly_model import GOLD, STEPS, _h, walk
+from test_mayfly_model import GOLD, PERCOORD, STEPS, _h, bounds_of, percoord_witness, walk
 
 pytestmark = pytest.mark.gpu
 
@@ -68,11 +68,14 @@ def _ints(g, key):
     return [int(v) for v in g.get_state(key)]
 
 
-@pytest.mark.parametrize("name", sorted(STEPS))
+# (the last record: bounds that differ in every coordinate, tests/golden/mayfly_percoord.json)
+@pytest.mark.parametrize("name", sorted(STEPS) + sorted(PERCOORD))
 def test_every_recorded_generation_from_the_reference_state(hip, name):
-    rec = STEPS[name]
+    rec = STEPS.get(name) or PERCOORD[name]
     n, np_ = rec["n"], rec["np"]
-    lo, up = rec["lower"] * np.ones(n), rec["box"] * np.ones(n)
+    lo, up = (np.asarray(v, float) for v in bounds_of(rec))
+    if name in PERCOORD:
+        percoord_witness(rec)
     width = up - lo
     g = hip.Mayfly(np_, rec["mfev"], seed=5, **rec["params"])
     g.initialize(rec["objective"], lo, up, np.zeros(n))

@@ -121,13 +121,59 @@ def test_generations_under_the_devices_draws_are_the_model(hip, n, np_, obj, pgb
     selection and counter equal; positions and velocities bit for bit, except the descendants of an exp()
     form, which are held to XTOL of the box width; values to FTOL.  Two flies the mutation touches
     (pmutnp = 0.3), a tenth of their coordinates each."""
+    _walk_under_the_devices_draws(hip, n, np_, obj, pgb, [-5.] * n, [5.] * n, 100 + n)
+
+
+PAR = dict(pmutnp=0.3, pmutdim=0.1)
+# (n, np, pgb, seed): the seed is one under which the model's own run meets the witness below
+PERCOORD = [(37, 6, False, 137), (257, 6, True, 357)]
+
+
+def _percoord_handle(hip, n, np_, pgb, seed, lo, up):
+    g = hip.Mayfly(np_, 10 ** 6, seed=seed, record_draws=True, pgb=pgb, **PAR)
+    g.initialize("sphere", np.asarray(lo), np.asarray(up), np.zeros(n))
+    return g
+
+
+@pytest.mark.parametrize("n,np_,pgb,seed", PERCOORD, ids=["n%d" % c[0] for c in PERCOORD])
+def test_generations_under_bounds_that_differ_in_every_coordinate(hip, n, np_, pgb, seed):
+    """tests/_boxes.py's box: the initial draw, vmax = k (up[j] - lo[j]), the mutation's sigma and both clamps
+    read another pair of bounds in every coordinate.  The witness is established before anything is compared: a
+    first handle only hands over its starting state and the tables of what its generator drew, and the model
+    runs alone on them with its own objective; over its generations at least three coordinates of a fly sit on
+    their lower bound, three on their upper bound, and three stay strictly inside in every fly.  Then a second
+    handle of the same seed walks as above.  n = 37 is off every tile, 257 puts one live lane into the second
+    pass."""
+    from _boxes import binding_witness, percoord_box
+    lo, up = percoord_box(n)
+    gens = 4
+    a = _percoord_handle(hip, n, np_, pgb, seed, lo, up)
+    w = mm.Mayfly(device_objective("sphere", n), n, np_, list(lo), list(up), 10 ** 6, pgb=pgb, **PAR)
+    w.stable_sort = True
+    w.start({key: a.get_state(key).copy() for key in STATE})
+    # the initial draw, coordinate by coordinate (the reference, and so the engine, stores the drawn point as
+    # the fly's velocity and starts every fly at the origin: mayfly_model.Mayfly.init_words)
+    for key in ("males_v", "females_v"):
+        V = a.get_state(key).reshape(np_, n)
+        assert ((V >= lo) & (V <= up)).all()
+        assert ((V.max(0) - V.min(0)) > 0.1 * (up - lo)).sum() >= n // 2
+    flies = []
+    for _ in range(gens):
+        a.iterate()
+        w.iterate(mm.TableSource(a.get_state("draws"), n, np_, w.nmut, w.nmd))
+        flies += [np.array([y.x for y in w.males]), np.array([y.x for y in w.females])]
+    binding_witness(flies, lo, up)
+    _walk_under_the_devices_draws(hip, n, np_, "sphere", pgb, list(lo), list(up), seed, gens)
+
+
+def _walk_under_the_devices_draws(hip, n, np_, obj, pgb, lo, up, seed, gens=4):
     f = device_objective(obj, n)
-    lo, up = [-5.] * n, [5.] * n
-    width = 10. * np.ones(n)
-    par = dict(pgb=pgb, pmutnp=0.3, pmutdim=0.1)
-    g = _start(hip, n, np_, obj=obj, seed=100 + n, record_draws=True, **par)
+    width = np.asarray(up, float) - np.asarray(lo, float)
+    par = dict(pgb=pgb, **PAR)
+    g = hip.Mayfly(np_, 10 ** 6, seed=seed, record_draws=True, **par)
+    g.initialize(obj, np.asarray(lo, float), np.asarray(up, float), np.zeros(n))
     worst = Worst()
-    for k in range(4):
+    for k in range(gens):
         tag = "n %d generation %d " % (n, k)
         before = {key: g.get_state(key).copy() for key in STATE}
         g.iterate()

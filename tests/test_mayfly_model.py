@@ -19,6 +19,9 @@ PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mayfl
 with open(PATH) as fh:
     GOLD = json.load(fh)
 STEPS = {rec["name"]: rec for rec in GOLD["steps"]}
+# one short record under bounds that differ in every coordinate (tests/_boxes.py): its "box" is "percoord"
+with open(os.path.join(os.path.dirname(PATH), "mayfly_percoord.json")) as fh:
+    PERCOORD = {rec["name"]: rec for rec in json.load(fh)["steps"]}
 PATHS = ("f_attract", "f_random", "m_attract", "m_dance", "improve_not_last", "short_window", "aliased",
          "clamp_box", "clamp_vmax")
 
@@ -27,14 +30,21 @@ def _h(v):
     return [float.fromhex(s) for s in v]
 
 
+def bounds_of(rec):
+    if rec["box"] == "percoord":
+        from _boxes import percoord_box
+        return [list(v) for v in percoord_box(rec["n"])]
+    return [rec["lower"]] * rec["n"], [rec["box"]] * rec["n"]
+
+
 def reference_model(rec, **kw):
     """(model, source) at the recorded run's init()"""
     n, np_ = rec["n"], rec["np"]
     words = jaya_model.Words(mm.mt19937_words(rec["seed"], sum(rec["nwords"])))
     par = dict(rec["params"])
     par.update(kw)
-    m = mm.Mayfly(chol_model.objective(rec["objective"], n), n, np_, [rec["lower"]] * n, [rec["box"]] * n,
-                  rec["mfev"], **par)
+    lo, up = bounds_of(rec)
+    m = mm.Mayfly(chol_model.objective(rec["objective"], n), n, np_, lo, up, rec["mfev"], **par)
     m.init_words(words)
     assert words.i == rec["nwords"][0]
     return m, mm.WordsSource(words, n)
@@ -59,9 +69,9 @@ def _check(m, st, tag):
     assert m.fbest == float.fromhex(st["fbest"]), tag + "fbest"
 
 
-@pytest.mark.parametrize("name", sorted(STEPS))
+@pytest.mark.parametrize("name", sorted(STEPS) + sorted(PERCOORD))
 def test_the_model_replays_the_recorded_reference(name):
-    rec = STEPS[name]
+    rec = STEPS.get(name) or PERCOORD[name]
     m, _ = reference_model(rec)
     _check(m, rec["init"], name + " init ")
     assert m.nmut == rec["nmut"]
@@ -72,6 +82,34 @@ def test_the_model_replays_the_recorded_reference(name):
         assert len(m.evals) == 3 * np_ + m.nmut and m.fev == st["fev"] and m.took == st["took"], tag
         assert (m.duplicates(True), m.duplicates(False)) == (st["dup_m"], st["dup_f"]), tag
     assert m.fev == 2 * np_ + len(rec["states"]) * (3 * np_ + m.nmut)
+
+
+def test_the_percoord_record_clamps_at_the_box_and_at_vmax():
+    """the record that pins vmax = k (up[j] - lo[j]), the mutation's sigma and the clamps under bounds that differ
+    in every coordinate: both clamps fire in generations the device can be held to, and every point the model
+    evaluates on the way lies in its coordinate's interval"""
+    (rec,) = PERCOORD.values()
+    assert rec["n"] <= 12 and len(rec["states"]) <= 5 and rec["nmut"] >= 1
+    assert rec["paths"]["clamp_box"] >= 3 and rec["paths"]["clamp_vmax"] >= 3
+    lo, up = bounds_of(rec)
+    for g, st, _, m in walk(rec):
+        for x, _ in m.evals:
+            assert all(a <= v <= b for a, v, b in zip(lo, x, up)), g
+    percoord_witness(rec)
+
+
+def percoord_witness(rec):
+    """from the reference's recorded run alone (the model reproduces it bit for bit): over the generations,
+    at least three coordinates of the flies on their lower bound, three on their upper bound, and three strictly
+    inside in every fly"""
+    import numpy as np
+    from _boxes import binding_witness
+    lo, up = (np.asarray(v, float) for v in bounds_of(rec))
+    states = []
+    for _, _, _, m in walk(rec):
+        st = m.state()
+        states += [np.asarray(st["males_x"], float), np.asarray(st["females_x"], float)]
+    return binding_witness(states, lo, up)
 
 
 def test_the_fixture_holds_the_shapes_the_paths_the_bands_and_the_signature():

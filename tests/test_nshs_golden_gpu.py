@@ -19,7 +19,7 @@ import pytest
 
 import jaya_model as jm
 import nshs_model as nm
-from test_nshs_model import FSTD_BOUND, GOLD, _h
+from test_nshs_model import FSTD_BOUND, GOLD, PERCOORD, _h, box_of
 
 pytestmark = pytest.mark.gpu
 
@@ -47,10 +47,12 @@ def _fstd_close(g, st, tag):
     return err
 
 
-@pytest.mark.parametrize("rec", GOLD["steps"], ids=[r["name"] for r in GOLD["steps"]])
+# (the last record: bounds that differ in every coordinate, tests/golden/nshs_percoord.json)
+@pytest.mark.parametrize("rec", GOLD["steps"] + PERCOORD["steps"],
+                         ids=[r["name"] for r in GOLD["steps"] + PERCOORD["steps"]])
 def test_injected_reference_uniforms_reproduce_reference_states(hip, rec):
     n, hms = rec["n"], rec["hms"]
-    lo, up = -rec["box"] * np.ones(n), rec["box"] * np.ones(n)
+    lo, up = (np.asarray(v, float) for v in box_of(rec))
     g = hip.NSHS(rec["mfev"], hms, rec["fstdmin"], seed=5)
     g.initialize(rec["objective"], lo, up, np.zeros(n))
     ini = rec["init"]

@@ -325,6 +325,62 @@ def _draws_of(seed, p, n, it):
     return out
 
 
+def _percoord_start(n, hms):
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    # a memory spread over each coordinate's own interval
+    X0 = lo + (up - lo) * np.random.default_rng(1000 * n + hms).random((hms, n))
+    return lo, up, X0
+
+
+def _percoord_model(n, hms, lo, up, X0, fs=None):
+    m = nm.Nshs(device_objective("sphere", n), n, hms, lo, up, 10 ** 6, 1e-4, form="device")
+    m.start(X0, fs=fs)
+    return m
+
+
+@pytest.mark.parametrize("n,hms", [(37, 6), (257, 5)])
+def test_bounds_that_differ_in_every_coordinate_bind_and_the_walk_is_the_model(hip, n, hms):
+    """tests/_boxes.py's box: nshs_coordinate's fresh value between lower[i] and upper[i], its bandwidth
+    (upper[i] - lower[i]) / tunerange and its clamp read another pair of bounds in every coordinate, and tunerange
+    is half the LARGEST width.  First the model alone, under the draws of the device's counters computed on the
+    host (_draws_of): its candidates reach their lower bound, their upper bound and stay strictly inside, three
+    coordinates of each at least.  Then the device from the same memory, phase by phase and fused in turn, bit
+    for bit.  n = 37 is off every tile; 257 puts one live lane into the second pass."""
+    from _boxes import binding_witness
+    seed, its = 100 * n + hms, 10
+    lo, up, X0 = _percoord_start(n, hms)
+    w = _percoord_model(n, hms, lo, up, X0)
+    cands = []
+    for it in range(its):
+        w.iterate(_draws_of(seed, 0, n, it))
+        cands.append(np.array(w.cand))
+    binding_witness(cands, lo, up)
+    assert w.tunerange == ((up - lo) / 2.).max() and w.wide
+    g = hip.NSHS(10 ** 6, hms, 1e-4, seed=seed, record_draws=True)
+    g.initialize("sphere", lo, up, np.zeros(n))
+    Xi = g.get_state("x").reshape(hms, n)
+    assert (Xi >= lo).all() and (Xi <= up).all()        # the initial memory, coordinate by coordinate
+    assert g.get_state("tunerange")[0] == w.tunerange
+    g.set_state("x", X0)
+    m = _percoord_model(n, hms, lo, up, X0, fs=g.get_state("f"))
+    _device_is_model(g, m, "n %d start " % n)
+    for it in range(its):
+        tag = "n %d iteration %d " % (n, it)
+        if it % 2:
+            _phases_against_model(g, m, tag)
+        else:
+            assert g.run(1) == 1
+            m.generate(g.get_state("draws").reshape(n, 4))
+            _bits(g.get_state("cand"), m.cand, tag + "fused cand")
+            m.evaluate(g.get_state("fcand")[0])
+            m.replace()
+            _device_is_model(g, m, tag + "fused ")
+        _bits(g.get_state("draws"), _draws_of(seed, 0, n, it), tag + "draws")
+        c = g.get_state("cand")
+        assert (c >= lo).all() and (c <= up).all()
+
+
 def test_recorded_draws_are_their_counters_and_injecting_them_repeats_the_iteration(hip):
     """the draws are keyed by (coordinate, block, iteration, stream | population) and by nothing
     else: the fused kernel, the phase kernels and a batch record the same uniforms.  Injected into

@@ -17,7 +17,10 @@ import nshs_model as nm
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 with open(os.path.join(ROOT, "tests", "golden", "nshs_runs.json")) as fh:
     GOLD = json.load(fh)
-for _rec in GOLD["steps"]:      # the fixture keeps the changed rows of a state: put the whole memory back
+# one short record under bounds that differ in every coordinate (tests/_boxes.py), "box": "percoord"
+with open(os.path.join(ROOT, "tests", "golden", "nshs_percoord.json")) as fh:
+    PERCOORD = json.load(fh)
+for _rec in GOLD["steps"] + PERCOORD["steps"]:      # the fixture keeps the changed rows of a state: put the whole memory back
     _x, _f, _n = _rec["init"]["x"], _rec["init"]["f"], _rec["n"]
     for _st in _rec["states"]:
         _x, _f = list(_x), list(_f)
@@ -45,9 +48,17 @@ def _same(a, b, what):
     assert a.tobytes() == b.tobytes(), (what, float(np.abs(a - b).max()))
 
 
+def box_of(rec):
+    if rec["box"] == "percoord":
+        from _boxes import percoord_box
+        return percoord_box(rec["n"])
+    return [-rec["box"]] * rec["n"], [rec["box"]] * rec["n"]
+
+
 def model_of(rec, form):
     n, hms = rec["n"], rec["hms"]
-    m = nm.Nshs(chol_model.objective(rec["objective"], n), n, hms, [-rec["box"]] * n, [rec["box"]] * n, rec["mfev"],
+    lo, up = box_of(rec)
+    m = nm.Nshs(chol_model.objective(rec["objective"], n), n, hms, lo, up, rec["mfev"],
                 rec["fstdmin"], form=form)
     m.start(_h(rec["init"]["x"]).reshape(hms, n))
     return m
@@ -68,7 +79,8 @@ def _check(m, st, tag, fstd=True):
     assert (m.ibest, m.iworst, m.it, m.fev) == (st["ibest"], st["iworst"], st["it"], st["fev"]), tag
 
 
-@pytest.mark.parametrize("rec", GOLD["steps"], ids=[r["name"] for r in GOLD["steps"]])
+@pytest.mark.parametrize("rec", GOLD["steps"] + PERCOORD["steps"],
+                         ids=[r["name"] for r in GOLD["steps"] + PERCOORD["steps"]])
 def test_reference_form_reproduces_the_recorded_states_bit_for_bit(rec):
     m = model_of(rec, "reference")
     _check(m, rec["init"], rec["name"] + " init ")
@@ -79,6 +91,21 @@ def test_reference_form_reproduces_the_recorded_states_bit_for_bit(rec):
         _same(m.cand, _h(st["cand"]), tag + "cand")
         _same([m.fcand], [float.fromhex(st["fcand"])], tag + "fcand")
         assert m.wide == rec["wide"], tag
+
+
+def test_the_percoord_record_binds_on_both_sides():
+    """the record that pins nshs_coordinate under bounds that differ in every coordinate: the reference's own
+    candidates reach a lower and an upper bound, its memory starts inside each coordinate's interval, and
+    tunerange is half the largest width"""
+    (rec,) = PERCOORD["steps"]
+    lo, up = (np.asarray(v) for v in box_of(rec))
+    assert rec["n"] <= 12 and len(rec["states"]) <= 5
+    X0 = _h(rec["init"]["x"]).reshape(rec["hms"], rec["n"])
+    assert (X0 >= lo).all() and (X0 <= up).all()
+    cands = np.array([_h(st["cand"]) for st in rec["states"]])
+    assert (cands >= lo).all() and (cands <= up).all()
+    assert (cands == lo).any() and (cands == up).any()
+    assert model_of(rec, "reference").tunerange == ((up - lo) / 2.).max()
 
 
 def test_device_form_differs_in_fstd_alone():

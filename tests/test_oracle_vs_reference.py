@@ -237,3 +237,120 @@ def test_restart_drivers_bit_exact(oracle_lib, ref_lib, driver, variant):
     xr, fr, _ = r.optimize("rastrigin", lo, up, guess)
     np.testing.assert_array_equal(xo, xr)
     assert fo == fr
+
+
+# ---- the per-coordinate box of tests/_boxes.py: bounds that differ in every coordinate and bind ----
+from _boxes import binding_witness, percoord_box, percoord_centre, percoord_guess    # noqa: E402
+
+
+@pytest.mark.parametrize("variant", ["cmaes", "active", "sep"])
+@pytest.mark.parametrize("n,lam,obj,seed", [(10, 8, "sphere", 10), (11, 12, "sphere", 10),
+                                            (12, 10, "rosenbrock", 16)])
+def test_cma_bound_percoord_box_bit_exact(oracle_lib, ref_lib, variant, n, lam, obj, seed):
+    """bound=True under lower[j] / upper[j] that differ per coordinate and are reached: the clamp of
+    the candidates (cmaes.cpp:74-77,93-95; sep_cmaes.cpp), every generation bit for bit.  The seeds
+    are ones under which the reference's own candidates meet the witness of the GPU cases: three
+    coordinates on their lower bound, three on their upper bound, three strictly inside in every row
+    (n = 10 is the smallest n whose three classes hold three coordinates each)."""
+    lo, up = percoord_box(n)
+    hs = []
+    for L in (oracle_lib, ref_lib):
+        L.seed(seed)
+        h = po.cma(L, variant, 10 ** 7, 1e-12, lam, sigma0=0.5, bound=True)
+        h.init(obj, lo, up, percoord_centre(n))
+        hs.append(h)
+    keys = ("xmean", "sigma", "csep" if variant == "sep" else "C", "D", "pc", "ps", "arx", "fit_val",
+            "fit_idx")
+    rows = []
+    for it in range(12):
+        for h in hs:
+            h.iterate()
+        _same(hs[0], hs[1], keys, "%s n=%d it=%d" % (variant, n, it))
+        rows.append(hs[1].get("arx").copy())
+    binding_witness(rows, lo, up)
+
+
+@pytest.mark.parametrize("algo,kw,keys", [
+    ("shade", dict(mfev=6000, npinit=30, tol=1e-8), ("x", "f", "arch", "MCR", "MF", "k", "np", "fev")),
+    ("jade", dict(mfev=6000, np_=25, tol=1e-8), ("x", "f", "arch", "mucr", "muf", "fev")),
+    ("sansde", dict(mfev=200000, np_=20, tol=1e-9), ("x", "f", "cr", "p", "fp", "crm", "crrec",
+                                                      "crdeltaf", "pns", "pnf", "fpns", "fpnf", "fev")),
+    ("apso", dict(mfev=6000, tol=1e-8, np_=15), ("x", "v", "xb", "f", "fb", "xbest", "fbest", "w",
+                                                 "c1", "c2", "state", "it", "fev")),
+    ("cso", dict(mfev=10 ** 8, stol=1e-9, np_=12, vmax=0.5), ("x", "v", "f", "mean", "meanw", "xbest", "fbest",
+                                                    "fev")),
+    ("cso", dict(mfev=10 ** 8, stol=1e-9, np_=30, pcompete=4, ring=True, vmax=0.5),
+     ("x", "v", "f", "meanw", "pmean", "home", "xbest", "fbest", "fev")),
+])
+@pytest.mark.parametrize("n", [7, 12])
+def test_swarms_percoord_box_bit_exact(oracle_lib, ref_lib, algo, kw, keys, n):
+    """the initial draw u (up[j] - lo[j]) + lo[j], the midpoint repair of the DE family
+    (shade.cpp / jade.cpp / sansde.cpp), APSO's and CSO's vmax = k (up[j] - lo[j]) and clamp, under
+    a box that differs per coordinate and excludes the optimum in two thirds of them"""
+    lo, up = percoord_box(n)
+    hs = []
+    for L in (oracle_lib, ref_lib):
+        L.seed(33)
+        h = getattr(po, algo)(L, **kw)
+        h.init("sphere", lo, up, percoord_centre(n))
+        hs.append(h)
+    o, r = hs
+    # (CSO's means do not exist before its first generation)
+    _same(o, r, ("x", "f") if algo == "cso" else keys, "%s init" % algo)
+    X0 = r.get("x").reshape(-1, n)
+    assert np.all(X0 >= lo) and np.all(X0 <= up)
+    on_lo = on_up = False
+    for it in range(80 if algo == "cso" else 40):
+        o.iterate()
+        r.iterate()
+        if algo == "apso" and not (0 <= r.scalar("state") <= 4):
+            break   # the reference indexed past its rule table (apso.cpp:384): undefined
+        _same(o, r, keys, "%s n=%d it=%d" % (algo, n, it))
+        X = r.get("x").reshape(-1, n)
+        on_lo, on_up = on_lo or bool((X == lo).any()), on_up or bool((X == up).any())
+    if algo in ("shade", "jade", "sansde"):
+        rl, ru = o.repairs()
+        assert rl >= 3 and ru >= 3, (rl, ru)        # the repair ran at both bounds
+    else:
+        assert on_lo and on_up                      # the clamp held particles on both bounds
+
+
+@pytest.mark.parametrize("local", [False, True])
+def test_ccpso_percoord_box_bit_exact(oracle_lib, ref_lib, capfd, local):
+    """CCPSO with correct=True: the clamp of every drawn coordinate (ccpso.cpp) and, with `local`,
+    the box scaled into the local search (ccpso.cpp:371-435)"""
+    n, npp = 12, 8
+    lo, up = percoord_box(n)
+    hs = []
+    for L in (oracle_lib, ref_lib):
+        L.seed(91)
+        extra = dict(local=po.cma(L, "cmaes", 300, 1e-8, 8), localfreq=3) if local else {}
+        h = po.ccpso(L, 10 ** 8, 1e-9, npp, [4] if local else [2, 3, 6], correct=True, **extra)
+        h.init("sphere", lo, up, percoord_centre(n))
+        hs.append(h)
+    for it in range(30):
+        for h in hs:
+            h.iterate()
+        for k in ("x", "y", "yhat", "fx", "fy", "k", "ibest", "strat", "fyhat", "phat", "fev", "is",
+                  "nswarm", "cpswarm", "improved"):
+            np.testing.assert_array_equal(hs[0].get(k), hs[1].get(k),
+                                          err_msg="ccpso local=%s it=%d %s" % (local, it, k))
+    X = hs[1].get("x").reshape(-1, n)
+    assert np.all(X >= lo) and np.all(X <= up) and (X == lo).any() and (X == up).any()
+    capfd.readouterr()
+
+
+@pytest.mark.parametrize("driver", ["bipop", "ipop"])
+def test_restart_drivers_percoord_box_bit_exact(oracle_lib, ref_lib, driver):
+    """the restart points are drawn per coordinate from [lower[i], upper[i]] (the drivers switch
+    the inner optimizer's clamp off, so the box enters a run through those draws alone)"""
+    n = 8
+    lo, up = percoord_box(n)
+    out = []
+    for L in (oracle_lib, ref_lib):
+        L.seed(44)
+        h = getattr(po, driver)(L, po.cma(L, "cmaes", 1, 1e-6, 4), 20000)
+        out.append(h.optimize("rastrigin", lo, up, percoord_guess(n)))
+    (xo, fo, _), (xr, fr, _) = out
+    np.testing.assert_array_equal(xo, xr)
+    assert fo == fr

@@ -20,9 +20,11 @@ STATE = ("ph", "fitns", "order", "pmut", "ig", "fev", "fbest", "xbest")
 LO, UP = -3.25, 5.
 
 
-def _start(hip, n=17, np_=32, nd=6, obj="rosenbrock", seed=7, P=1, ngen=10 ** 5, **kw):
+def _start(hip, n=17, np_=32, nd=6, obj="rosenbrock", seed=7, P=1, ngen=10 ** 5, box=None, **kw):
+    """`box`: (lower, upper) arrays in place of LO, UP"""
     g = hip.PIKAIA(np_, ngen, nd, seed=seed, populations=P, **kw)
-    g.initialize(obj, LO * np.ones(n), UP * np.ones(n), np.zeros(P * n))
+    lo, up = (LO * np.ones(n), UP * np.ones(n)) if box is None else box
+    g.initialize(obj, lo, up, np.zeros(P * n))
     return g
 
 
@@ -129,10 +131,28 @@ def test_generations_under_the_devices_draws_are_the_model(hip, n, np_, obj, kw)
     device recorded: parents, crossover windows, kinds of mutation, phenotypes, points, values, the elite
     decision, the rank order, pmut and the counters are the device's, the floats bit for bit.  A generation
     with a decision too close to call (pikaia_model.Pikaia.ok) asks for another seed."""
+    _walk_under_the_devices_draws(hip, n, np_, obj, kw, [LO] * n, [UP] * n)
+
+
+@pytest.mark.parametrize("n", [37, 257])
+def test_the_phenotype_is_scaled_by_each_coordinates_own_bounds(hip, n):
+    """tests/_boxes.py's box: x[i] = lower[i] + u[i] (upper[i] - lower[i]) is another map in every coordinate
+    (PIKAIA only scales by the box: the search runs in the unit cube and nothing is repaired into the box, so
+    there is no bound to sit on).  The walk above, bit for bit; n = 37 is off every tile, 257 puts one live lane
+    into the second pass."""
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    g = _walk_under_the_devices_draws(hip, n, 6, "sphere", dict(imut=5, ielite=1), list(lo), list(up))
+    X, U = g.get_state("x").reshape(6, n), g.get_state("ph").reshape(6, n)
+    assert ((X >= lo) & (X <= up)).all()
+    assert X.tobytes() == (lo + U * (up - lo)).tobytes()
+
+
+def _walk_under_the_devices_draws(hip, n, np_, obj, kw, lo, up):
     nd = 6
-    g = _start(hip, n, np_, nd, obj=obj, seed=200 + n, record_draws=True, **kw)
+    g = _start(hip, n, np_, nd, obj=obj, seed=200 + n, record_draws=True, box=(np.asarray(lo), np.asarray(up)), **kw)
     assert g.table_len() == pm.table_layout(n, np_, nd)["len"]
-    d = pm.Pikaia(device_objective(obj, n), n, np_, 10 ** 5, nd, [LO] * n, [UP] * n, order="stable", **kw)
+    d = pm.Pikaia(device_objective(obj, n), n, np_, 10 ** 5, nd, lo, up, order="stable", **kw)
     for k in range(5):
         tag = "n %d generation %d " % (n, k)
         before = {key: g.get_state(key).copy() for key in ("ph", "fitns", "order", "pmut", "ig", "fev")}
@@ -160,6 +180,7 @@ def test_generations_under_the_devices_draws_are_the_model(hip, n, np_, obj, kw)
         got = [int(g.get_state(key)[0]) for key in ("fev", "ig", "flag")]
         assert got == [d.fev, d.ig, 0], (tag, got)
     print("n %d np %d %s: paths %s" % (n, np_, obj, {p: c for p, c in d.paths.items() if c}))
+    return g
 
 
 def test_recorded_draws_injected_again_reproduce_the_run(hip):

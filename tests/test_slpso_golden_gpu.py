@@ -19,7 +19,7 @@ at most, p by 1.3e-15 (n = 5; bit-exact at n = 2, where Rosenbrock is a single t
 import numpy as np
 import pytest
 
-from test_slpso_model import GOLD, _h, replay
+from test_slpso_model import GOLD, PERCOORD, _h, box_of, replay
 
 pytestmark = pytest.mark.gpu
 
@@ -81,10 +81,14 @@ def phase_generation(g):
     return evals
 
 
-@pytest.mark.parametrize("rec", GOLD["steps"], ids=[r["name"] for r in GOLD["steps"]])
+# (the last record: bounds that differ in every coordinate, tests/golden/slpso_percoord.json)
+@pytest.mark.parametrize("rec", GOLD["steps"] + PERCOORD["steps"],
+                         ids=[r["name"] for r in GOLD["steps"] + PERCOORD["steps"]])
 def test_injected_reference_draws_reproduce_reference_states(hip, rec):
     n, np_ = rec["n"], rec["np"]
-    lo, up = -rec["box"] * np.ones(n), rec["box"] * np.ones(n)
+    lo, up = (np.asarray(v, float) for v in box_of(rec))
+    if rec["box"] == "percoord":        # the reference's run redrew three coordinates or more at each wall
+        assert min(rec["repairs"].values()) >= 3
     _, tables = replay(rec, check=False)
     g = hip.SLPSO(rec["mfev"], rec["stol"], np_, Ufmax=rec["Ufmax"], seed=5)
     g.initialize(rec["objective"], lo, up, np.zeros(n))

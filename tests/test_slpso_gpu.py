@@ -70,6 +70,51 @@ def test_device_generator_against_the_model_fed_its_recorded_draws(hip, n, np_, 
     print("n = %d, np = %d: worst relative deviation from the model: f %.3e, p %.3e, s %.3e; events %s"
           % (n, np_, worst["f"], worst["p"], worst["s"], " ".join(sorted(m.events))))
 
+def _percoord_pair(hip, n, np_, seed):
+    """a handle under tests/_boxes.py's box (rosenbrock, as above) and the model started from its initial swarm"""
+    from _boxes import percoord_box
+    lo, up = percoord_box(n)
+    g = hip.SLPSO(40 * np_, 1e-12, np_, seed=seed, record_draws=True)
+    g.initialize("rosenbrock", lo, up, np.zeros(n))
+    X = g.get_state("x").reshape(np_, n)
+    assert ((X >= lo) & (X <= up)).all()            # the initial draw, coordinate by coordinate
+    m = sm.Slpso(sm.device_objective("rosenbrock", n), list(lo), list(up), np_, 40 * np_, 1e-12)
+    m.trace = True
+    return g, m.start(X, [int(v) for v in g.get_state("perm")]), lo, up
+
+
+# (the seeds: ones under which the model's own run redraws at both walls and meets no close decision)
+@pytest.mark.parametrize("n,np_,seed", [(37, 6, 1037), (257, 5, 1257)])
+def test_the_redraw_under_bounds_that_differ_in_every_coordinate(hip, n, np_, seed):
+    """tests/_boxes.py's box: the eq. 11 redraw between a wall and the old position, and vmax, read another pair
+    of bounds in every coordinate (the kernels stage them as lo[i] / up[i]).  SLPSO never sits on a bound, so the
+    witness is the model's count of coordinates redrawn at each wall (`repairs`), three at least.  It is
+    established before anything is compared: a first handle only hands over its initial swarm and the tables of
+    what its generator drew, and the model runs alone on them: it must redraw at both walls and meet no decision
+    closer than 1e-9.  Then a second handle of the same seed walks
+    as in test_device_generator_against_the_model_fed_its_recorded_draws.  n = 37 is off every tile, 257 puts
+    one live lane into the second pass."""
+    gens = 10
+    a, w, lo, up = _percoord_pair(hip, n, np_, seed)
+    for _ in range(gens):
+        a.iterate()
+        w.iterate(sm.TableSource(a.get_state("draws"), n, np_))
+    assert min(w.repairs.values()) >= 3, w.repairs
+    assert min(w.gaps) >= 1e-9, "a close decision: choose another seed"
+    g, m, lo, up = _percoord_pair(hip, n, np_, seed)
+    worst = {"f": 0., "p": 0., "s": 0.}
+    compare(g, m.state(), "init ", worst)
+    for it in range(1, gens + 1):
+        if it % 2:
+            g.iterate()
+        else:
+            phase_generation(g)
+        m.iterate(sm.TableSource(g.get_state("draws"), n, np_))
+        compare(g, m.state(), "n = %d generation %d " % (n, it), worst)
+        X = g.get_state("x").reshape(np_, n)
+        assert ((X >= lo) & (X <= up)).all()
+    assert m.repairs == w.repairs and min(m.gaps) >= 1e-9
+
 
 # (b) ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [65, 130])

@@ -25,7 +25,10 @@ with open(os.path.join(ROOT, "tests", "golden", "slpso_runs.json")) as fh:
     GOLD = json.load(fh)
 # the fixture keeps the changed entries of a state's arrays and, of a generation's mt19937 words, their
 # number and CRC-32: put whole arrays back, and the words from the record's seed
-for _rec in GOLD["steps"]:
+# one short record under bounds that differ in every coordinate (tests/_boxes.py), "box": "percoord"
+with open(os.path.join(ROOT, "tests", "golden", "slpso_percoord.json")) as fh:
+    PERCOORD = json.load(fh)
+for _rec in GOLD["steps"] + PERCOORD["steps"]:
     sm.unpack_states([_rec["init"]] + _rec["states"])
     _live = sm.Mt19937Words(_rec["seed"])
     _live.take(_rec["init"]["words"])
@@ -53,9 +56,17 @@ def _same(a, b, what):
     assert a.tobytes() == b.tobytes(), (what, float(np.abs(a - b).max()))
 
 
+def box_of(rec):
+    if rec["box"] == "percoord":
+        from _boxes import percoord_box
+        return [list(v) for v in percoord_box(rec["n"])]
+    return [-rec["box"]] * rec["n"], [rec["box"]] * rec["n"]
+
+
 def model_of(rec):
     n, np_ = rec["n"], rec["np"]
-    m = sm.Slpso(chol_model.objective(rec["objective"], n), [-rec["box"]] * n, [rec["box"]] * n, np_, rec["mfev"],
+    lo, up = box_of(rec)
+    m = sm.Slpso(chol_model.objective(rec["objective"], n), lo, up, np_, rec["mfev"],
                  rec["stol"], Ufmax=rec["Ufmax"])
     return m.start(_h(rec["init"]["x"]).reshape(np_, n), rec["init"]["perm"])
 
@@ -93,7 +104,8 @@ def replay(rec, check=True):
     return m, tables
 
 
-@pytest.mark.parametrize("rec", GOLD["steps"], ids=[r["name"] for r in GOLD["steps"]])
+@pytest.mark.parametrize("rec", GOLD["steps"] + PERCOORD["steps"],
+                         ids=[r["name"] for r in GOLD["steps"] + PERCOORD["steps"]])
 def test_model_reproduces_the_recorded_states_bit_for_bit(rec):
     m, tables = replay(rec)
     assert sorted(m.events) == rec["events"]
@@ -121,6 +133,21 @@ def test_the_records_cover_every_branch():
     assert WANTED <= seen
     assert [(r["n"], r["np"]) for r in GOLD["steps"]] == [(2, 2), (5, 3), (12, 8), (33, 6), (65, 4)]
     assert GOLD["steps"][2]["Ufmax"] == 1.
+
+
+def test_the_percoord_record_redraws_at_both_walls():
+    """the record that pins the eq. 11 redraw (between the wall and the old position) and vmax under bounds that
+    differ in every coordinate: at least three coordinates are redrawn at each wall, and every recorded position lies in its coordinate's interval"""
+    (rec,) = PERCOORD["steps"]
+    assert rec["n"] <= 12 and len(rec["states"]) <= 5
+    assert {"redraw_low", "redraw_high"} <= set(rec["events"])
+    # the witness that the box binds: coordinates the model redrew at each wall while it reproduced the record
+    m, _ = replay(rec, check=False)
+    assert m.repairs == rec["repairs"] and min(m.repairs.values()) >= 3, m.repairs
+    lo, up = (np.asarray(v) for v in box_of(rec))
+    for st in [rec["init"]] + rec["states"]:
+        X = _h(st["x"]).reshape(rec["np"], rec["n"])
+        assert (X >= lo).all() and (X <= up).all()
 
 
 def test_the_live_mt19937_is_the_standard_one():

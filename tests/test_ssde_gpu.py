@@ -47,19 +47,20 @@ def box(n):
     return -3. * np.ones(n), 5. * np.ones(n)
 
 
-def make(hip, shape, f=None, **ext):
+def make(hip, shape, f=None, bounds=None, **ext):
+    """`bounds`: (lower, upper) in place of box(n)"""
     n, npinit, obj, mfev, opts = shape
     ext.setdefault("seed", 77)
     g = hip.SSDE(mfev, npinit, 1e-12, **opts, **ext)
-    lo, up = box(n)
+    lo, up = bounds or box(n)
     g.initialize(obj if f is None else f, lo, up, np.zeros(n * ext.get("populations", 1)))
     return g
 
 
-def model_from(g, shape, population=0):
+def model_from(g, shape, population=0, bounds=None):
     """the model started from the device's pool and values"""
     n, npinit, obj, mfev, opts = shape
-    lo, up = box(n)
+    lo, up = bounds or box(n)
     m = sm.Ssde(sm.device_objective(obj, n), lo, up, mfev, npinit, 1e-12, min_np=4, **opts)
     x = g.get_state("x", population).reshape(-1, n)
     m.start(x, g.get_state("f", population), fev=int(g.get_state("fev", population)[0]))
@@ -117,6 +118,46 @@ def test_device_draws_against_the_model(hip, shape):
     assert int(g.get_state("gen")[0]) == 5
     if opts.get("usede"):
         assert {"de_success", "de_failure"} & m.events
+
+
+# (n, npinit, seed): the seed is one under which the model's own run meets the witness below
+PERCOORD = [(37, 12, 77), (257, 12, 77)]
+
+
+@pytest.mark.parametrize("n,npinit,seed", PERCOORD, ids=["n%d" % c[0] for c in PERCOORD])
+def test_the_redraw_under_bounds_that_differ_in_every_coordinate(hip, n, npinit, seed):
+    """tests/_boxes.py's box with the DE step: the start holds every point beside its opposite
+    lower + upper - x, and a coordinate of a DE trial outside [lo[d], up[d]] is drawn again inside it -- another
+    pair of bounds in every coordinate (the kernels stage them as lo[i] / up[i]).  SSDE never sits on a bound,
+    so the witness is the model's count of coordinates redrawn past each bound (`repairs`), three at least.  It
+    is established before anything is compared: a first handle only hands over its starting pool and the tables
+    of what its generator drew, and the model runs alone on them with its own objective.  Then a second handle
+    of the same seed walks as in test_device_draws_against_the_model, twice as long.  n = 37 is off every tile,
+    257 puts one live lane into the second pass."""
+    from _boxes import percoord_box
+    bounds = percoord_box(n)
+    lo, up = bounds
+    shape, gens = (n, npinit, "sphere", 100 * npinit, {"usede": True}), 10
+    # ---- the witness: the model alone on the generator's draws
+    a = make(hip, shape, bounds=bounds, seed=seed, record_draws=True)
+    x0 = a.get_state("x").reshape(-1, n)
+    assert (x0 >= lo).all() and (x0 <= up).all()
+    w = model_from(a, shape, bounds=bounds)
+    for _ in range(gens):
+        a.iterate()
+        w.iterate(sm.TableSource(a.get_state("draws"), n, npinit))
+    assert min(w.repairs.values()) >= 3, w.repairs
+    # ---- the walk
+    g = make(hip, shape, bounds=bounds, seed=seed, record_draws=True)
+    m = model_from(g, shape, bounds=bounds)
+    same(g, m, "init")
+    for it in range(1, gens + 1):
+        g.iterate()
+        m.iterate(sm.TableSource(g.get_state("draws"), n, npinit))
+        same(g, m, "generation %d" % it)
+        x = g.get_state("x").reshape(-1, n)
+        assert (x >= lo).all() and (x <= up).all()
+    assert m.repairs == w.repairs
 
 
 def test_the_fused_kernel_and_the_phase_path_agree(hip):

@@ -28,6 +28,13 @@ def steps(golden):
     return sm.load_steps(golden)
 
 
+@pytest.fixture(scope="module")
+def percoord():
+    """one short record under bounds that differ in every coordinate (tests/_boxes.py): its "box" is "percoord" """
+    with open(os.path.join(ROOT, "tests", "golden", "ssde_percoord.json")) as fh:
+        return sm.load_steps(json.load(fh))
+
+
 def same_bits(a, b):
     a, b = np.asarray(a, float), np.asarray(b, float)
     return a.shape == b.shape and a.tobytes() == b.tobytes()
@@ -46,8 +53,33 @@ def test_fixture_shapes(steps):
         assert r["max_attempts"] <= 8 and (r["min_gap"] >= 1e-6 or r["n"] <= 2)
 
 
-def test_model_replays_the_recorded_generations_bit_for_bit(steps):
-    for rec in steps:
+def test_the_percoord_record_starts_with_opposites_and_redraws(percoord):
+    """the record that pins the model's box rule under bounds that differ in every coordinate: it starts with
+    usede (points and their opposites lower + upper - x: test_model_reproduces_init_from_the_words holds the
+    model's start to the record bit for bit), a redraw happens, and every evaluated point lies in its
+    coordinate's interval"""
+    (rec,) = percoord
+    n, npinit = rec["n"], rec["npinit"]
+    assert n <= 12 and len(rec["states"]) <= 5 and rec["usede"] == 1 and "de_redraw" in rec["events"]
+    # the witness that the box binds: coordinates the model redrew past each bound while it replays the record
+    m = sm.model_of(rec, chol_model.objective(rec["objective"], n))
+    m.start(rec["init"]["x"].reshape(npinit, n), rec["init"]["f"], fev=rec["init"]["fev"])
+    have, saved = False, 0.
+    for st in rec["states"]:
+        w = jm.Words(st["words"])
+        w.have, w.saved = have, saved
+        m.iterate(sm.WordsSource(w, n, npinit))
+        have, saved = w.have, w.saved
+    assert m.repairs == rec["repairs"] and min(m.repairs.values()) >= 3, m.repairs
+    lo, up = (np.asarray(v) for v in sm.box_of(rec))
+    X0 = rec["init"]["x"].reshape(-1, n)
+    assert (X0 >= lo).all() and (X0 <= up).all()
+    for st in rec["states"]:
+        assert (st["pts"] >= lo).all() and (st["pts"] <= up).all()
+
+
+def test_model_replays_the_recorded_generations_bit_for_bit(steps, percoord):
+    for rec in steps + percoord:
         n, npinit = rec["n"], rec["npinit"]
         m = sm.model_of(rec, chol_model.objective(rec["objective"], n))
         m.trace = True
@@ -69,8 +101,8 @@ def test_model_replays_the_recorded_generations_bit_for_bit(steps):
             assert same_bits([p for p, _ in m.points], st["pts"]) and same_bits([v for _, v in m.points], st["vals"])
 
 
-def test_model_reproduces_init_from_the_words(steps):
-    for rec in steps:
+def test_model_reproduces_init_from_the_words(steps, percoord):
+    for rec in steps + percoord:
         m = sm.model_of(rec, chol_model.objective(rec["objective"], rec["n"]))
         w = sm.Mt19937Words(rec["seed"])
         m.init_reference(w)
