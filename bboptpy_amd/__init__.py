@@ -10,8 +10,9 @@ from .objectives import vectorized, DeviceObjective
 from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, CMAES,
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
                            SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES,
-                           SpiralSearch, NSHS, LmCMAES, xNES, AMALGAM, SLPSO, CRS, SSDE, ACD, Mayfly, PIKAIA)
+                           SpiralSearch, NSHS, LmCMAES, xNES, AMALGAM, SLPSO, CRS, SSDE, ACD, Mayfly, PIKAIA,
+                           NelderMead)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "PIKAIA", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "PIKAIA", "NelderMead", "objectives",
            "vectorized", "DeviceObjective"]

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
     ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
-    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA = range(26)
+    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA, ALGO_NELDER_MEAD = range(27)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -42,6 +42,10 @@ CRS_PHASE_ADVANCE, CRS_PHASE_EVALUATE, CRS_PHASE_ABSORB = range(3)
 SSDE_PHASE_ADVANCE, SSDE_PHASE_EVALUATE, SSDE_PHASE_ABSORB = range(3)
 # bbo_acd_phase
 ACD_PHASE_ADVANCE, ACD_PHASE_EVALUATE, ACD_PHASE_ABSORB = range(3)
+# bbo_nm_phase
+NM_PHASE_ADVANCE, NM_PHASE_EVALUATE, NM_PHASE_ABSORB = range(3)
+# NelderMead "flag": the factorial test passed, mfev < fev
+NM_FLAG_CONVERGED, NM_FLAG_BUDGET = 1, 2
 # ACD "flag" and "rule"
 ACD_FLAG_CONVERGED, ACD_FLAG_BUDGET = 1, 2
 ACD_RULE_FTOL, ACD_RULE_XTOL = 1, 2
@@ -156,6 +160,12 @@ class PikaiaParams(C.Structure):
         + [(k, C.c_int) for k in ("imut", "irep", "ielite", "repair", "raw", "substream")]
 
 
+class NmParams(C.Structure):
+    """bbo_nm_params: the arguments of NelderMead that bbo_params has no field for"""
+    _fields_ = [("minit", C.c_int), ("pinit", C.c_int), ("checkev", C.c_int), ("eps", C.c_double),
+                ("repair", C.c_int), ("speculate", C.c_int), ("lds", C.c_int), ("substream", C.c_int)]
+
+
 class Objective(C.Structure):
     _fields_ = [("kind", C.c_int), ("builtin", C.c_int), ("scalar", SCALAR_FN),
                 ("batch", BATCH_FN), ("user", C.c_void_p)]
@@ -225,6 +235,7 @@ EXTENSIONS = {
     "acd": (AcdParams, True, {}),
     "mayfly": (MayflyParams, False, {"draws": _TABLE}),
     "pikaia": (PikaiaParams, False, {"draws": _TABLE}),
+    "nm": (NmParams, True, {}),
 }
 
 

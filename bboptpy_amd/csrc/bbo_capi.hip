@@ -17,6 +17,7 @@
 #include "bbo_acd.hpp"
 #include "bbo_mayfly.hpp"
 #include "bbo_pikaia.hpp"
+#include "bbo_nm.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -42,6 +43,7 @@ Optimizer* make_ssde_engine(const bbo_params &p);     // bbo_ssde.hip
 Optimizer* make_acd_engine(const bbo_params &p);      // bbo_acd.hip
 Optimizer* make_mayfly_engine(const bbo_params &p);   // bbo_mayfly.hip
 Optimizer* make_pikaia_engine(const bbo_params &p);   // bbo_pikaia.hip
+Optimizer* make_nm_engine(const bbo_params &p);       // bbo_nm.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 void probe_objective(int obj, int form, int n, int rows, const double *X, double *f_out);   // bbo_probe.hip
 }
@@ -153,6 +155,7 @@ const struct {
     { BBO_ALGO_SLPSO, bbo::make_slpso_engine }, { BBO_ALGO_CRS, bbo::make_crs_engine },
     { BBO_ALGO_SSDE, bbo::make_ssde_engine }, { BBO_ALGO_ACD, bbo::make_acd_engine },
     { BBO_ALGO_MAYFLY, bbo::make_mayfly_engine }, { BBO_ALGO_PIKAIA, bbo::make_pikaia_engine },
+    { BBO_ALGO_NELDER_MEAD, bbo::make_nm_engine },
 };
 
 bbo::ObjectiveSpec to_spec(const bbo_objective *o)
@@ -270,6 +273,7 @@ void bbo_params_default(bbo_params *p, int algo)
     if (algo == BBO_ALGO_SPIRAL) p->np = 20;   /* py/multivariate_py.cpp:348 */
     if (algo == BBO_ALGO_NSHS || algo == BBO_ALGO_CRS) p->poll_every = 0;   /* the engine's own chunk: iterations, not generations */
     if (algo == BBO_ALGO_ACD) p->poll_every = 0;    /* one sweep of n coordinate steps */
+    if (algo == BBO_ALGO_NELDER_MEAD) p->poll_every = 0;    /* the engine's own chunk of simplex steps */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -812,6 +816,29 @@ int bbo_pikaia_configure(bbo_handle h, const bbo_pikaia_params *p)
 int bbo_pikaia_inject_draws(bbo_handle h, const double *table, int count)
 {
     return guarded(h, [&] { engine_of<bbo::PikaiaEngine>(h)->inject_draws(table, count); });
+}
+
+void bbo_nm_params_default(bbo_nm_params *p)
+{
+    if (!p) return;
+    p->minit = 1;       /* py/multivariate_py.cpp:307-337: spendley, mehta2019_refined */
+    p->pinit = 3;
+    p->checkev = 10;
+    p->eps = 1e-3;
+    p->repair = 0;
+    p->speculate = 0;
+    p->lds = -1;
+    p->substream = 0;
+}
+
+int bbo_nm_configure(bbo_handle h, const bbo_nm_params *p)
+{
+    return configure_of<bbo::NmEngine>(h, p, "bbo_nm_configure");
+}
+
+int bbo_nm_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { engine_of<bbo::NmEngine>(h)->phase(phase); });
 }
 
 // diagnostics: no handle, so the message is the one of bbo_last_error(NULL)

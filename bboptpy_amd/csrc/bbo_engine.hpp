@@ -184,12 +184,16 @@ struct DrawTables {
 };
 
 // What a population has pending for a host objective: `count` points, rows of ld doubles from
-// cand[off] on, whose values go to value[p * count ...].
+// cand[off] on, whose values go to value[p * count ...] (to value[value_off ...] where the engine's
+// batches differ in length).  With `stop_below` the batch is a sequential search: the first value
+// below it is the last point the callable sees, the values behind it are +inf.
 struct PendingPoints {
     const DevBuf<double> *cand;
     size_t off;
     int count, ld;
     DevBuf<double> *value;
+    long long value_off = -1;
+    const double *stop_below = nullptr;
 };
 
 // Scal: the engine's per-population scalars; the base reads its `stop`, `fev` and `conv` (and
@@ -437,10 +441,15 @@ protected:
             xh.resize((size_t) pt.count * pt.ld);
             fh.assign(pt.count, 0.);
             pt.cand->download(xh.data(), xh.size(), pt.off);
-            for (int i = 0; i < pt.count; i++)
+            for (int i = 0; i < pt.count; i++) {
                 obj_.eval_host(xh.data() + (size_t) i * pt.ld, 1, n, pt.ld, &fh[i]);
+                if (pt.stop_below && fh[i] < *pt.stop_below) {
+                    std::fill(fh.begin() + i + 1, fh.end(), std::numeric_limits<double>::infinity());
+                    break;
+                }
+            }
             nan_to_inf(fh.data(), pt.count);
-            pt.value->upload(fh.data(), pt.count, (size_t) p * pt.count);
+            pt.value->upload(fh.data(), pt.count, pt.value_off >= 0 ? (size_t) pt.value_off : (size_t) p * pt.count);
         }
     }
 

@@ -61,7 +61,8 @@ enum Stream : uint32_t {
     STREAM_MAYFLY_Z = 42,
     STREAM_PIKAIA_INIT = 43,
     STREAM_PIKAIA_MATE = 44,
-    STREAM_PIKAIA_LOCUS = 45
+    STREAM_PIKAIA_LOCUS = 45,
+    STREAM_NM_INIT = 46
 };
 
 struct u32x4 {

@@ -1339,6 +1339,98 @@ class PIKAIA(MultivariateSearch):
         self._inject("bbo_pikaia_inject_draws", table)
 
 
+class NelderMead(MultivariateSearch):
+    """NelderMead(mfev, tol, rad0, minit=NelderMead.spendley, pinit=NelderMead.mehta2019_refined, checkev=10,
+    eps=1e-3) -- :307-337 (the simplex search of Nelder & Mead as O'Neill's AS 47 with restarts, the adaptive
+    coefficients of Gao & Han 2012 and Mehta 2020, four initial simplexes; nelder_mead.cpp).  One workgroup per
+    simplex, a lane per coordinate: `populations=P` starts P independent searches from the P rows of `guess`, a
+    multi-start the reference has no counterpart for.  n is at most 128.  The bounds are read by minit=random
+    alone (which needs a finite box); the search ignores them, as in the reference.
+    optimize() is the reference's: init() and nelmin() whole -- the steps while n_evals < mfev and the stop test
+    (every checkev steps) has not fired, the factorial test of 2 n probes at xmin[i] +- rad0 eps, a restart from
+    the first probe that improved -- and returns xmin as nelmin() leaves it, converged = the factorial test
+    passed.  Reproduced literally: the centroid summed afresh every step, first maximum / first minimum on ties,
+    the in-place shrink that moves the best row too, the refused outside contraction that stores pstar with
+    the value of the contracted point (nelder_mead.cpp:195-197; repair=True, keyword-only, stores its own), the
+    drift the probes' restore leaves in xmin.
+    Departure: the reference's step protocol is broken (its init() builds no simplex, so iterate() after
+    initialize() walks zeros, and solution() returns a scratch vector).  Here initialize() builds and evaluates
+    the first simplex as nelmin()'s first pass does (n_evals = n + 1), iterate() is one iterate() of the
+    reference from there, solution() gives the best row, n_evals and the stop test's verdict of the last step.
+    run(g) counts simplex steps and is nelmin() for up to g of them.  get_state("flag") is 1 converged, 2 budget;
+    "branch" is the last step's path (1 expansion kept, 2 expansion refused, 3 reflection, 4 inside contraction,
+    5 shrink, 6 outside contraction, 7 outside contraction refused).  A NaN value counts as +inf.
+    Extensions, keyword-only: `repair`; `lds=True / False` keeps the simplex of a launch in LDS / in HBM (same results;
+    the default chooses: HBM only at n near 128 with thousands of populations, where it was measured faster); `substream=s` lets population p draw minit=random from sub-stream s + p; `speculate` (pstar and the
+    three possible second points of a step evaluated at once on four wavefronts) was built, bit-identical, measured
+    slower at 1, 256 and 4096 populations alike and dropped: only False is accepted."""
+    _algo = _ffi.ALGO_NELDER_MEAD
+    _extension = "nm"
+    _accepts_program = False
+    MAX_N = 128
+
+    class NelderMead_SimplexInit(enum.IntEnum):
+        """NelderMead::simplex_initializer, bound with export_values (:310-317)"""
+        coordinate_axis = 0
+        spendley = 1
+        pfeffer = 2
+        random = 3
+
+    class NelderMead_ParamInit(enum.IntEnum):
+        """NelderMead::parameter_initializer, bound with export_values (:319-328)"""
+        original = 0
+        gao2010 = 1
+        mehta2019_crude = 2
+        mehta2019_refined = 3
+
+    coordinate_axis, spendley, pfeffer, random = (NelderMead_SimplexInit.coordinate_axis,
+                                                  NelderMead_SimplexInit.spendley, NelderMead_SimplexInit.pfeffer,
+                                                  NelderMead_SimplexInit.random)
+    original, gao2010, mehta2019_crude, mehta2019_refined = (NelderMead_ParamInit.original, NelderMead_ParamInit.gao2010,
+                                                             NelderMead_ParamInit.mehta2019_crude,
+                                                             NelderMead_ParamInit.mehta2019_refined)
+
+    def __init__(self, mfev, tol, rad0, minit=NelderMead_SimplexInit.spendley,
+                 pinit=NelderMead_ParamInit.mehta2019_refined, checkev=10, eps=1e-3, *, repair=False,
+                 speculate=False, lds=None, substream=0, **ext):
+        super().__init__(**ext)
+        if speculate:
+            raise ValueError("NelderMead: the speculative step was measured and dropped; speculate must be False")
+        if int(checkev) < 1:
+            raise ValueError("NelderMead: checkev must be >= 1")
+        if not _np.isfinite(float(rad0)):
+            raise ValueError("NelderMead: rad0 must be finite")
+        if not _np.isfinite(float(eps)):
+            raise ValueError("NelderMead: eps must be finite")
+        if int(mfev) < 1:
+            raise ValueError("NelderMead: mfev must be positive")
+        p = self._params
+        p.mfev, p.tol, p.sigma0 = int(mfev), float(tol), float(rad0)    # (rad0 travels in `sigma0`)
+        s = self._nm = _ffi.NmParams()
+        s.minit, s.pinit = int(self.NelderMead_SimplexInit(minit)), int(self.NelderMead_ParamInit(pinit))
+        s.checkev, s.eps = int(checkev), float(eps)
+        s.repair, s.speculate, s.substream = int(bool(repair)), 0, int(substream)
+        s.lds = -1 if lds is None else int(bool(lds))
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("NelderMead: dimension must be in [1, %d]" % self.MAX_N)
+        if self._nm.minit == int(self.NelderMead_SimplexInit.random):
+            self._require_finite_box(n, lower, upper, "NelderMead: minit = random draws the simplex from [lower, upper]")
+        return n, lower, upper, guess
+
+    def phase(self, which):
+        """a step from batch to batch of evaluations: 0 advance to the next pending batch ("pending" points: one,
+        or the n + 1 rows of a shrunk simplex), 1 evaluate it ("value"), 2 absorb the values and advance to the
+        next batch of the same step.  Phases 0 and 2 return the number of populations that have a batch pending;
+        the step is complete when it is 0."""
+        self._phase(which)
+        if int(which) == 1:
+            return None
+        return self._pending()
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

@@ -67,7 +67,8 @@ typedef enum {
     BBO_ALGO_SSDE = 22,        /* SSDESearch   src/multivariate/de/ssde.h             */
     BBO_ALGO_ACD = 23,         /* ACD          src/multivariate/acd/acd.h             */
     BBO_ALGO_MAYFLY = 24,      /* MayflySearch src/multivariate/mayfly/mayfly.h       */
-    BBO_ALGO_PIKAIA = 25       /* PikaiaSearch src/multivariate/pikaia/pikaia.h       */
+    BBO_ALGO_PIKAIA = 25,      /* PikaiaSearch src/multivariate/pikaia/pikaia.h       */
+    BBO_ALGO_NELDER_MEAD = 26  /* NelderMead   src/multivariate/simplex/nelder_mead.h */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -784,6 +785,47 @@ typedef struct {
 void bbo_pikaia_params_default(bbo_pikaia_params *p);   /* 0.85, 0.005, 0.0005, 0.25, 1., 2, 1, 0, 0, 0, 0 */
 int bbo_pikaia_configure(bbo_handle h, const bbo_pikaia_params *p);
 int bbo_pikaia_inject_draws(bbo_handle h, const double *table, int count);
+
+/* ---- NelderMead (BBO_ALGO_NELDER_MEAD): NelderMead(mfev,tol,rad0,minit=spendley,pinit=mehta2019_refined,
+ * checkev=10,eps=1e-3)  py/multivariate_py.cpp:307-337, the simplex search of Nelder & Mead as O'Neill's
+ * AS 47 with restarts, the adaptive coefficients of Gao & Han 2012 and Mehta 2020 and four initial simplexes
+ * (nelder_mead.cpp).  mfev and tol travel in bbo_params, rad0 in `sigma0`, the rest here.  One workgroup per
+ * population, a lane per coordinate; a multi-start is `populations` rows of `guess`.  Limits: n in [1, 128],
+ * checkev >= 1, rad0 and eps finite; minit = random (3) draws the simplex from [lower, upper] and needs a
+ * finite box, nothing else reads the bounds.  bbo_init refuses an objective program (BBO_ERR_ARG each).
+ * bbo_nm_configure is legal between bbo_create and bbo_init.  No restart base, not sharded over devices.
+ * Departure from the reference, whose step protocol is broken (its init() builds no simplex, so iterate()
+ * after it walks zeros, and solution() returns the scratch vector of the shrink): bbo_init builds and
+ * evaluates the first simplex as nelmin()'s first pass does (fev = n + 1), one bbo_iterate is one iterate()
+ * of the reference from there (the shrink's n + 1 evaluations included, no stop flag, no factorial test) and
+ * bbo_solution gives row ilo, fev and the conv of the last step.  bbo_run counts simplex steps and is
+ * nelmin(): the steps while fev < mfev and not converged, then the factorial test (2 n probes at xmin[i] +-
+ * step[i] eps, counted up to and including the first below ynl, the coordinates restored by += del, -= 2 del,
+ * += del as the reference does), then the restart from the probe that improved or "flag" 1; "flag" 2 where
+ * mfev < fev.  bbo_optimize is bbo_init + that, whole, and returns "xmin" as nelmin() leaves it.
+ * Reproduced: the centroid is summed over all n + 1 rows in row order, less row ihi, divided by n, every step;
+ * ihi is the first maximum, ilo the first minimum; the outside contraction that is refused stores pstar with
+ * the value y2star (nelder_mead.cpp:195-197; repair = 1 stores ystar); the shrink runs in place row after
+ * row, so row ilo itself moves unless scoef = 0.5 and the rows behind it read the moved one; a shrink
+ * returns before the stop test's bookkeeping; the stop test compares the undivided sum of squares with
+ * tol^2 n every checkev steps while fev <= mfev.  speculate = 1 (pstar and the three possible second
+ * points of a step evaluated at once on four wavefronts) was built, bit-identical, measured slower at 1, 256 and
+ * 4096 populations alike and dropped: bbo_nm_configure refuses it.  lds = 1 keeps the simplex in LDS over a launch,
+ * 0 in HBM; -1 (the default) takes HBM where the simplex leaves one workgroup per CU in LDS and there are at least
+ * four populations per CU, as measured; the state does not depend on it.  substream: population p draws minit = random from sub-stream substream + p.
+ * bbo_nm_phase walks with a host objective's granularity: 0 advance to the next pending batch ("pending"
+ * points: 1, or n + 1 rows of the simplex, or 2 n probes), 1 evaluate it, 2 absorb the values and advance.
+ * A host objective sees exactly the reference's points in its order, the factorial probes up to the first
+ * that improved.  A NaN value counts as +inf.
+ * Keys: "p" ((n + 1) x n) "y" "ilo" "ihi" (0-based) "ylo" "ynl" "jcount" "fev" "del" "start" "xmin" "step"
+ * "conv" "flag" "pending" "stage" "coef" (ccoef, ecoef, rcoef, scoef) "branch" (the last step: 1 expansion
+ * kept, 2 expansion refused, 3 reflection, 4 inside contraction, 5 shrink, 6 outside contraction, 7 outside
+ * contraction refused) "restarts" "it" "cand" "value" "lds".  Writable: "p" "y" "ilo" "ylo" "jcount" "fev"
+ * "start" "del" "value" "lds"; nothing is evaluated. */
+typedef struct { int minit, pinit, checkev; double eps; int repair, speculate, lds, substream; } bbo_nm_params;
+void bbo_nm_params_default(bbo_nm_params *p);   /* 1, 3, 10, 1e-3, 0, 0, -1, 0 */
+int bbo_nm_configure(bbo_handle h, const bbo_nm_params *p);
+int bbo_nm_phase(bbo_handle h, int phase);
 
 /* ---- diagnostics -------------------------------------------------------------------------------
  * bbo_probe_objective: built-in `objective` at `rows` points of `n` coordinates (X, rows x n, host
