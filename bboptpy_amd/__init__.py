@@ -11,8 +11,8 @@ from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, 
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
                            SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES,
                            SpiralSearch, NSHS, LmCMAES, xNES, AMALGAM, SLPSO, CRS, SSDE, ACD, Mayfly, PIKAIA,
-                           NelderMead)
+                           NelderMead, Rosenbrock)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "PIKAIA", "NelderMead", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "PIKAIA", "NelderMead", "Rosenbrock", "objectives",
            "vectorized", "DeviceObjective"]

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
     ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
-    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA, ALGO_NELDER_MEAD = range(27)
+    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA, ALGO_NELDER_MEAD, ALGO_ROSENBROCK = range(28)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -46,6 +46,10 @@ ACD_PHASE_ADVANCE, ACD_PHASE_EVALUATE, ACD_PHASE_ABSORB = range(3)
 NM_PHASE_ADVANCE, NM_PHASE_EVALUATE, NM_PHASE_ABSORB = range(3)
 # NelderMead "flag": the factorial test passed, mfev < fev
 NM_FLAG_CONVERGED, NM_FLAG_BUDGET = 1, 2
+# bbo_rosen_phase
+ROSEN_PHASE_ADVANCE, ROSEN_PHASE_EVALUATE, ROSEN_PHASE_ABSORB = range(3)
+# Rosenbrock "flag": stepi <= tol, the budget
+ROSEN_FLAG_CONVERGED, ROSEN_FLAG_BUDGET = 1, 2
 # ACD "flag" and "rule"
 ACD_FLAG_CONVERGED, ACD_FLAG_BUDGET = 1, 2
 ACD_RULE_FTOL, ACD_RULE_XTOL = 1, 2
@@ -166,6 +170,11 @@ class NmParams(C.Structure):
                 ("repair", C.c_int), ("speculate", C.c_int), ("lds", C.c_int), ("substream", C.c_int)]
 
 
+class RosenParams(C.Structure):
+    """bbo_rosen_params: the arguments of Rosenbrock that bbo_params has no field for"""
+    _fields_ = [("decf", C.c_double), ("repair", C.c_int), ("wide", C.c_int), ("substream", C.c_int)]
+
+
 class Objective(C.Structure):
     _fields_ = [("kind", C.c_int), ("builtin", C.c_int), ("scalar", SCALAR_FN),
                 ("batch", BATCH_FN), ("user", C.c_void_p)]
@@ -236,6 +245,7 @@ EXTENSIONS = {
     "mayfly": (MayflyParams, False, {"draws": _TABLE}),
     "pikaia": (PikaiaParams, False, {"draws": _TABLE}),
     "nm": (NmParams, True, {}),
+    "rosen": (RosenParams, True, {}),
 }
 
 

@@ -18,6 +18,7 @@
 #include "bbo_mayfly.hpp"
 #include "bbo_pikaia.hpp"
 #include "bbo_nm.hpp"
+#include "bbo_rosen.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -44,6 +45,7 @@ Optimizer* make_acd_engine(const bbo_params &p);      // bbo_acd.hip
 Optimizer* make_mayfly_engine(const bbo_params &p);   // bbo_mayfly.hip
 Optimizer* make_pikaia_engine(const bbo_params &p);   // bbo_pikaia.hip
 Optimizer* make_nm_engine(const bbo_params &p);       // bbo_nm.hip
+Optimizer* make_rosen_engine(const bbo_params &p);    // bbo_rosen.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
 void probe_objective(int obj, int form, int n, int rows, const double *X, double *f_out);   // bbo_probe.hip
 }
@@ -155,7 +157,7 @@ const struct {
     { BBO_ALGO_SLPSO, bbo::make_slpso_engine }, { BBO_ALGO_CRS, bbo::make_crs_engine },
     { BBO_ALGO_SSDE, bbo::make_ssde_engine }, { BBO_ALGO_ACD, bbo::make_acd_engine },
     { BBO_ALGO_MAYFLY, bbo::make_mayfly_engine }, { BBO_ALGO_PIKAIA, bbo::make_pikaia_engine },
-    { BBO_ALGO_NELDER_MEAD, bbo::make_nm_engine },
+    { BBO_ALGO_NELDER_MEAD, bbo::make_nm_engine }, { BBO_ALGO_ROSENBROCK, bbo::make_rosen_engine },
 };
 
 bbo::ObjectiveSpec to_spec(const bbo_objective *o)
@@ -274,6 +276,7 @@ void bbo_params_default(bbo_params *p, int algo)
     if (algo == BBO_ALGO_NSHS || algo == BBO_ALGO_CRS) p->poll_every = 0;   /* the engine's own chunk: iterations, not generations */
     if (algo == BBO_ALGO_ACD) p->poll_every = 0;    /* one sweep of n coordinate steps */
     if (algo == BBO_ALGO_NELDER_MEAD) p->poll_every = 0;    /* the engine's own chunk of simplex steps */
+    if (algo == BBO_ALGO_ROSENBROCK) p->poll_every = 0;     /* the engine's own chunk of line searches */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -839,6 +842,25 @@ int bbo_nm_configure(bbo_handle h, const bbo_nm_params *p)
 int bbo_nm_phase(bbo_handle h, int phase)
 {
     return guarded(h, [&] { engine_of<bbo::NmEngine>(h)->phase(phase); });
+}
+
+void bbo_rosen_params_default(bbo_rosen_params *p)
+{
+    if (!p) return;
+    p->decf = 0.1;      /* rosenbrock.h:55 */
+    p->repair = 0;
+    p->wide = -1;
+    p->substream = 0;
+}
+
+int bbo_rosen_configure(bbo_handle h, const bbo_rosen_params *p)
+{
+    return configure_of<bbo::RosenEngine>(h, p, "bbo_rosen_configure");
+}
+
+int bbo_rosen_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { engine_of<bbo::RosenEngine>(h)->phase(phase); });
 }
 
 // diagnostics: no handle, so the message is the one of bbo_last_error(NULL)

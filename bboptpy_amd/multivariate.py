@@ -1431,6 +1431,69 @@ class NelderMead(MultivariateSearch):
         return self._pending()
 
 
+class Rosenbrock(MultivariateSearch):
+    """Rosenbrock(mfev, tol, step0, decf=0.1) -- the constructor of the reference's Rosenbrock (rosenbrock.h:55),
+    which it binds to no Python class: Rosenbrock's rotating-axes search with the line search of Davies, Swann and
+    Campey (doubling of the step, then a Lagrange quadratic through three of four points) and Palmer's
+    orthogonalisation of the directions (rosenbrock.cpp).  A local method that draws no random number.  One
+    workgroup per search: `populations=P` starts P independent searches from the P rows of `guess`, a multi-start
+    the reference has no counterpart for.  n is at most 128.  The bounds are stored and never read, as in the
+    reference, so no finite box is required.  step0 and decf must not be 0 and tol not negative: with a step of 0
+    a search would double until the budget ends it.  (The objective of the same name is bb.objectives.rosenbrock.)
+    optimize() is the reference's: init() and iterate() until it ends -- converged when the step, multiplied by
+    decf whenever a stage moved less than the step, is at most tol; on the budget when n_evals >= mfev is met inside
+    the doubling loop or behind a stage, so n_evals passes mfev by a few evaluations.
+    **On a budget exit optimize() returns the ZERO vector**: the reference writes its result only when it converges
+    (rosenbrock.cpp:197), and this is reproduced; `repair=True` (keyword-only) returns the end point of the last
+    completed line search where the run did not converge, and changes nothing else.
+    initialize() / iterate() / solution() are the reference's: initialize() evaluates nothing, one iterate() is one
+    line search (about eight evaluations) with its bookkeeping, solution() is the same vector as optimize()'s,
+    under the same `repair` rule.  run(g) counts line searches.  get_state("flag") is 1 converged, 2 budget;
+    "path" is the last search's path (direction 1 forward / 2 backward / 3 straight to the interpolation, rounds of
+    the doubling loop, imin, end 0 none / 1 kept / 2 restored / 3 budget).  A callable is called exactly as often
+    as in the reference and in its order, the second call at x0 included.  Departure: a NaN value counts as +inf.
+    Extensions, keyword-only: `repair`; `wide=True / False` evaluates the points of a batch at once on a wavefront
+    each / in turn on one wavefront (same results; the default is True except at n <= 64 with at least four
+    populations per CU, as measured); `substream` is accepted
+    for symmetry with the other engines and unused."""
+    _algo = _ffi.ALGO_ROSENBROCK
+    _extension = "rosen"
+    _accepts_program = False
+    MAX_N = 128
+
+    def __init__(self, mfev, tol, step0, decf=0.1, *, repair=False, wide=None, substream=0, **ext):
+        super().__init__(**ext)
+        if int(mfev) < 1:
+            raise ValueError("Rosenbrock: mfev must be positive")
+        if not _np.isfinite(float(step0)) or float(step0) == 0.:
+            raise ValueError("Rosenbrock: step0 must be finite and not 0")
+        if not _np.isfinite(float(decf)) or float(decf) == 0.:
+            raise ValueError("Rosenbrock: decf must be finite and not 0")
+        if not float(tol) >= 0.:
+            raise ValueError("Rosenbrock: tol must be >= 0: with a step of 0 a search doubles until the budget ends it")
+        p = self._params
+        p.mfev, p.tol, p.sigma0 = int(mfev), float(tol), float(step0)    # (step0 travels in `sigma0`)
+        s = self._rosen = _ffi.RosenParams()
+        s.decf, s.repair, s.substream = float(decf), int(bool(repair)), int(substream)
+        s.wide = -1 if wide is None else int(bool(wide))
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("Rosenbrock: dimension must be in [1, %d]" % self.MAX_N)
+        return n, lower, upper, guess
+
+    def phase(self, which):
+        """a line search from batch to batch of evaluations: 0 advance to the next pending batch ("pending"
+        points: 2, 1 or 4), 1 evaluate it ("value"), 2 absorb the values and advance to the next batch of the same
+        search.  Phases 0 and 2 return the number of populations that have a batch pending; the search and its
+        bookkeeping are complete when it is 0."""
+        self._phase(which)
+        if int(which) == 1:
+            return None
+        return sum(int(self.get_state("pending", p)[0]) > 0 for p in range(self._params.populations))
+
+
 class APSO(MultivariateSearch):
     """APSO(mfev, tol, np, correct=True) -- :265-269"""
     _algo = _ffi.ALGO_APSO

@@ -68,7 +68,8 @@ typedef enum {
     BBO_ALGO_ACD = 23,         /* ACD          src/multivariate/acd/acd.h             */
     BBO_ALGO_MAYFLY = 24,      /* MayflySearch src/multivariate/mayfly/mayfly.h       */
     BBO_ALGO_PIKAIA = 25,      /* PikaiaSearch src/multivariate/pikaia/pikaia.h       */
-    BBO_ALGO_NELDER_MEAD = 26  /* NelderMead   src/multivariate/simplex/nelder_mead.h */
+    BBO_ALGO_NELDER_MEAD = 26, /* NelderMead   src/multivariate/simplex/nelder_mead.h */
+    BBO_ALGO_ROSENBROCK = 27   /* Rosenbrock   src/multivariate/rosenbrock/rosenbrock.h */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -826,6 +827,39 @@ typedef struct { int minit, pinit, checkev; double eps; int repair, speculate, l
 void bbo_nm_params_default(bbo_nm_params *p);   /* 1, 3, 10, 1e-3, 0, 0, -1, 0 */
 int bbo_nm_configure(bbo_handle h, const bbo_nm_params *p);
 int bbo_nm_phase(bbo_handle h, int phase);
+
+/* ---- Rosenbrock (BBO_ALGO_ROSENBROCK): Rosenbrock(mfev,tol,step0,decf=0.1)  rosenbrock.h:55, Rosenbrock's
+ * rotating-axes search with the line search of Davies, Swann and Campey (doubling, then a Lagrange quadratic
+ * through three of four points) and Palmer's orthogonalisation (rosenbrock.cpp; the reference binds it to no
+ * Python class).  mfev and tol travel in bbo_params, step0 in `sigma0`, decf here.  No random draw.  One workgroup
+ * per population; a multi-start is `populations` rows of `guess`.  Limits: n in [1, 128], step0 and decf finite and not 0, tol >= 0 (with a step of 0 the doubling loop
+ * of a search would end on the budget alone, inside one launch);
+ * the bounds are stored and never read.  bbo_init refuses an objective program (BBO_ERR_ARG each) and evaluates
+ * nothing.  bbo_rosen_configure is legal between bbo_create and bbo_init.  No restart base, not sharded.
+ * One bbo_iterate is one iterate() of the reference: a line search from x[i - 1] along v[i] into x[i], d[i] = the
+ * step taken, then i++, or the extra search along the stage's displacement, or the step test with the
+ * orthogonalisation or the shrink of the step.  bbo_run counts line searches.  bbo_optimize is init() + iterate()
+ * until _ierr >= 0 and returns _x1, WHICH ONLY A CONVERGED RUN WRITES: ON A BUDGET EXIT THE RESULT IS THE ZERO
+ * VECTOR, as in the reference (rosenbrock.cpp:197 is the only write).  repair = 1 returns the end point of the last
+ * completed line search, x[i - 1], where the run has not converged, and changes nothing else.  The budget is
+ * tested inside the doubling loop and behind a stage only, so n_evals passes mfev by a few evaluations.
+ * wide = 1 evaluates the points of a batch at once, a wavefront each (256 threads); 0 in turn on one wavefront;
+ * -1 (the default) takes 1 except at n <= 64 with at least four populations per CU, as measured (DESIGN.md
+ * section 3.20); the state does not depend on it.  substream is reserved (the method draws nothing).
+ * bbo_rosen_phase walks with a host objective's granularity: 0 advance to the next pending batch ("pending"
+ * points: 2 first, then 1 back, 1 per doubling, 4 for the interpolation, 1 final), 1 evaluate it, 2 absorb the
+ * values and advance.  A host objective sees exactly the reference's points in its order, the second call at x0
+ * included.  Departure: a NaN value counts as +inf.
+ * Keys: "x" ((n + 2) x n) "v" ((n + 2) x n) "d" (n + 2) "stepi" "i" "fev" "x1" "flag" (1 converged, 2 budget)
+ * "path" (the last search: direction 1 forward / 2 backward / 3 straight to the interpolation, rounds of the
+ * doubling loop, imin or -1, end 0 none / 1 kept / 2 restored / 3 budget) "fs" "pending" "value" "cand" (the pending
+ * batch; behind a search with a built-in the four interpolation points, whose values are "fs") "stage"
+ * "it" "orth" "orths" "walk_ticks" "orth_ticks" (ticks of the constant-rate clock inside rosen_walk, and inside its
+ * orthogonalisations) "s" "fx0" "fx" (lineSearch()'s, the last values) "wide".  Writable: "x" "v" "d" "stepi" "i" "fev" "value" "wide"; nothing is evaluated. */
+typedef struct { double decf; int repair, wide, substream; } bbo_rosen_params;
+void bbo_rosen_params_default(bbo_rosen_params *p);   /* 0.1, 0, -1, 0 */
+int bbo_rosen_configure(bbo_handle h, const bbo_rosen_params *p);
+int bbo_rosen_phase(bbo_handle h, int phase);
 
 /* ---- diagnostics -------------------------------------------------------------------------------
  * bbo_probe_objective: built-in `objective` at `rows` points of `n` coordinates (X, rows x n, host
