@@ -11,8 +11,9 @@ from .multivariate import (MultivariateSolution, MultivariateSearch, BaseCMAES, 
                            ActiveCMAES, SepCMAES, CholeskyCMAES, IPopCMAES, BiPopCMAES, JADE, SHADE,
                            SANSDE, APSO, CSO, CCPSO, JAYA, DSA, HEES,
                            SpiralSearch, NSHS, LmCMAES, xNES, AMALGAM, SLPSO, CRS, SSDE, ACD, Mayfly, PIKAIA,
-                           NelderMead, Rosenbrock)
+                           NelderMead, Rosenbrock, BasinHopping, BasinHopping_StepStrategy,
+                           BasinHopping_AdaptStrategy)
 
 __all__ = ["MultivariateSolution", "MultivariateSearch", "BaseCMAES", "CMAES", "ActiveCMAES",
-           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "PIKAIA", "NelderMead", "Rosenbrock", "objectives",
+           "SepCMAES", "CholeskyCMAES", "IPopCMAES", "BiPopCMAES", "JADE", "SHADE", "SANSDE", "APSO", "CSO", "CCPSO", "JAYA", "DSA", "HEES", "SpiralSearch", "NSHS", "LmCMAES", "xNES", "AMALGAM", "SLPSO", "CRS", "SSDE", "ACD", "Mayfly", "PIKAIA", "NelderMead", "Rosenbrock", "BasinHopping", "BasinHopping_StepStrategy", "BasinHopping_AdaptStrategy", "objectives",
            "vectorized", "DeviceObjective"]

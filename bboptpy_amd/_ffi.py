@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libbbopt_hip.so")
 ALGO_CMAES, ALGO_ACTIVE_CMAES, ALGO_SHADE, ALGO_JADE, ALGO_APSO, ALGO_IPOP, ALGO_BIPOP, \
     ALGO_SEP_CMAES, ALGO_SANSDE, ALGO_CSO, ALGO_CCPSO, ALGO_CHOLESKY_CMAES, ALGO_JAYA, ALGO_DSA, \
     ALGO_HEES, ALGO_SPIRAL, ALGO_NSHS, ALGO_LM_CMAES, ALGO_XNES, ALGO_AMALGAM, ALGO_SLPSO, \
-    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA, ALGO_NELDER_MEAD, ALGO_ROSENBROCK = range(28)
+    ALGO_CRS, ALGO_SSDE, ALGO_ACD, ALGO_MAYFLY, ALGO_PIKAIA, ALGO_NELDER_MEAD, ALGO_ROSENBROCK, \
+    ALGO_BASIN_HOPPING = range(29)
 # bbo_objective_kind
 OBJ_BUILTIN, OBJ_SCALAR_CB, OBJ_BATCH_CB, OBJ_PROGRAM = 0, 1, 2, 3
 # bbo_status (the ones Python tells apart)
@@ -50,6 +51,10 @@ NM_FLAG_CONVERGED, NM_FLAG_BUDGET = 1, 2
 ROSEN_PHASE_ADVANCE, ROSEN_PHASE_EVALUATE, ROSEN_PHASE_ABSORB = range(3)
 # Rosenbrock "flag": stepi <= tol, the budget
 ROSEN_FLAG_CONVERGED, ROSEN_FLAG_BUDGET = 1, 2
+# bbo_bh_phase
+BH_PHASE_STEP, BH_PHASE_COLLECT, BH_PHASE_EVALUATE, BH_PHASE_DECIDE = range(4)
+# BasinHopping "flag": mit reached
+BH_FLAG_MIT = 2
 # ACD "flag" and "rule"
 ACD_FLAG_CONVERGED, ACD_FLAG_BUDGET = 1, 2
 ACD_RULE_FTOL, ACD_RULE_XTOL = 1, 2
@@ -175,6 +180,13 @@ class RosenParams(C.Structure):
     _fields_ = [("decf", C.c_double), ("repair", C.c_int), ("wide", C.c_int), ("substream", C.c_int)]
 
 
+class BhParams(C.Structure):
+    """bbo_bh_params: the step strategy and the arguments of BasinHopping"""
+    _fields_ = [("stepsize", C.c_double), ("adaptive", C.c_int), ("accept_rate", C.c_double), ("interval", C.c_int),
+                ("factor", C.c_double), ("temp", C.c_double)] \
+        + [(k, C.c_int) for k in ("mit", "print", "lockstep", "substream", "nstep0", "naccept0")]
+
+
 class Objective(C.Structure):
     _fields_ = [("kind", C.c_int), ("builtin", C.c_int), ("scalar", SCALAR_FN),
                 ("batch", BATCH_FN), ("user", C.c_void_p)]
@@ -198,6 +210,8 @@ CORE = {
     "bbo_params_default": ([C.POINTER(Params), _i], None),
     "bbo_create": ([C.POINTER(Params), C.POINTER(_h)], _i),
     "bbo_create_restart": ([C.POINTER(Params), _h, C.POINTER(_h)], _i),
+    "bbo_create_basin": ([C.POINTER(Params), _h, C.POINTER(_h)], _i),
+    "bbo_bh_draws": ([C.c_uint64, _i, _i, _i, _dp], _i),
     "bbo_destroy": ([_h], _i),
     "bbo_init": ([_h, _i, _dp, _dp, _dp, C.POINTER(Objective)], _i),
     "bbo_iterate": ([_h], _i),
@@ -246,6 +260,7 @@ EXTENSIONS = {
     "pikaia": (PikaiaParams, False, {"draws": _TABLE}),
     "nm": (NmParams, True, {}),
     "rosen": (RosenParams, True, {}),
+    "bh": (BhParams, True, {"draws": _TABLE}),
 }
 
 

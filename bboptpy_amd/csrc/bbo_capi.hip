@@ -19,6 +19,7 @@
 #include "bbo_pikaia.hpp"
 #include "bbo_nm.hpp"
 #include "bbo_rosen.hpp"
+#include "bbo_bh.hpp"
 
 #include <cstddef>
 #include <memory>
@@ -47,6 +48,7 @@ Optimizer* make_pikaia_engine(const bbo_params &p);   // bbo_pikaia.hip
 Optimizer* make_nm_engine(const bbo_params &p);       // bbo_nm.hip
 Optimizer* make_rosen_engine(const bbo_params &p);    // bbo_rosen.hip
 Optimizer* make_restart_driver(const bbo_params &p, Optimizer *base);   // bbo_restart.hip
+Optimizer* make_bh_engine(const bbo_params &p, Optimizer *minimizer);   // bbo_bh.hip
 void probe_objective(int obj, int form, int n, int rows, const double *X, double *f_out);   // bbo_probe.hip
 }
 
@@ -277,6 +279,7 @@ void bbo_params_default(bbo_params *p, int algo)
     if (algo == BBO_ALGO_ACD) p->poll_every = 0;    /* one sweep of n coordinate steps */
     if (algo == BBO_ALGO_NELDER_MEAD) p->poll_every = 0;    /* the engine's own chunk of simplex steps */
     if (algo == BBO_ALGO_ROSENBROCK) p->poll_every = 0;     /* the engine's own chunk of line searches */
+    if (algo == BBO_ALGO_BASIN_HOPPING) p->poll_every = 0;  /* the engine's own count of rounds */
     if (has_long_params(algo)) {               // (see PARAMS_BASE_BYTES)
         p->stol = 0.;
         p->ranked = 0;
@@ -313,6 +316,19 @@ int bbo_create_restart(const bbo_params *params, bbo_handle base, bbo_handle *ou
         h->algo = params->algo;
         const bbo_params own = own_copy(params);
         h->opt.reset(bbo::make_restart_driver(own, base->opt.get()));
+        *out = h.release();
+    });
+}
+
+int bbo_create_basin(const bbo_params *params, bbo_handle minimizer, bbo_handle *out)
+{
+    return created("bbo_create_basin", params && out && minimizer && minimizer->opt, [&] {
+        *out = nullptr;
+        if (params->algo != BBO_ALGO_BASIN_HOPPING)
+            throw bbo::Error(BBO_ERR_ARG, "bbo_create_basin: algo must be BBO_ALGO_BASIN_HOPPING");
+        std::unique_ptr<bbo_handle_s> h(new bbo_handle_s());
+        h->algo = params->algo;
+        h->opt.reset(bbo::make_bh_engine(own_copy(params), minimizer->opt.get()));
         *out = h.release();
     });
 }
@@ -861,6 +877,48 @@ int bbo_rosen_configure(bbo_handle h, const bbo_rosen_params *p)
 int bbo_rosen_phase(bbo_handle h, int phase)
 {
     return guarded(h, [&] { engine_of<bbo::RosenEngine>(h)->phase(phase); });
+}
+
+void bbo_bh_params_default(bbo_bh_params *p)
+{
+    if (!p) return;
+    /* py/multivariate_py.cpp:83-97: the adaptive strategy's and BasinHopping's defaults */
+    p->stepsize = 1.;
+    p->adaptive = 1;
+    p->accept_rate = 0.5;
+    p->interval = 5;
+    p->factor = 0.9;
+    p->temp = 1.;
+    p->mit = 99;
+    p->print = 1;
+    p->lockstep = -1;
+    p->substream = 0;
+    p->nstep0 = 0;
+    p->naccept0 = 0;
+}
+
+int bbo_bh_configure(bbo_handle h, const bbo_bh_params *p)
+{
+    return configure_of<bbo::BhEngine>(h, p, "bbo_bh_configure");
+}
+
+int bbo_bh_phase(bbo_handle h, int phase)
+{
+    return guarded(h, [&] { engine_of<bbo::BhEngine>(h)->phase(phase); });
+}
+
+int bbo_bh_inject_draws(bbo_handle h, const double *table, int count)
+{
+    return guarded(h, [&] { engine_of<bbo::BhEngine>(h)->inject_draws(table, count); });
+}
+
+int bbo_bh_draws(uint64_t seed, int substream, int hop, int n, double *out)
+{
+    return created("bbo_bh_draws", out != nullptr, [&] {
+        if (n < 1 || n > bbo::BH_MAX_N || hop < 0 || substream < 0 || substream >= (1 << 24))
+            throw bbo::Error(BBO_ERR_ARG, "bbo_bh_draws: n in [1, 128], hop >= 0, substream in [0, 2^24)");
+        bbo::bh_draws_host(seed, substream, hop, n, out);
+    });
 }
 
 // diagnostics: no handle, so the message is the one of bbo_last_error(NULL)

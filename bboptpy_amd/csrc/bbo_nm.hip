@@ -154,11 +154,7 @@ void NmEngine::init(int n, const double *lower, const double *upper, const doubl
         y_.upload(z.data(), (size_t) P * (n + 1));
         std::vector<NmScal> sc(P);
         std::memset(sc.data(), 0, sizeof(NmScal) * P);
-        for (auto &s : sc) {                                        // :82-86
-            s.jcount = np_.checkev;
-            s.del = 1.;
-            s.stage = NM_BUILD;
-        }
+        for (auto &s : sc) s = nm_fresh_scal(np_.checkev);
         scal_.upload(sc.data(), P);
     }
 
@@ -169,6 +165,7 @@ void NmEngine::init(int n, const double *lower, const double *upper, const doubl
     d.lower = lower_.p; d.upper = upper_.p; d.aux = aux_.p; d.scal = scal_.p;
     if (c.lds) allow_walk_lds();
     inited_ = true;
+    inits_++;
 
     // the first simplex and its n + 1 values, as nelmin()'s first pass (:251-260): no step
     c.honor_stop = 0;

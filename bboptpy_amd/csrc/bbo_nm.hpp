@@ -61,6 +61,16 @@ struct NmScal {
     int jcount, kind, branch, restarts;
 };
 
+// the scalars of a fresh start (:82-86): what init() uploads and nm_rearm writes
+__host__ __device__ inline NmScal nm_fresh_scal(int checkev)
+{
+    NmScal s = {};
+    s.jcount = checkev;
+    s.del = 1.;
+    s.stage = NM_BUILD;
+    return s;
+}
+
 struct NmConst {
     int n, ld;
     int obj, mfev, honor_stop, npop;
@@ -82,6 +92,7 @@ struct NmDev {
 };
 
 class NmEngine: public WalkEngine<NmScal> {
+    friend class BhEngine;      // borrows the handle as its local minimiser (bbo_bh.hpp)
 public:
     static constexpr const char *HANDLE_NAME = "not a NelderMead handle";
     explicit NmEngine(const bbo_params &p);
@@ -110,6 +121,7 @@ private:
     void coefficients(int n);
 
     bbo_nm_params np_ {};
+    int inits_ = 0;          // bbo_init calls so far: a borrower notices a handle that was initialised behind its back
     NmConst c_ {};
     NmDev d_ {};
     DevBuf<double> P_, y_, start_, xmin_, step_, cand_, value_;

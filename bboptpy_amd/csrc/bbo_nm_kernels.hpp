@@ -27,6 +27,7 @@ __device__ inline double nm_value(const NmConst &c, const double *row, const dou
     return f != f ? NM_INF : f;
 }
 
+#ifndef BBO_WALK_DEVICE_FUNCTIONS_ONLY   // (bbo_bh.hip takes the value function and the re-arm, not the kernels)
 // grid (P), 64 threads (n <= 64) or 128; dynamic LDS: the simplex, (n + 1) ld doubles, under c.lds
 //   mode   NM_FUSED: evaluates inside and ends at the goal or a stop.  NM_ADVANCE: walks to the next batch
 //          of points, leaves them in `cand` (or in the simplex: a fresh or a shrunk one) and ends.
@@ -362,6 +363,21 @@ __global__ __launch_bounds__(NM_THREADS) void nm_walk(NmDev d, NmConst c, int mo
     for (int q = tid; q < n1; q += nt) d.y[(size_t) p * n1 + q] = ys[q];
     if (tid == 0) d.scal[p] = s;
 }
+#endif
+
+// A fresh start of population p at `from` (n doubles), by the workgroup that calls it: exactly the state init()
+// uploads -- start, xmin zero, the fresh scalars (del = 1 on step = rad0, stage NM_BUILD, jcount = checkev, the
+// counters and stop zero).  The simplex, y, cand and value are written by the walk before it reads them.  The
+// next launch of nm_walk under honor_stop builds the simplex and goes on as nelmin() does (BasinHopping's hops).
+__device__ inline void nm_rearm(const NmDev &d, const NmConst &c, int p, const double *from, int tid, int nt)
+{
+    const size_t pv = (size_t) p * c.ld;
+    for (int j = tid; j < c.ld; j += nt) {
+        d.start[pv + j] = j < c.n ? from[j] : 0.;
+        d.xmin[pv + j] = 0.;
+    }
+    if (tid == 0) d.scal[p] = nm_fresh_scal(c.checkev);
+}
 
 // where the pending batch of a population lies: rows of the simplex, or rows of cand
 __device__ inline const double *nm_pending_rows(const NmDev &d, const NmConst &c, int p, int stage)
@@ -371,6 +387,7 @@ __device__ inline const double *nm_pending_rows(const NmDev &d, const NmConst &c
     return stage == NM_WAIT_SECOND ? cand + c.ld : cand;
 }
 
+#ifndef BBO_WALK_DEVICE_FUNCTIONS_ONLY
 // the built-in at every population's pending batch (bbo_nm_phase 1).  grid (P), NM_THREADS threads
 __global__ __launch_bounds__(NM_THREADS) void nm_eval(NmDev d, NmConst c)
 {
@@ -384,5 +401,6 @@ __global__ __launch_bounds__(NM_THREADS) void nm_eval(NmDev d, NmConst c)
         if (lane == 0) d.value[(size_t) p * c.vs + r] = f;
     }
 }
+#endif
 
 } // namespace bbo

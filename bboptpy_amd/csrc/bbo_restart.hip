@@ -11,6 +11,7 @@
 // default run) drives the inner engine under the key seed + 0x9E3779B97F4A7C15 * r.
 #include "bbo_cma.hpp"
 #include "bbo_rng.hpp"
+#include "bbo_tabular.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -268,26 +269,9 @@ private:
                     false);
     }
 
-    // the Tabular row format of src/tabular.hpp:65-77 (values at max_digits10)
-    static std::string istr(long v) { return std::to_string(v); }
-    static std::string dstr(double v)
-    {
-        char buf[64];
-        snprintf(buf, sizeof(buf), "%.17g", v);
-        return buf;
-    }
-    void print_row(const std::vector<std::string> &cells, bool header)
-    {
-        int sum = 0;
-        for (size_t i = 0; i < cells.size(); i++) {
-            printf(" | %*s", widths_[i], cells[i].c_str());
-            sum += widths_[i];
-        }
-        printf(" | \n");
-        if (header)
-            printf(" |%s| \n", std::string(sum + 3 * ((int) cells.size() - 1) + 2, '=').c_str());
-        fflush(stdout);
-    }
+    static std::string istr(long v) { return tabular_int(v); }
+    static std::string dstr(double v) { return tabular_double(v); }
+    void print_row(const std::vector<std::string> &cells, bool header) { tabular_row(widths_, cells, header); }
 
     bbo_params params_;
     CmaEngine *base_;

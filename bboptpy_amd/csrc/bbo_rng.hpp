@@ -62,7 +62,9 @@ enum Stream : uint32_t {
     STREAM_PIKAIA_INIT = 43,
     STREAM_PIKAIA_MATE = 44,
     STREAM_PIKAIA_LOCUS = 45,
-    STREAM_NM_INIT = 46
+    STREAM_NM_INIT = 46,
+    STREAM_BH_STEP = 47,
+    STREAM_BH_ACCEPT = 48
 };
 
 struct u32x4 {

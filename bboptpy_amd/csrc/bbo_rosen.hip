@@ -70,6 +70,7 @@ void RosenEngine::init(int n, const double *lower, const double *upper, const do
     }
     c.tol = params_.tol;
     c.decf = rp_.decf;
+    c.step0 = params_.sigma0;
     mid_generation_ = false;
 
     const size_t ld = c.ld, vec = (size_t) P * ld, mat = vec * (n + 2);
@@ -99,11 +100,7 @@ void RosenEngine::init(int n, const double *lower, const double *upper, const do
         value_.upload(z.data(), (size_t) P * ROSEN_BATCH);
         std::vector<RosenScal> sc(P);
         std::memset(sc.data(), 0, sizeof(RosenScal) * P);
-        for (auto &s : sc) {                                        // :85-92
-            s.stepi = params_.sigma0;
-            s.i = 1;
-            s.pimin = -1;
-        }
+        for (auto &s : sc) s = rosen_fresh_scal(params_.sigma0);
         scal_.upload(sc.data(), P);
     }
 
@@ -113,6 +110,7 @@ void RosenEngine::init(int n, const double *lower, const double *upper, const do
     d.cand = cand_.p; d.value = value_.p;
     d.aux = aux_.p; d.scal = scal_.p;
     inited_ = true;
+    inits_++;
 }
 
 void RosenEngine::launch_body(int mode, int k, bool begin)

@@ -64,11 +64,22 @@ struct RosenScal {
     long long walk_ticks, orth_ticks;
 };
 
+// the scalars of a fresh start (:85-92): what init() uploads and rosen_rearm writes
+__host__ __device__ inline RosenScal rosen_fresh_scal(double step0)
+{
+    RosenScal s = {};
+    s.stepi = step0;
+    s.i = 1;
+    s.pimin = -1;
+    return s;
+}
+
 struct RosenConst {
     int n, ld;
     int obj, mfev, honor_stop, npop;
     int wide, repair;
     double tol, decf;
+    double step0;            // what a re-arm sets stepi to
 };
 
 struct RosenDev {
@@ -83,6 +94,7 @@ struct RosenDev {
 };
 
 class RosenEngine: public WalkEngine<RosenScal> {
+    friend class BhEngine;      // borrows the handle as its local minimiser (bbo_bh.hpp)
 public:
     static constexpr const char *HANDLE_NAME = "not a Rosenbrock handle";
     explicit RosenEngine(const bbo_params &p);
@@ -110,6 +122,7 @@ private:
     void launch_body(int mode, int k, bool begin);
 
     bbo_rosen_params rp_ {};
+    int inits_ = 0;          // bbo_init calls so far: a borrower notices a handle that was initialised behind its back
     RosenConst c_ {};
     RosenDev d_ {};
     DevBuf<double> x_, v_, vold_, dd_, x0_, x1_, cand_, value_;

@@ -26,6 +26,7 @@ __device__ inline double rosen_value(const RosenConst &c, const double *row, con
     return f != f ? ROSEN_INF : f;
 }
 
+#ifndef BBO_WALK_DEVICE_FUNCTIONS_ONLY   // (bbo_bh.hip takes the value function and the re-arm, not the kernels)
 // grid (P), 64 threads (the narrow form: the points of a batch in turn) or ROSEN_THREADS (the wide form: a
 // wavefront per point of a batch)
 //   mode   ROSEN_FUSED: evaluates inside and ends at the goal or a stop.  ROSEN_ADVANCE: walks to the next batch
@@ -329,7 +330,31 @@ __global__ __launch_bounds__(ROSEN_THREADS) void rosen_walk(RosenDev d, RosenCon
     s.walk_ticks += wall_clock64() - t_begin;
     if (tid == 0) d.scal[p] = s;
 }
+#endif
 
+// A fresh start of population p at `from` (n doubles), by the workgroup that calls it: exactly the state init()
+// uploads -- row 0 of x = from and its other rows zero, v the identity in rows 1 .. n, vold, d, x0 and x1 zero
+// (x1 is what a budget exit returns), the fresh scalars (stepi = step0, i = 1, pimin = -1, the counters and stop
+// zero).  cand and value are written by the walk before it reads them (BasinHopping's hops).
+__device__ inline void rosen_rearm(const RosenDev &d, const RosenConst &c, int p, const double *from, int tid, int nt)
+{
+    const int n = c.n, ld = c.ld;
+    const size_t pv = (size_t) p * ld, pm = (size_t) p * (n + 2) * ld;
+    for (int q = tid; q < (n + 2) * ld; q += nt) {
+        const int r = q / ld, j = q - r * ld;
+        d.x[pm + q] = r == 0 && j < n ? from[j] : 0.;
+        d.v[pm + q] = r >= 1 && r <= n && j == r - 1 ? 1. : 0.;
+        d.vold[pm + q] = 0.;
+    }
+    for (int q = tid; q < n + 2; q += nt) d.d[(size_t) p * (n + 2) + q] = 0.;
+    for (int j = tid; j < ld; j += nt) {
+        d.x0[pv + j] = 0.;
+        d.x1[pv + j] = 0.;
+    }
+    if (tid == 0) d.scal[p] = rosen_fresh_scal(c.step0);
+}
+
+#ifndef BBO_WALK_DEVICE_FUNCTIONS_ONLY
 // the built-in at every population's pending batch (bbo_rosen_phase 1).  grid (P), ROSEN_THREADS threads
 __global__ __launch_bounds__(ROSEN_THREADS) void rosen_eval(RosenDev d, RosenConst c)
 {
@@ -341,5 +366,6 @@ __global__ __launch_bounds__(ROSEN_THREADS) void rosen_eval(RosenDev d, RosenCon
     const double f = rosen_value(c, d.cand + ((size_t) p * ROSEN_BATCH + w) * c.ld, d.aux, lane);
     if (lane == 0) d.value[(size_t) p * ROSEN_BATCH + w] = f;
 }
+#endif
 
 } // namespace bbo

@@ -1502,3 +1502,314 @@ class APSO(MultivariateSearch):
         super().__init__(**ext)
         p = self._params
         p.mfev, p.tol, p.np, p.correct = int(mfev), float(tol), int(np), int(bool(correct))
+
+
+class BasinHopping_StepStrategy:
+    """BasinHopping_StepStrategy(stepsize) -- StepsizeStrategy, :83-85 (basinhopping.cpp:46-60): a hop moves every
+    coordinate by stepsize U[-1, 1) (upper - lower) and clamps it to the box less 5 % on each side.  The object is
+    the caller's: BasinHopping reads `stepsize` (and an adaptive strategy's `nstep`, `naccept`) at initialize() and,
+    on a one-population handle, writes them back after optimize() / iterate() / run()."""
+    _adaptive = False
+
+    def __init__(self, stepsize):
+        self.stepsize = float(stepsize)
+        self.nstep = self.naccept = 0
+        if not _np.isfinite(self.stepsize):
+            raise ValueError("BasinHopping: stepsize must be finite")
+
+
+class BasinHopping_AdaptStrategy(BasinHopping_StepStrategy):
+    """BasinHopping_AdaptStrategy(stepsize=1., accept_rate=0.5, interval=5, factor=0.9) -- AdaptiveStepsizeStrategy,
+    :87-90 (basinhopping.cpp:62-94): every `interval` steps the step is divided by `factor` when more than
+    `accept_rate` of the hops so far were accepted, and multiplied by it otherwise.  Departures: interval < 1 and a
+    factor that is not finite and positive are refused."""
+    _adaptive = True
+
+    def __init__(self, stepsize=1., accept_rate=0.5, interval=5, factor=0.9):
+        super().__init__(stepsize)
+        self.accept_rate, self.interval, self.factor = float(accept_rate), int(interval), float(factor)
+        if self.interval < 1:
+            raise ValueError("BasinHopping: interval must be >= 1")
+        if not (_np.isfinite(self.factor) and self.factor > 0.):
+            raise ValueError("BasinHopping: factor must be finite and positive")
+        if self.accept_rate != self.accept_rate:
+            raise ValueError("BasinHopping: accept_rate must not be NaN")
+
+
+class BasinHopping(MultivariateSearch):
+    """BasinHopping(minimizer, stepstrat, print=True, mit=99, temp=1.) -- :91-97 (basin hopping of Wales & Doye as
+    SciPy states it; basinhopping.cpp): a Metropolis chain whose every hop is a step of `stepstrat` from the
+    incumbent, a whole run of `minimizer` from there, one extra evaluation of what it returned, and the test
+    exp(min(0, -(new - old) / temp)) >= U[0, 1); temp = 0 accepts only what is not worse.  optimize() is init() and
+    `mit` hops and returns the best point, n_evals = the minimisations' counts + 1 each, converged = False always.
+    With a NelderMead or a Rosenbrock of this package as the minimizer the chain lives on the device: one chain per
+    population of the minimizer (`populations`, by default the minimizer's), re-armed there between hops, so no point,
+    value or decision crosses to the host; with a built-in objective the chains hop asynchronously, each starting its
+    next minimisation in the launch after its last one ended.  `lockstep=True` hops only when every minimisation has
+    ended (same results; the default is asynchronous except at n > 64 with at least 256 chains, as measured).  Every draw is addressed by (seed, substream + population, hop, coordinate), so a chain does
+    not depend on scheduling, the chunk sizes or `populations`.  initialize() is init() (log row -1), iterate() one
+    hop of every chain that has hops left, run(g) up to g.  get_state: "log" (rows of it, f, conv, step, accept,
+    f*, fev, the reference's table), "log_start" / "log_sol" (the start handed to the minimizer and what it
+    returned, per row), "log_fev", "x", "energy", "xbest", "fbest", "stepsize", "nstep", "naccept", "it", "fev",
+    "flag" (2: mit reached).  print=True prints the reference's table for population 0.
+    Reproduced literally: std::min(0., v) lets a NaN product accept (temp = 0 with equal energies); the strategy's
+    history is not reset by init(); a Rosenbrock minimizer that ends on its budget returns the ZERO vector, which
+    is evaluated and hopped from (that class's `repair=True` changes it).  Departures: a NaN energy counts as +inf;
+    a box that is not finite, temp < 0 and mit < 0 are refused.  NelderMead(minit=random) is refused on the device
+    (it would draw the same simplex on every hop).
+    Any other object with optimize(f, lower, upper, guess) -- and `native=False` for the two above -- takes the
+    Python-driven path: one population, the chain's arithmetic in Python on the same draws (bbo_bh_draws), the
+    minimizer called once per hop; run() raises there.  Extensions, in **ext: `seed`, `populations`, `poll_every`,
+    `lockstep`, `native`, `substream`, `device`."""
+    _algo = _ffi.ALGO_BASIN_HOPPING
+    _extension = "bh"
+    _accepts_program = False
+    MAX_N = 128
+    _WIDTHS = (5, 25, 5, 25, 6, 25, 10)     # basinhopping.cpp:148
+
+    def __init__(self, minimizer, stepstrat, print=True, mit=99, temp=1., **ext):
+        lockstep, native = ext.pop("lockstep", None), ext.pop("native", None)
+        substream = int(ext.pop("substream", 0))
+        if not isinstance(stepstrat, BasinHopping_StepStrategy):
+            raise TypeError("stepstrat must be a BasinHopping_StepStrategy or a BasinHopping_AdaptStrategy")
+        if not callable(getattr(minimizer, "optimize", None)):
+            raise TypeError("minimizer must have optimize(f, lower, upper, guess)")
+        walks = isinstance(minimizer, (NelderMead, Rosenbrock))
+        if native and not walks:
+            raise ValueError("BasinHopping: only NelderMead and Rosenbrock of this package are native minimizers")
+        self._native = walks if native is None else bool(native)
+        if self._native:
+            ext.setdefault("populations", minimizer._params.populations)
+            ext.setdefault("device", minimizer._params.device)
+        super().__init__(**ext)
+        if int(mit) < 0:
+            raise ValueError("BasinHopping: mit must be >= 0")
+        if not float(temp) >= 0.:
+            raise ValueError("BasinHopping: temp must be >= 0")
+        if not 0 <= substream < 1 << 24:
+            raise ValueError("BasinHopping: substream must be in [0, 2^24)")
+        p = self._params
+        if self._native:
+            if minimizer._params.populations != p.populations:
+                raise ValueError("BasinHopping: the minimizer must hold as many populations as there are chains "
+                                 "(populations=%d, the minimizer's %d)" % (p.populations, minimizer._params.populations))
+            if minimizer._params.device != p.device:
+                raise ValueError("BasinHopping: the minimizer must live on the same device")
+            if isinstance(minimizer, NelderMead) and minimizer._nm.minit == int(NelderMead.random):
+                raise ValueError("BasinHopping: NelderMead(minit=random) draws its simplex by the restart count alone, "
+                                 "the same one on every hop: it is no native minimizer (use another minit, or native=False)")
+        elif p.populations != 1:
+            raise ValueError("BasinHopping: the Python-driven path holds one population")
+        self._minimizer, self._stepstrat = minimizer, stepstrat
+        self._minimizer_handle = None
+        self._table = None
+        self._py = None
+        s = self._bh = _ffi.BhParams()
+        _ffi.lib().bbo_bh_params_default(C.byref(s))
+        s.print, s.mit, s.temp = int(bool(print)), int(mit), float(temp)
+        s.lockstep, s.substream = -1 if lockstep is None else int(bool(lockstep)), substream
+        self._read_strategy()
+
+    def _read_strategy(self):
+        s, st = self._bh, self._stepstrat
+        s.stepsize, s.adaptive = float(st.stepsize), int(st._adaptive)
+        s.nstep0, s.naccept0 = int(st.nstep), int(st.naccept)
+        if st._adaptive:
+            s.accept_rate, s.interval, s.factor = float(st.accept_rate), int(st.interval), float(st.factor)
+
+    def _write_strategy(self):
+        if self._params.populations == 1 and self._handle is not None:
+            st = self._stepstrat
+            st.stepsize = float(self.get_state("stepsize")[0])
+            st.nstep, st.naccept = int(self.get_state("nstep")[0]), int(self.get_state("naccept")[0])
+
+    # -- the handle borrows the minimizer's ------------------------------------------------
+    def _create(self):
+        h = C.c_void_p()
+        mh = self._minimizer._ensure_handle()
+        _ffi.check(_ffi.lib().bbo_create_basin(C.byref(self._params), mh, C.byref(h)))
+        self._minimizer_handle = mh
+        return h
+
+    def _ensure_handle(self):
+        # (as the restart drivers: a minimizer that re-created its handle leaves this one stale)
+        if self._handle is not None and self._minimizer._handle is not self._minimizer_handle:
+            _ffi.lib().bbo_destroy(self._handle)
+            self._handle = None
+        return super()._ensure_handle()
+
+    def _live(self):
+        if self._handle is not None and self._minimizer._handle is not self._minimizer_handle:
+            raise RuntimeError("the minimizer was re-created (reseed) after this BasinHopping was initialized: call "
+                               "initialize() / optimize() again")
+
+    def _problem(self, f, lower, upper, guess):
+        n, lower, upper, guess = super()._problem(f, lower, upper, guess)
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("BasinHopping: dimension must be in [1, %d]" % self.MAX_N)
+        self._require_finite_box(n, lower, upper, "BasinHopping: a step is a fraction of upper - lower")
+        return n, lower, upper, guess
+
+    # -- the reference's methods -------------------------------------------------------------
+    def initialize(self, f, lower, upper, guess):
+        if not self._native:
+            return self._py_initialize(f, lower, upper, guess)
+        n, lower, upper, guess = self._problem(f, lower, upper, guess)
+        self._read_strategy()
+        h = self._ensure_handle()
+        L = _ffi.lib()
+        self._check(L.bbo_bh_configure(h, C.byref(self._bh)))
+        if self._bh.print:
+            sys.stdout.flush()      # the table is written by the library
+        self._minimizer._binding, self._minimizer._n = self._binding, n      # (its engine calls the same objective)
+        self._check(L.bbo_init(h, n, lower, upper, guess, C.byref(self._binding.struct)))
+        if self._table is not None:
+            self._inject("bbo_bh_inject_draws", self._table)
+        self._write_strategy()
+
+    def optimize(self, f, lower, upper, guess):
+        self.initialize(f, lower, upper, guess)
+        if not self._native:
+            while self._py["it"] < self._bh.mit:
+                self._py_hop()
+            return self.solution()
+        self.run(self._bh.mit)
+        return self.solution()
+
+    def iterate(self):
+        if not self._native:
+            if self._py is None:
+                raise RuntimeError("iterate() called before initialize()")
+            if self._py["it"] < self._bh.mit:
+                self._py_hop()
+            return
+        self._live()
+        super().iterate()
+        self._write_strategy()
+
+    def run(self, max_generations):
+        if not self._native:
+            raise RuntimeError("run() needs a device-resident minimizer: with a Python-driven minimizer the chain "
+                               "advances in Python (iterate())")
+        self._live()
+        done = super().run(max_generations)
+        self._write_strategy()
+        return done
+
+    def solution(self, population=0):
+        if self._native:
+            return super().solution(population)
+        if self._py is None:
+            raise RuntimeError("solution() called before initialize()")
+        return MultivariateSolution(self._py["xbest"], self._py["fev"], False)
+
+    def phase(self, which):
+        """0 every idle chain with hops left takes its step and re-arms its minimizer (which then walks through its
+        own handle), 1 collect the results of the minimisations that have stopped, 2 evaluate the pending energy
+        points, 3 decide"""
+        self._phase(which)
+
+    def inject_draws(self, table):
+        """the draws of the hops that follow instead of the generator: per hop n step uniforms in [-1, 1) and one
+        accept uniform in [0, 1), for every chain; None: the generator.  Before initialize() the table is kept and
+        injected there."""
+        self._table = None if table is None else _np.ascontiguousarray(_np.asarray(table, dtype=_np.float64)).ravel()
+        if self._native and self._handle is not None and self._n is not None:
+            self._inject("bbo_bh_inject_draws", self._table)
+
+    @staticmethod
+    def draws(seed, substream, hop, n):
+        """the n step uniforms and the accept uniform of one hop, as the device draws them (bbo_bh_draws)"""
+        out = _np.zeros(n + 1)
+        _ffi.check(_ffi.lib().bbo_bh_draws(int(seed) & 0xFFFFFFFFFFFFFFFF, int(substream), int(hop), int(n), out))
+        return out
+
+    # -- the Python-driven path ----------------------------------------------------------------
+    def get_state(self, key, population=0):
+        if self._native:
+            return super().get_state(key, population)
+        if self._py is None:
+            raise RuntimeError("get_state() called before initialize()")
+        py, st = self._py, self._stepstrat
+        one = {"energy": py.get("energy"), "fbest": py.get("fbest"), "stepsize": st.stepsize, "nstep": st.nstep,
+               "naccept": st.naccept, "it": py["it"], "fev": py["fev"], "n": self._n,
+               "flag": 2 if py["it"] >= self._bh.mit else 0}
+        if key in one:
+            return _np.array([one[key]], dtype=_np.float64)
+        if key in ("x", "xbest", "log", "log_start", "log_sol", "log_fev"):
+            return _np.array(py[key], dtype=_np.float64).ravel()
+        raise KeyError("unknown state key %r" % key)
+
+    def _row(self, cells):
+        print("".join(" | " + (c if isinstance(c, str) else "%d" % c if isinstance(c, int) else "%.17g" % c).rjust(w)
+                      for c, w in zip(cells, self._WIDTHS)) + " | ")
+
+    def _py_minimize(self, start):
+        sol = self._minimizer.optimize(self._py["f"], self._py["lower"], self._py["upper"], start)
+        x = sol.x
+        f = self._py["f"]
+        e = float(f(x))
+        return x, (_np.inf if e != e else e), sol.n_evals, bool(sol.converged)
+
+    def _py_initialize(self, f, lower, upper, guess):
+        lower, upper, guess = _as_vec(lower, "lower"), _as_vec(upper, "upper"), _as_vec(guess, "guess")
+        n = lower.size
+        if not 1 <= n <= self.MAX_N:
+            raise ValueError("BasinHopping: dimension must be in [1, %d]" % self.MAX_N)
+        self._require_finite_box(n, lower, upper, "BasinHopping: a step is a fraction of upper - lower")
+        if not callable(f):
+            raise TypeError("the Python-driven path evaluates the energy on the host: the objective must be callable")
+        self._n = n
+        py = self._py = {"f": f, "lower": lower, "upper": upper[:n].copy(), "it": 0, "fev": 0,
+                         "log": [], "log_start": [], "log_sol": [], "log_fev": []}
+        x, e, fev, conv = self._py_minimize(guess[:n].copy())
+        py["x"], py["energy"], py["xbest"], py["fbest"] = x.copy(), e, x.copy(), e
+        py["fev"] += fev + 1
+        st = self._stepstrat
+        py["log"].append([-1., e, float(conv), st.stepsize, 1., e, float(py["fev"])])
+        py["log_start"].append(guess[:n].copy()), py["log_sol"].append(x.copy()), py["log_fev"].append(fev)
+        if self._bh.print:
+            self._row(["it", "f", "conv", "step", "accept", "f*", "fev"])
+            print(" |" + "=" * (sum(self._WIDTHS) + 3 * (len(self._WIDTHS) - 1) + 2) + "| ")
+            self._row([-1, e, int(conv), st.stepsize, 1, e, py["fev"]])
+
+    def _py_hop(self):
+        """iterate() of the reference (basinhopping.cpp:155-190) in its operation order, on the device's draws"""
+        py, st, n = self._py, self._stepstrat, self._n
+        hop = py["it"]
+        if self._table is not None and (hop + 1) * (n + 1) <= self._table.size:
+            u = self._table[hop * (n + 1):(hop + 1) * (n + 1)]
+        else:
+            u = self.draws(self._params.seed, self._bh.substream, hop, n)
+        if st._adaptive:
+            st.nstep += 1
+            if st.nstep % st.interval == 0:
+                if (1. * st.naccept) / st.nstep > st.accept_rate:
+                    st.stepsize /= st.factor
+                else:
+                    st.stepsize *= st.factor
+        x1 = py["x"].copy()
+        lo, up = py["lower"], py["upper"]
+        for i in range(n):
+            x1[i] += st.stepsize * u[i] * (up[i] - lo[i])
+            margin = 0.05 * (up[i] - lo[i])
+            hi, lw = up[i] - margin, lo[i] + margin
+            t = hi if hi < x1[i] else x1[i]
+            x1[i] = t if lw < t else lw
+        x, e, fev, conv = self._py_minimize(x1.copy())
+        py["fev"] += fev + 1
+        beta = _np.inf if self._bh.temp == 0. else 1. / self._bh.temp
+        with _np.errstate(invalid="ignore"):
+            v = -(_np.float64(e) - _np.float64(py["energy"])) * _np.float64(beta)
+        accept = bool(_np.exp(v if v < 0. else 0.) >= u[n])
+        if accept:
+            py["energy"], py["x"] = e, x.copy()
+            if st._adaptive:
+                st.naccept += 1
+        if e < py["fbest"]:
+            py["fbest"], py["xbest"] = e, x.copy()
+        py["log"].append([float(hop), e, float(conv), st.stepsize, float(accept), py["fbest"], float(py["fev"])])
+        py["log_start"].append(x1), py["log_sol"].append(x.copy()), py["log_fev"].append(fev)
+        if self._bh.print:
+            self._row([hop, e, int(conv), st.stepsize, int(accept), py["fbest"], py["fev"]])
+        py["it"] += 1

@@ -69,7 +69,8 @@ typedef enum {
     BBO_ALGO_MAYFLY = 24,      /* MayflySearch src/multivariate/mayfly/mayfly.h       */
     BBO_ALGO_PIKAIA = 25,      /* PikaiaSearch src/multivariate/pikaia/pikaia.h       */
     BBO_ALGO_NELDER_MEAD = 26, /* NelderMead   src/multivariate/simplex/nelder_mead.h */
-    BBO_ALGO_ROSENBROCK = 27   /* Rosenbrock   src/multivariate/rosenbrock/rosenbrock.h */
+    BBO_ALGO_ROSENBROCK = 27,  /* Rosenbrock   src/multivariate/rosenbrock/rosenbrock.h */
+    BBO_ALGO_BASIN_HOPPING = 28 /* BasinHopping src/multivariate/basin/basinhopping.h  */
 } bbo_algo;
 
 /* Built-in objectives evaluated on the device (the reference ships none; id 1 is
@@ -860,6 +861,50 @@ typedef struct { double decf; int repair, wide, substream; } bbo_rosen_params;
 void bbo_rosen_params_default(bbo_rosen_params *p);   /* 0.1, 0, -1, 0 */
 int bbo_rosen_configure(bbo_handle h, const bbo_rosen_params *p);
 int bbo_rosen_phase(bbo_handle h, int phase);
+
+/* ---- BasinHopping (BBO_ALGO_BASIN_HOPPING): BasinHopping(minimizer,stepstrat,print=True,mit=99,temp=1.) with
+ * BasinHopping_StepStrategy(stepsize) / BasinHopping_AdaptStrategy(stepsize=1.,accept_rate=0.5,interval=5,factor=0.9)
+ * py/multivariate_py.cpp:83-97, basinhopping.cpp.  Metropolis chains whose every hop is a whole local minimisation:
+ * a step of stepsize U[-1,1) (upper - lower) per coordinate clamped to the box less 5 % on each side, the minimiser
+ * from there, one extra evaluation of what it returned, exp(min(0, -(new - old) / temp)) >= U[0,1).
+ * bbo_create_basin borrows `minimizer`, a BBO_ALGO_NELDER_MEAD or BBO_ALGO_ROSENBROCK handle of this library with the
+ * same populations and device; it stays owned by the caller, must outlive the handle and is driven by it (its
+ * state is the last minimisation's).  One chain per population, re-armed on the device between hops (DESIGN.md
+ * section 3.21).  BBO_ERR_ARG: another handle, mismatched populations / device, NelderMead with minit = random (it
+ * addresses its draws by the restart count alone and would draw the same simplex on every hop); at bbo_bh_configure
+ * interval < 1, factor not finite and positive, temp < 0, mit < 0; at bbo_init a box that is not finite, n > 128,
+ * an objective program.  A NaN energy counts as +inf.  params: seed, device, populations, poll_every (rounds of walk
+ * chunk + hop between polls of the finished chains; 0: 8).
+ * bbo_init is init(): the first minimisation from the guess and log row -1.  bbo_iterate is one hop of every chain
+ * that has hops left, bbo_run(g) up to g, bbo_optimize init and hops to mit; converged is always 0, n_evals the sum of
+ * the minimisations' counts + 1 each.  With a built-in objective the chains hop asynchronously (lockstep = 1: a hop
+ * only when every minimisation has stopped; same results; -1, the default, takes 1 at n > 64 with at least 256
+ * chains, as measured); with a callable the minimiser's host loop runs to every
+ * population's stop, then one host batch values the energy points.  Every draw is addressed by (seed, substream +
+ * population, hop, coordinate or the accept slot): a chain does not depend on scheduling or on `populations`.
+ * nstep0 / naccept0: the history of an adaptive strategy that has been used before (the reference's init() resets
+ * none of it).  print: the reference's table for population 0, rows as the polls discover them.
+ * bbo_bh_phase: 0 every idle chain with hops left takes its step and re-arms its minimiser, 1 collect the stopped
+ * minimisations' results, 2 evaluate the pending energy points, 3 decide.
+ * bbo_bh_inject_draws (after bbo_init): per hop n step uniforms in [-1, 1) and one accept uniform in [0, 1), consumed
+ * by every chain instead of Philox while the table covers the hop; NULL ends it.  bbo_bh_draws: the same n + 1
+ * uniforms of (seed, substream, hop) computed on the host; needs no handle and no device.
+ * State: "x" "energy" "xbest" "fbest" "stepsize" "nstep" "naccept" "it" "fev" "flag" (0 running, 2 mit reached)
+ * "log" ((it + 1) x 7: it, f, conv, step, accept, f*, fev) "log_start" "log_sol" ((it + 1) x n: the start handed to
+ * the minimiser and what it returned) "log_fev" "xtrial" "xsol" "stage" "pending" "lockstep" "n" "profile".
+ * Writable between hops: "x" "energy" "stepsize" "nstep" "naccept"; "profile".  A minimiser that is initialised again on its own
+ * after bbo_init (another problem, a run of its own) leaves the handle stale: every call returns BBO_ERR_STATE until
+ * the next bbo_init.  "xtrial" "xsol" "stage" "pending" are what a caller of bbo_bh_phase reads between its steps. */
+typedef struct {
+    double stepsize; int adaptive; double accept_rate; int interval; double factor, temp;
+    int mit, print, lockstep, substream, nstep0, naccept0;
+} bbo_bh_params;
+void bbo_bh_params_default(bbo_bh_params *p);   /* 1., 1, 0.5, 5, 0.9, 1., 99, 1, -1, 0, 0, 0 */
+int bbo_create_basin(const bbo_params *params, bbo_handle minimizer, bbo_handle *out);
+int bbo_bh_configure(bbo_handle h, const bbo_bh_params *p);
+int bbo_bh_phase(bbo_handle h, int phase);
+int bbo_bh_inject_draws(bbo_handle h, const double *table, int count);
+int bbo_bh_draws(uint64_t seed, int substream, int hop, int n, double *out);
 
 /* ---- diagnostics -------------------------------------------------------------------------------
  * bbo_probe_objective: built-in `objective` at `rows` points of `n` coordinates (X, rows x n, host

@@ -4,6 +4,7 @@
 # (the engines outside bench.py have their own scripts, one JSON line per measurement:
 #  bench_spiral.py, bench_hees.py, bench_nshs.py, bench_lm.py, bench_xnes.py, bench_amalgam.py,
 #  bench_slpso.py, bench_crs.py, bench_ssde.py, bench_mayfly.py, bench_pikaia.py, bench_neldermead.py, bench_rosenbrock.py,
+#  bench_basinhopping.py,
 #  bench_program_objective.py)
 TAG=$1; shift
 WLS=${@:-"M C1 C3 C2 JADE SANSDE SEP CSO CCPSO C4 C5"}
